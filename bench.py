@@ -2,23 +2,28 @@
 """bench.py -- BASELINE.json metric ("leaf proofs/sec (whole node) + NTT GB/s vs HBM peak, 2^20-row table build") on MI355X.
 
     python bench.py --gpus N --steps K --warmup W            (N > 1 without a launcher: starts its own N ranks)
+    python bench.py --gpus N --steps K --warmup W --full     (the same headline, then every check and side leg below)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-Default workload (`--workload table`, run_table below): BASELINE configs[3] as ONE contiguous block of table rows per rank. Without
-`--rows` (the driver's command) the block is 2^17 rows -- a step is 1/`--steps` of it -- so that `--gpus 8` builds the metric's
-whole 2^20-row table (8 blocks + 7 separator rows, three join levels) and 1 / 2 / 4 GPUs the same block per rank; with `--rows R` a
-step is R rows and the block `--steps` x R. The warm-up block is `--warmup` steps, at most 5120 rows. One work plan per block.
+Default workload (`--workload table`, run_table below): BASELINE configs[3] as ONE contiguous block of `--steps` x `--rows` table rows
+per rank. A step is `--rows` rows, 1024 when `--rows` is not given, so that the timed work grows with `--steps`: `--steps 128` gives
+every rank a 2^17-row block and `--gpus 8 --steps 128` builds the metric's whole 2^20-row table (8 blocks + 7 separator rows, three
+join levels). The warm-up block is `--warmup` steps, at most 5120 rows. One work plan per block.
+
+A plain run does what the headline needs and nothing else: set-up, warm-up, the timed block, `--dump-outputs DIR` if given (the
+block root proof as .npy files, see dump_outputs), the JSON line. The self-check, the CPU baseline, the side legs and the kernel legs
+described below run with `--full` only.
 Per row the reference proves 4 cells-tree nodes and 1 row-tree node, each a framework proof (witness generation, base prove(),
 wrap chain to 2^12 rows: recursion-framework/src/circuit_builder.rs:286-311, wrap_circuit.rs:122-148); here they are REAL
 circuits with the reference's tree logic (mapreduce-plonky2_amd/table.py), their witnesses replayed on the device
 (mp2g_witness_program_run_dev), the row tree scheduled by ryhope's batched work plan (mp2g_update_plan_*), the rows' multiset
-digests computed inside the timed region. value = framework proofs per second (5 per row). At N = 1 the same JSON line carries BASELINE's other single-GPU configurations:
+digests computed inside the timed region. value = framework proofs per second (5 per row). With `--full` at N = 1 the same JSON line carries BASELINE's other single-GPU configurations:
 `config2` = configs[2] at full size (1024 real leaf proofs aggregated 2-to-1: 2047 framework proofs), `by_base_degree` = the table
 rate with every base circuit padded to 2^k rows, k = 12..15, and carrying the reference's leaf gate set (the
 reference's real base degrees lie there), `leaves_prove_only` = round 2's headline (`--workload leaves`: prove() only, synthetic
 circuits, resident witnesses), `roofline` = configs[1].
 
-Self-check. After the timed region: the block root's public inputs = the off-circuit tree hash / multiset digest / min / max and the
+Self-check (`--full`). After the timed region: the block root's public inputs = the off-circuit tree hash / multiset digest / min / max and the
 root passes the oracle's verifier; one framework proof of every circuit kind of the timed block is re-proved from its captured
 witness by the CPU oracle -- caps, openings and FRI proof bit for bit, and accepted by its verifier (transcript, PLONK identity with
 the gate terms, FRI). "verified": k counts those prove() calls; any mismatch makes the run fail. The oracle proofs of that leg are
@@ -29,8 +34,8 @@ move one final proof each, device to device over RCCL. Before anything is timed 
 buffer the same way (sharding.probe_handoff); if that fails anywhere, all levels use the staged hand-off (download + torch tensor)
 and `config.sharding` says so.
 
-The NTT half of the metric is the `roofline` object: BASELINE configs[1]'s 2^22-point forward NTT, timed with HIP events on the
-context's stream in this same run, algorithmic 16 B/point.
+The NTT half of the metric is the `roofline` object (`--full`): BASELINE configs[1]'s 2^22-point forward NTT, timed with HIP events on
+the context's stream in this same run, algorithmic 16 B/point.
 
 Other workloads: leaves (above), tree (synthetic circuits + aggregation levels), recursion (map-reduce trees of real proofs + the
 final Poseidon wrap), ntt (the roofline leg alone, for rocprof).
@@ -105,6 +110,16 @@ class ClockReader:
             except Exception:
                 self.p.kill()
             self.p = None
+
+
+class NoClocks:
+    """a plain run of the table workload reads no clocks: ClockReader's helper process is started for `--full` and the other workloads"""
+
+    def read(self, device):
+        return None
+
+    def close(self):
+        pass
 
 
 class CpuFarm:
@@ -890,13 +905,18 @@ def main(argv=None):
     ap.add_argument("--witness-check", action="store_true",
                     help="also run the device-side witness check (gate + copy constraints on H) inside every prove, "
                          "as plonky2's prove() does before it panics on a bad witness")
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the timed CPU leg (the self-check still runs)")
-    ap.add_argument("--no-verify", action="store_true", help="skip the oracle self-check of the sampled proofs")
-    ap.add_argument("--cpu-budget", type=float, default=20.0, help="seconds of CPU oracle work for the cpu_baseline sample")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the timed CPU leg (the self-check still runs; --workload table: with --full)")
+    ap.add_argument("--no-verify", action="store_true", help="skip the oracle self-check of the sampled proofs (--workload table: with --full)")
+    ap.add_argument("--cpu-budget", type=float, default=20.0, help="seconds of CPU oracle work for the cpu_baseline sample (--workload table: with --full)")
     ap.add_argument("--trees", type=int, default=8, help="--workload recursion: independent trees per rank and step, one host thread + GPU stream each")
-    ap.add_argument("--rows", type=int, default=None, help="--workload table: table rows per rank and step (5 framework proofs each). Unset (the driver's command): the "
-                    "rank's block is 2^17 rows whatever --steps says -- a step is 1/steps of it -- so that 8 ranks build the metric's 2^20-row table (8 x 2^17 rows + 7 "
-                    "separator rows) and 1 / 2 / 4 ranks the same block per rank (weak scaling that ends on the named configuration); see block_plan()")
+    ap.add_argument("--rows", type=int, default=None, help="--workload table: table rows per rank and step (5 framework proofs each). Unset: 1024 rows a step, so "
+                    "that --steps 128 gives every rank a 2^17-row block and 8 ranks the metric's 2^20-row table (8 x 2^17 rows + 7 separator rows); see block_plan()")
+    ap.add_argument("--full", action="store_true", help="after the headline, everything else the line reports: the self-check against the CPU oracle, cpu_baseline, "
+                    "the whole-table digest, the kernel legs (roofline, sponge, commit, roofline_alu), config2, by_base_degree, --leaves-leg, the clocks. Off: the "
+                    "run sets up, warms up, times the steps, writes --dump-outputs and prints the line. (--workload table; the other workloads and --resume-dir "
+                    "always run their own checks)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="--workload table: after the timed steps write what the timed block returned -- its root proof "
+                    "(public inputs, caps, openings, FRI proof) -- as DIR/<name>.npy, float64 (see dump_outputs)")
     ap.add_argument("--workers", type=int, default=4, help="--workload table: concurrent work-plan items per rank, one host thread + GPU stream + prover set each")
     ap.add_argument("--table-batch", type=int, default=48, help="--workload table: proofs per prove() launch sequence of a worker (round 5: 4 x 48 in flight does 912 proofs/s "
                     "where 4 x 32 does 842 -- the per-batch latency kernels, witness replay, transcript, tree tops, are paid once per 48 proofs; profiles/r05/variants_ab.txt -- and "
@@ -912,17 +932,17 @@ def main(argv=None):
                     "instead of on the device (mp2g_witness_program_run_dev, the default): the A/B switch")
     ap.add_argument("--lean", action="store_true", help="--workload table: keep only the frontier of the row tree in host memory (automatic above 16384 rows); the "
                     "self-check is then the root's public inputs and the oracle's verifier on the root, not the re-proving of sampled nodes")
-    ap.add_argument("--leaves-leg", action="store_true", help="--workload table at N = 1: also run the short prove()-only leg on synthetic circuits (round 2's headline, "
+    ap.add_argument("--leaves-leg", action="store_true", help="--workload table at N = 1 with --full: also run the short prove()-only leg on synthetic circuits (round 2's headline, "
                     "`leaves_prove_only`); off by default since round 6: the driver's window goes to the 2^17-row block")
     ap.add_argument("--no-leaves-leg", action="store_true", help="(the default now; kept so that older command lines still parse)")
     ap.add_argument("--pad-base-bits", type=int, default=0, help="--workload table: pad every base circuit of both circuit sets to 2^k rows (no-op rows) and give it "
                     "the reference's leaf gate set (SURVEY 8(d): base degrees k = 12..15); 0 = the circuits' natural degrees (the headline)")
-    ap.add_argument("--degree-sweep", default="12,13,14,15", help="--workload table at N = 1: after the headline, the table rate at these base degrees (one block of "
+    ap.add_argument("--degree-sweep", default="12,13,14,15", help="--workload table at N = 1 with --full: after the headline, the table rate at these base degrees (one block of "
                     "--sweep-rows rows each) in the same line as `by_base_degree`; '' = skip")
     ap.add_argument("--sweep-rows", type=int, default=1024, help="rows of the block timed at every base degree of --degree-sweep (halved above k = 14)")
     ap.add_argument("--sweep-runs", type=int, default=2, help="builds of that block per base degree; the median is reported (of two builds: the later one, the first still grows buffers). "
                     "Round 5 ran 3; 2 keeps the driver's N = 1 command inside its window now that the timed block is 2^17 rows")
-    ap.add_argument("--config2-leaves", type=int, default=1024, help="--workload table at N = 1: leaves of the BASELINE configs[2] leg (2-to-1 aggregation of real leaf proofs, "
+    ap.add_argument("--config2-leaves", type=int, default=1024, help="--workload table at N = 1 with --full: leaves of the BASELINE configs[2] leg (2-to-1 aggregation of real leaf proofs, "
                     "2 x leaves - 1 framework proofs) reported as `config2`; 0 = skip")
     ap.add_argument("--resume-dir", default=None, help="--workload table at N = 1: build the table as --table-blocks blocks of --steps x --rows rows ACROSS CALLS -- every "
                     "block's root proof is kept in this directory as ProofWithVK bytes (mapreduce-plonky2_amd/proofstore.py: the reference's proof store, "
@@ -943,11 +963,14 @@ def main(argv=None):
     if args.resume_dir and (args.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1):
         raise SystemExit("bench.py: --resume-dir builds the blocks one after another on ONE GPU (the single-GPU rehearsal of the N-rank run); "
                          "with N GPUs every rank builds its block in one call: drop --resume-dir and pass --gpus N")
+    if args.dump_outputs and (args.workload != "table" or args.resume_dir):
+        raise SystemExit("bench.py: --dump-outputs writes the root proof of the timed table block: --workload table without --resume-dir")
     if args.gpus > 1 and "RANK" not in os.environ:
         return launch_ranks(args.gpus, sys.argv[1:] if argv is None else list(argv))
-    clocks = ClockReader()  # before anything initialises the GPU
+    plain = args.workload == "table" and not args.resume_dir and not args.full  # the headline alone: no helper processes, no side legs
+    clocks = NoClocks() if plain else ClockReader()  # before anything initialises the GPU
     # the CPU baseline's process farm (N = 1 only, like cpu_baseline itself): its helper too must exist before the GPU is touched
-    farm = CpuFarm() if (args.workload == "table" and not args.resume_dir and not args.no_cpu_baseline and not args.no_verify
+    farm = CpuFarm() if (args.workload == "table" and args.full and not args.resume_dir and not args.no_cpu_baseline and not args.no_verify
                          and int(os.environ.get("WORLD_SIZE", "1")) == 1) else None
 
     rank = int(os.environ.get("RANK", "0"))
@@ -1408,25 +1431,45 @@ def config2_leg(rig, n_leaves, seed=0xC0FFEE03):
             "setup_s": round(setup_s, 1), "root_verified": True, "root_public_inputs": [int(x) for x in pis]}
 
 
-DEFAULT_BLOCK_ROWS = 1 << 17   # rows of one rank's block when --rows is not given: 8 ranks x 2^17 = BASELINE configs[3]'s 2^20-row table
+DEFAULT_STEP_ROWS = 1024      # rows of a step when --rows is not given: 128 steps = a 2^17-row block, 8 ranks x 2^17 = BASELINE configs[3]'s 2^20-row table
 WARMUP_ROWS_CAP = 5120         # the warm-up block creates the provers of every circuit; more rows than this add nothing to that
 
 
-def block_plan(rows, steps, warmup, default_rows=None):
-    """Rows of a rank's timed block and of its warm-up block. `rows` given: steps x rows (a step = `rows` rows). `rows` None: the block
-    is `default_rows` rows (2^17; MP2G_BENCH_BLOCK_ROWS scales the default down for tests) and a step is 1/steps of it -- steps - 1
-    steps of ceil(block / steps) rows and a shorter last one; the block is ONE work plan either way, steps are only the unit of
-    ms_per_step. The warm-up block is warmup steps, never more than WARMUP_ROWS_CAP rows. Returns (block rows, rows per step, warm-up rows)."""
+def block_plan(rows, steps, warmup, default_step_rows=None):
+    """Rows of a rank's timed block and of its warm-up block: the block is steps x (rows per step), a step `rows` rows or, with `rows`
+    None, `default_step_rows` (DEFAULT_STEP_ROWS; MP2G_BENCH_STEP_ROWS scales the default down for tests). The block is ONE work plan,
+    steps are the unit of the timed work and of ms_per_step. The warm-up block is warmup steps, never more than WARMUP_ROWS_CAP rows.
+    Returns (block rows, rows per step, warm-up rows)."""
     steps = max(1, int(steps))
     if rows is None:
-        n_rows = int(default_rows if default_rows is not None else os.environ.get("MP2G_BENCH_BLOCK_ROWS", DEFAULT_BLOCK_ROWS))
-        assert n_rows >= 1
-        per_step = -(-n_rows // steps)
+        per_step = int(default_step_rows if default_step_rows is not None else os.environ.get("MP2G_BENCH_STEP_ROWS", DEFAULT_STEP_ROWS))
     else:
         per_step = int(rows)
-        n_rows = steps * per_step
+    assert per_step >= 1
+    n_rows = steps * per_step
     warm = min(max(0, int(warmup)) * per_step, WARMUP_ROWS_CAP)
     return n_rows, per_step, warm
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, proof):
+    """--dump-outputs: what a caller of the timed block receives -- its root proof (caps, openings, FRI proof, public inputs; with
+    several ranks the joined tree's) -- as DIR/root_<part>.npy. The parts are Goldilocks words (u64); float64 holds them exactly as
+    two 32-bit halves, so every file has the part's own shape plus a last axis [low 32 bits, high 32 bits]. The inputs of a run are
+    fixed by its arguments (seeded), so two builds of the project can be compared file for file. Returns the files written."""
+    os.makedirs(path, exist_ok=True)
+    parts = {"root_caps": proof[0], "root_openings": proof[1], "root_fri_proof": proof[2], "root_public_inputs": proof[3]}
+    arrays = {}
+    for name, words in parts.items():
+        w = np.ascontiguousarray(words, dtype=np.uint64)
+        arrays[name] = np.stack([(w & np.uint64(0xFFFFFFFF)).astype(np.float64), (w >> np.uint64(32)).astype(np.float64)], axis=-1)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, f"--dump-outputs: {total} bytes exceed {DUMP_LIMIT_BYTES}"
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return sorted(arrays)
 
 
 def run_table(args, rank, local_rank, world, dist, torch, VARIANT, clocks, farm=None):
@@ -1442,15 +1485,16 @@ def run_table(args, rank, local_rank, world, dist, torch, VARIANT, clocks, farm=
     -- value digests, their accumulation up both trees, row ids (mp2g_map_to_curve_batch, mp2g_row_digests, mp2g_curve_sum_ranges) --
     is inside the timed region too.
 
-    A STEP is `--rows` rows (5 x rows framework proofs); without `--rows` the block is 2^17 rows and a step 1/K of it (block_plan).
+    A STEP is `--rows` rows (5 x rows framework proofs), 1024 without `--rows` (block_plan).
     The W warm-up steps are one contiguous block of W steps' rows, 5120 at most (other rows than the timed ones; it creates the
     provers), the K timed steps one contiguous block -- one work plan, a row tree log2(rows) deep -- not K rebuilds of the same rows. With several ranks every rank builds its own block and log2(ranks) join
     levels follow inside the timed region: the owner of a parent receives the other block's root proof (device to device over RCCL)
     and proves the separator row between the blocks. value = framework proofs per second.
 
-    After the timed region: the root's public inputs are compared with the off-circuit tree hash / digest / min / max and the root
-    passes the oracle's verifier; one framework proof of every circuit kind is re-proved from its captured witness by the CPU oracle
-    -- bit-exact and verified; those oracle proofs are the cpu_baseline sample. At N = 1 the same line then carries: BASELINE
+    After the timed region: `--dump-outputs` writes the root proof (rank 0). With `--full`: the root's public inputs are compared with
+    the off-circuit tree hash / digest / min / max and the root passes the oracle's verifier; one framework proof of every circuit kind
+    is re-proved from its captured witness by the CPU oracle -- bit-exact and verified; those oracle proofs are the cpu_baseline
+    sample. With `--full` at N = 1 the same line then carries: BASELINE
     configs[2] at full size (`config2`), the table rate at base degrees k = 12..15 (`by_base_degree`: every base circuit padded to
     2^k rows with the reference's leaf gate set), the prove()-only loop of round 2 (`leaves_prove_only`), the kernel
     legs (`roofline` = configs[1]'s 2^22-point NTT) and the whole-table multiset digest of 2^20 rows."""
@@ -1465,7 +1509,7 @@ def run_table(args, rank, local_rank, world, dist, torch, VARIANT, clocks, farm=
     mods = (mp2, R, FW, C, T, IX)
     n_cols, seed = 4, 0xC0FFEE04
     ranks_here = int(os.environ.get("LOCAL_WORLD_SIZE", world))
-    oracle_build = native_oracle() if world == 1 and not args.no_cpu_baseline and not args.no_verify else None  # before tests/oracle.py is first imported
+    oracle_build = native_oracle() if args.full and world == 1 and not args.no_cpu_baseline and not args.no_verify else None  # before tests/oracle.py is first imported
     rig = TableRig(mods, local_rank, VARIANT, args.workers, args.table_batch, args.subtree, args.host_witness, ranks_here, pad_bits=args.pad_base_bits,
                    group_rows=args.group_rows, native=args.native_build)
     params, ctx = rig.params, rig.ctx
@@ -1568,12 +1612,16 @@ def run_table(args, rank, local_rank, world, dist, torch, VARIANT, clocks, farm=
         dt, n_total = float(t[0].item()), int(t[1].item())
     else:
         n_total = n_local
+    if args.dump_outputs and rank == 0:  # what the timed block returned: the root proof (the joined tree's with several ranks)
+        dump_outputs(args.dump_outputs, cur[0])
 
-    # ---- checks (outside the timed region) ---------------------------------------------------------------------------------
+    # ---- checks (outside the timed region; --full) -------------------------------------------------------------------------
     # every rank: its block's root exposes the off-circuit tree hash, multiset digest, min / max of the block; the oracle verifies it
-    want, w_all = rig.check_root(st, verify=not args.no_verify)
-    verified, cpu_base, medians = (0 if args.no_verify else 1), None, None
-    if rank == 0 and world > 1:  # the joined tree: digest = the whole table's (blocks and separators), min of block 0
+    verified, cpu_base, medians = 0, None, None
+    if args.full:
+        want, w_all = rig.check_root(st, verify=not args.no_verify)
+        verified = 0 if args.no_verify else 1
+    if args.full and rank == 0 and world > 1:  # the joined tree: digest = the whole table's (blocks and separators), min of block 0
         root_pis = cur[0][3]
         ws = [w_all]
         for r in range(1, world):
@@ -1584,7 +1632,7 @@ def run_table(args, rank, local_rank, world, dist, torch, VARIANT, clocks, farm=
             ws.append(mp2.compute_table_row_digest(ctx, tb.col_ids, tb.values, tb.values[:, 0:1])[0])
         assert np.array_equal(mp2.curve_sum(ctx, np.stack(ws), weierstrass=True)[1], root_pis[4:15]), "root digest != digest of the whole table"
         assert np.array_equal(root_pis[26:34], want[26:34]), "root min != min of block 0"
-    if not args.no_verify:
+    if args.full and not args.no_verify:
         samples = rig.capture_samples(st)
         timed = world == 1 and not args.no_cpu_baseline
         v, cpu_base = check_against_oracle(samples, args.cpu_budget, timed, ranks_here)
@@ -1612,14 +1660,14 @@ def run_table(args, rank, local_rank, world, dist, torch, VARIANT, clocks, farm=
             else:
                 cpu_base["mode"] = lat["mode"]
             cpu_base["oracle_build"] = oracle_build
-    if dist is not None:
+    if args.full and dist is not None:
         v = torch.tensor([verified], device="cuda" if nccl else "cpu", dtype=torch.int64)
         dist.all_reduce(v)
         verified = int(v.item())
 
     # the whole-table multiset digest at BASELINE size (2^20 rows x 5 columns), device resident, timed once
     digest_ms = None
-    if rank == 0:
+    if args.full and rank == 0:
         big = 1 << 20
         rng = np.random.default_rng(seed)
         d_ids = ctx.to_device(st["table"].col_ids)
@@ -1632,7 +1680,7 @@ def run_table(args, rank, local_rank, world, dist, torch, VARIANT, clocks, farm=
         for b_ in (d_ids, d_values, d_unique):
             b_.free()
 
-    side = world == 1  # the side legs run at N = 1 only (like cpu_baseline): the scaling runs time the table build and nothing else
+    side = world == 1 and args.full  # the side legs run at N = 1 only (like cpu_baseline): the scaling runs time the table build and nothing else
     # a side leg that fails must not take the headline with it: its field then carries the error, `side_leg_errors` names it
     side_errors = []
 
@@ -1645,7 +1693,7 @@ def run_table(args, rank, local_rank, world, dist, torch, VARIANT, clocks, farm=
             side_errors.append(name)
             return {"error": f"{type(e).__name__}: {e}"[:400]}
 
-    legs = kernel_legs(ctx, mp2, C, VARIANT, args.hasher, rank) if rank == 0 else None
+    legs = kernel_legs(ctx, mp2, C, VARIANT, args.hasher, rank) if args.full and rank == 0 else None
     shapes = params.shapes()
     mem_free, mem_total = ctx.mem_info()  # with every prover of the run still alive: what the planner's estimate is calibrated on
     setup_s, workers, host_threads, plan = rig.setup_s, len(rig.ctxs), rig.host_threads, rig.plan
@@ -1743,14 +1791,13 @@ def run_table(args, rank, local_rank, world, dist, torch, VARIANT, clocks, farm=
                "table_2p20_rows_extrapolated_s": (1 << 20) / rows_per_s + (digest_ms or 0) / 1e3,  # = the measured time when this run is the whole table
                "table_rows_total": world * n_rows + world - 1,  # the ranks' blocks and the separator rows between them
                "table_digest_2p20_rows_ms": digest_ms,
-               "config": {"workload": f"table: configs[3], ONE contiguous block of {n_rows} rows per rank (= {args.steps} steps of " + (f"{rows_per_step} rows" if args.rows is not None else
-                                      f"1/{args.steps} of the block, {rows_per_step} rows but for the last: --rows unset = the 2^17-row block of the metric's table") +
+               "config": {"workload": f"table: configs[3], ONE contiguous block of {n_rows} rows per rank (= {args.steps} steps of {rows_per_step} rows" +
                                       f"; row tree {depth} levels deep, one work plan" + (f"; {world} blocks + {world - 1} separator rows = {world * n_rows + world - 1} rows, joined in {n_levels} level(s)" if world > 1 else "") + ") "
                                       f"-- per row {n_cols} cells-tree proofs (2 leaves, 1 full, 1 partial) + 1 row-tree proof (leaf / partial / full + the cells root through the "
                                       "cells-set verifier gadget), all REAL framework proofs = witness program + base prove() + wrap chain to 2^12 rows, witness check on; row tree "
                                       "scheduled by the batched UpdateTree work plan; the rows' multiset digests (map-to-curve, row ids, accumulation up both trees) inside the timed "
                                       "region; value = framework proofs/s (5 per row). " + ("THIS IS the full 2^20-row build of configs[3]" if world * n_rows >= 1 << 20 else
-                                      full_table_note(full_rec)) + "; configs[2] at "
+                                      full_table_note(full_rec)) + "; with --full: configs[2] at "
                                       "full size = `config2`; base degrees 12..15 = `by_base_degree`; roofline leg = configs[1] 2^22-point NTT",
                           "rows_per_rank": n_rows, "rows_per_step": rows_per_step, "row_tree_depth": depth, "warmup_rows_per_rank": warm_rows,
                           "value_columns": n_cols, "workers": workers, "batch": args.table_batch, "subtree_size": args.subtree, "group_rows": args.group_rows or 32 * args.table_batch, "pad_base_bits": args.pad_base_bits,
@@ -1771,10 +1818,12 @@ def run_table(args, rank, local_rank, world, dist, torch, VARIANT, clocks, farm=
                                           ", host tensors over gloo; every join pair probed before t0)"),
                           "handoff": handoff,
                           "root_public_inputs": root_pis_out,
-                          "verified": f"{verified} prove() calls: on every rank the block root passes the oracle's verifier and one framework proof of every circuit kind of the timed "
-                                      "block equals the CPU oracle's proofs of the same witnesses bit for bit and passes its verifier; the block roots expose the off-circuit "
-                                      "tree hash, digest (= compute_table_row_digest of the block), min, max and the circuit-set digest"},
-               "clocks": clocks.read(local_rank)}
+                          "verified": (f"{verified} prove() calls: on every rank the block root passes the oracle's verifier and one framework proof of every circuit kind of the timed "
+                                       "block equals the CPU oracle's proofs of the same witnesses bit for bit and passes its verifier; the block roots expose the off-circuit "
+                                       "tree hash, digest (= compute_table_row_digest of the block), min, max and the circuit-set digest") if args.full else
+                                      "nothing checked: the self-check runs with --full"}}
+        if args.full:
+            out["clocks"] = clocks.read(local_rank)
         if full_rec is not None:  # the metric's named configuration, completed across calls (bench.py --resume-dir): a committed record, not this run
             out["table_2p20_rows_completed"] = full_rec
         if config2 is not None:
@@ -1787,7 +1836,8 @@ def run_table(args, rank, local_rank, world, dist, torch, VARIANT, clocks, farm=
                 "`--workload leaves`, round 2's headline)", "ms_per_step": leaves["ms_per_step"], "batch": 128}
         if side_errors:
             out["side_leg_errors"] = side_errors
-        out.update(legs)
+        if legs is not None:
+            out.update(legs)
         alu = out.get("roofline_alu")
         if alu is not None and alu.get("step_valu_wave_insts_per_framework_proof"):
             # the whole table build against the same peak: (every kernel's VALU wave-instructions per framework proof, a committed counter pass) x this run's proofs/s

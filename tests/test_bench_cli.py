@@ -31,22 +31,55 @@ def test_resume_dir_is_a_single_gpu_mode(tmp_path):
 
 
 def test_block_plan_rows_per_rank():
-    """the rows of a rank's block: without --rows the block is 2^17 rows whatever --steps says, so that 8 ranks build the metric's
-    2^20-row table (+ 7 separator rows) and 1 / 2 / 4 ranks the same block per rank; the warm-up block never exceeds 5120 rows"""
+    """the rows of a rank's block: --steps x the rows of a step (1024 without --rows), so that the timed work grows with --steps and
+    --steps 128 gives every rank a 2^17-row block -- 8 ranks build the metric's 2^20-row table (+ 7 separator rows); the warm-up block
+    is --warmup steps and never exceeds 5120 rows"""
     sys.path.insert(0, ROOT)
     import bench
-    n, per_step, warm = bench.block_plan(None, 20, 5)  # the driver's command
-    assert n == 1 << 17 and per_step == 6554 and warm == 5120 and 19 * per_step < n <= 20 * per_step
+    assert bench.block_plan(None, 20, 5) == (20 * 1024, 1024, 5120)
+    assert [bench.block_plan(None, k, 1)[0] for k in (1, 2, 5)] == [1024, 2048, 5120]
+    n, per_step, warm = bench.block_plan(None, 128, 1)
+    assert n == 1 << 17 and per_step == 1024 and warm == 1024
     assert 8 * n == 1 << 20 and 8 * n + 7 == 1048583
-    assert bench.block_plan(None, 5, 1)[0] == 1 << 17 and bench.block_plan(None, 5, 0)[2] == 0
+    assert bench.block_plan(None, 5, 0)[2] == 0 and bench.block_plan(None, 5, 9)[2] == 5120
     assert bench.block_plan(1024, 20, 5) == (20480, 1024, 5120) and bench.block_plan(1024, 20, 9)[2] == 5120
     assert bench.block_plan(8, 2, 1) == (16, 8, 8)
-    assert bench.block_plan(None, 4, 1, default_rows=16) == (16, 4, 4)
-    os.environ["MP2G_BENCH_BLOCK_ROWS"] = "24"
+    assert bench.block_plan(None, 4, 1, default_step_rows=16) == (64, 16, 16)
+    os.environ["MP2G_BENCH_STEP_ROWS"] = "24"
     try:
-        assert bench.block_plan(None, 5, 2) == (24, 5, 10)
+        assert bench.block_plan(None, 5, 2) == (120, 24, 48)
+        assert bench.block_plan(8, 5, 2) == (40, 8, 16)  # --rows wins over the default
     finally:
-        del os.environ["MP2G_BENCH_BLOCK_ROWS"]
+        del os.environ["MP2G_BENCH_STEP_ROWS"]
+
+
+def test_full_and_dump_outputs_options():
+    """`--full` (everything beyond the headline) and `--dump-outputs DIR` are on the command line; the dump belongs to the table
+    workload and is refused elsewhere before any GPU is touched"""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs" in r.stdout
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MP2G_BENCH_BACKEND")}
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "ntt", "--dump-outputs", "x"], capture_output=True, text=True,
+                       timeout=300, env=env)
+    assert r.returncode != 0 and "--dump-outputs writes the root proof of the timed table block" in r.stderr + r.stdout
+
+
+def test_dump_outputs_is_exact(tmp_path):
+    """dump_outputs writes a root proof's four parts as float64 [low, high] 32-bit halves: every u64 word comes back exactly"""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import bench
+    rng = np.random.default_rng(7)
+    P = (1 << 64) - (1 << 32) + 1
+    proof = tuple(rng.integers(0, P, size=s, dtype=np.uint64) for s in ((3, 16, 4), (90, 2), (4000,), (38,)))
+    proof[2][:3] = [0, P - 1, (1 << 53) + 1]  # words a float64 of the whole word would round
+    names = bench.dump_outputs(str(tmp_path / "d"), proof)
+    assert names == ["root_caps", "root_fri_proof", "root_openings", "root_public_inputs"]
+    for name, want in zip(("root_caps", "root_openings", "root_fri_proof", "root_public_inputs"), proof):
+        a = np.load(str(tmp_path / "d" / (name + ".npy")))
+        assert a.dtype == np.float64 and a.shape == want.shape + (2,)
+        got = a[..., 0].astype(np.uint64) | (a[..., 1].astype(np.uint64) << np.uint64(32))
+        assert np.array_equal(got, want)
 
 
 def test_cpu_throughput_sweep_reports_the_best_mode():

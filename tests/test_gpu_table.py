@@ -164,7 +164,7 @@ def test_bench_default_workload_is_the_table_build():
     cpu_baseline objects (all-thread / one-thread medians, CPU model), and the side legs of the driver's line at small sizes: BASELINE
     configs[2] (a 64-leaf tree of real proofs here), the table rate at a padded base degree, the prove()-only loop"""
     line = _bench(["--rows", "8", "--steps", "2", "--warmup", "1", "--workers", "2", "--table-batch", "8", "--subtree", "8", "--cpu-budget", "1",
-                   "--config2-leaves", "64", "--degree-sweep", "12", "--sweep-rows", "8", "--sweep-runs", "2", "--leaves-leg"])
+                   "--config2-leaves", "64", "--degree-sweep", "12", "--sweep-rows", "8", "--sweep-runs", "2", "--leaves-leg", "--full"])
     assert line["config"]["workload"].startswith("table:") and line["unit"] == "proofs/s" and line["n_gpus"] == 1
     assert line["config"]["rows_per_rank"] == 16 and line["config"]["row_tree_depth"] == 4 and line["steps"] == 2
     assert abs(line["value"] * line["ms_per_step"] * 2 / 1e3 - 5 * 16) < 1e-6  # one 16-row block, 5 framework proofs per row
@@ -190,12 +190,31 @@ def test_bench_default_workload_is_the_table_build():
     assert 0 < line["roofline"]["valu"]["frac_of_valu_peak"] < 1 and line["commit_135x2p15"]["leaf_sponge_ms"] > 0 and line["commit_135x2p15"]["tree_levels_ms"] > 0
 
 
+def test_bench_plain_run_is_the_headline_alone(tmp_path):
+    """python bench.py without --full: the timed block and nothing else (no self-check, CPU baseline, side or kernel legs, clocks);
+    the block is --steps steps of --rows rows; --dump-outputs writes the block root proof, whose public inputs are the line's, and a
+    second run with the same arguments writes the same files word for word"""
+    args = ["--rows", "8", "--steps", "2", "--warmup", "1", "--workers", "2", "--table-batch", "8", "--subtree", "8", "--dump-outputs"]
+    line = _bench(args + [str(tmp_path / "a")])
+    assert all(k in line for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step")) and line["unit"] == "proofs/s"
+    assert line["config"]["rows_per_rank"] == 16 and line["steps"] == 2 and abs(line["value"] * line["ms_per_step"] * 2 / 1e3 - 5 * 16) < 1e-6
+    assert line["verified"] == 0 and not [k for k in ("roofline", "cpu_baseline", "config2", "by_base_degree", "leaves_prove_only", "clocks", "sponge") if k in line]
+    names = sorted(os.listdir(str(tmp_path / "a")))
+    assert names == ["root_caps.npy", "root_fri_proof.npy", "root_openings.npy", "root_public_inputs.npy"]
+    pis = np.load(str(tmp_path / "a" / "root_public_inputs.npy"))
+    assert pis.dtype == np.float64 and pis.shape == (T.ROWS_IO + 4, 2)
+    assert [int(lo) | (int(hi) << 32) for lo, hi in pis] == line["config"]["root_public_inputs"]
+    again = _bench(args + [str(tmp_path / "b")])
+    assert again["config"]["root_public_inputs"] == line["config"]["root_public_inputs"]
+    assert all(np.array_equal(np.load(str(tmp_path / "a" / f)), np.load(str(tmp_path / "b" / f))) for f in names)
+
+
 def test_bench_gpus_2_starts_its_own_ranks():
     """`python bench.py --gpus 2` without a launcher: two ranks (gloo rendezvous, both on this box's GPU), one block of rows each, the
     separator row between them proved by rank 0 over both block roots; the run itself asserts that the root's digest is the whole
     table's and its min the first block's"""
     line = _bench(["--gpus", "2", "--rows", "8", "--steps", "1", "--warmup", "1", "--workers", "2", "--table-batch", "8", "--subtree", "4", "--no-leaves-leg",
-                   "--no-cpu-baseline"], env={"MP2G_BENCH_BACKEND": "gloo"})
+                   "--no-cpu-baseline", "--full"], env={"MP2G_BENCH_BACKEND": "gloo"})
     assert line["n_gpus"] == 2 and line["config"]["workload"].startswith("table:")
     assert "1 join level" in line["config"]["sharding"]
     # 2 x 8 rows + the separator row, 5 proofs each
@@ -287,7 +306,7 @@ def test_bench_gpus_4_two_join_levels():
     the separator rows 1 and 5, then rank 2 hands the joined tree to rank 0, which proves separator 3 over two joined trees. The run asserts
     the root's digest = the digest of all 4 x 6 + 3 rows and its min = block 0's; every rank checks its block root and its sampled proofs."""
     line = _bench(["--gpus", "4", "--rows", "6", "--steps", "1", "--warmup", "1", "--workers", "1", "--table-batch", "8", "--subtree", "4", "--no-leaves-leg",
-                   "--no-cpu-baseline"], env={"MP2G_BENCH_BACKEND": "gloo", "MP2G_HANDOFF_PROBE_FAIL": "3"})
+                   "--no-cpu-baseline", "--full"], env={"MP2G_BENCH_BACKEND": "gloo", "MP2G_HANDOFF_PROBE_FAIL": "3"})
     assert line["n_gpus"] == 4 and "2 join level" in line["config"]["sharding"]
     assert abs(line["value"] * line["ms_per_step"] / 1e3 - 5 * (4 * 6 + 3)) < 1e-6 and line["verified"] >= 4 * 13
     # the pre-timing probe: rank 3's direct send "failed" (the test knob), its peer's recv was answered by the staged tensor, and every
@@ -301,11 +320,11 @@ def test_bench_gpus_8_three_join_levels():
     8 x 2 + 7 rows and its min = block 0's; every rank checks its block root and its sampled proofs; all eight ranks answer the
     backend's all_reduce before anything is timed."""
     line = _bench(["--gpus", "8", "--steps", "2", "--warmup", "1", "--workers", "1", "--table-batch", "4", "--subtree", "4", "--no-leaves-leg",
-                   "--no-cpu-baseline"], env={"MP2G_BENCH_BACKEND": "gloo", "MP2G_BENCH_BLOCK_ROWS": "2"})
+                   "--no-cpu-baseline", "--full"], env={"MP2G_BENCH_BACKEND": "gloo", "MP2G_BENCH_STEP_ROWS": "1"})
     assert line["n_gpus"] == 8 and line["config"]["join_levels"] == 3 and "3 join level" in line["config"]["sharding"]
     assert line["config"]["rccl_ranks"] == 8 and line["config"]["ranks_on_host"] == 8 and line["config"]["backend"] == "gloo"
-    # the driver's command shape: no --rows, so the rank's block is the default block (2^17 rows; scaled to 2 rows here), a step is
-    # 1/steps of it, and 8 ranks build 8 blocks + 7 separator rows; every join pair was probed before t0
+    # the driver's command shape: no --rows, so a step is the default step (1024 rows; scaled to 1 row here), the rank's block is
+    # steps of it, and 8 ranks build 8 blocks + 7 separator rows; every join pair was probed before t0
     assert line["config"]["rows_per_rank"] == 2 and line["config"]["rows_per_step"] == 1 and line["steps"] == 2 and line["table_rows_total"] == 8 * 2 + 7
     assert line["config"]["handoff"]["mode"] == "host" and "probed before t0" in line["config"]["sharding"]
     assert abs(line["value"] * line["ms_per_step"] * 2 / 1e3 - 5 * (8 * 2 + 7)) < 1e-6 and line["verified"] >= 8 * 10
@@ -399,7 +418,7 @@ def test_bench_python_build():
     default workload above asserts that): block root checked against the off-circuit tree and the oracle's verifier, one framework
     proof of every circuit kind re-proved by the oracle bit for bit, the scheduler named in the line"""
     line = _bench(["--rows", "8", "--steps", "2", "--warmup", "1", "--workers", "2", "--table-batch", "8", "--subtree", "8", "--python-build", "--no-cpu-baseline",
-                   "--config2-leaves", "0", "--degree-sweep", "", "--no-leaves-leg"])
+                   "--config2-leaves", "0", "--degree-sweep", "", "--no-leaves-leg", "--full"])
     assert line["config"]["host_orchestration"]["scheduler"].startswith("python") and line["verified"] >= 16
     assert 0 <= line["config"]["host_orchestration"]["host_glue_share"] < 1
     assert abs(line["value"] * line["ms_per_step"] * 2 / 1e3 - 5 * 16) < 1e-6
@@ -411,7 +430,7 @@ def test_bench_gpus_2_python_build():
     proofs and the separator rows above them are proved through the Python unit loop over the same chains); the run asserts the joined
     root's digest (the whole table's) and min"""
     line = _bench(["--gpus", "2", "--rows", "8", "--steps", "1", "--warmup", "1", "--workers", "2", "--table-batch", "8", "--subtree", "4", "--no-leaves-leg",
-                   "--no-cpu-baseline", "--python-build"], env={"MP2G_BENCH_BACKEND": "gloo"})
+                   "--no-cpu-baseline", "--python-build", "--full"], env={"MP2G_BENCH_BACKEND": "gloo"})
     assert line["n_gpus"] == 2 and line["config"]["host_orchestration"]["scheduler"].startswith("python")
     assert abs(line["value"] * line["ms_per_step"] / 1e3 - 5 * 17) < 1e-6 and line["verified"] >= 2 * 13
 
