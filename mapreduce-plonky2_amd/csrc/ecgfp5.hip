@@ -24,17 +24,6 @@
 namespace mp2g {
 
 // large bodies are real functions: the SWU / scalar-mul kernels call them hundreds of times
-// EC_WAVES_ATTR (tools/dbg/ec_variants.sh): the occupancy the register allocator is held to on the kernels (the attribute is for
-// kernels only; the out-of-line bodies are compiled for any workgroup size, i.e. within 128 VGPRs); empty = the allocator's own
-// choice (it fills the 256 VGPRs a 128-lane block can have)
-#ifndef EC_WAVES_ATTR
-#define EC_WAVES_ATTR
-#endif
-// EC_LB: the launch bound DECLARED on the three heavy kernels (they are always launched with 128 lanes). The bound reaches the
-// out-of-line bodies too (the flat work-group size propagates to callees): 1024 would hold everything to 128 VGPRs, 768 to 168
-#ifndef EC_LB
-#define EC_LB 128
-#endif
 #define GLN __device__ __noinline__
 struct gl5 { u64 c[5]; };
 
@@ -105,7 +94,6 @@ GLD gl5 gl5_mul(const gl5& a, const gl5& b) {
 // a^2 with the symmetry used: 15 products a_j a_k (j <= k) instead of 25 -- each enters output limb (j + k) mod 5 with the factor
 // (2 if j < k) * (3 if j + k >= 5, z^5 = 3) folded into the column accumulation. Squarings are over half of the multiset digest's
 // GF(p^5) operations (63 per square root, 5 of the 9 products of a point doubling).
-#ifndef EC_NO_SQR
 GLN gl5 gl5_sqr_limbs(u64 x0, u64 x1, u64 x2, u64 x3, u64 x4) {
   const u64 a[5] = {x0, x1, x2, x3, x4};
   gl5 r;
@@ -126,9 +114,6 @@ GLN gl5 gl5_sqr_limbs(u64 x0, u64 x1, u64 x2, u64 x3, u64 x4) {
   return r;
 }
 GLD gl5 gl5_sqr(const gl5& a) { return gl5_sqr_limbs(a.c[0], a.c[1], a.c[2], a.c[3], a.c[4]); }
-#else
-GLD gl5 gl5_sqr(const gl5& a) { return gl5_mul(a, a); }
-#endif
 // Frobenius powers: coefficient i times (3^((p-1)/5))^(i*e)
 GLD gl5 gl5_frob1(const gl5& a) {
   return gl5_make(a.c[0], gl_mul(a.c[1], 1041288259238279555ULL), gl_mul(a.c[2], 15820824984080659046ULL),
@@ -273,11 +258,8 @@ GLN pt pt_dbl(const pt& p) {
 // w = 1 / u = W / Z, in which doubling is 1M + 7S:  D = W^2 - 2X - 2Z^2,  X' = 16 b (WZ)^4,  W' = 2 W^4 - 4 (WZ)^2 - D^2,  Z' = 2 D W Z
 // (the same map as pt_dbl, x' = 4 b w^2 / D_a^2 and w' = (2 w^4 - 4 w^2 - D_a^2) / (2 w D_a) with D_a = w^2 - 2x - 2, on those
 // coordinates); (X : Z^2 : Z : W) are fractional coordinates again. 4M + 6S, then 3 x (1M + 7S), then 1S: 595 base products against
-// 4 x (4M + 5S) = 700. The neutral element has Z = 0 in the Jacobian form and is put back by hand. (-DEC_DBL_PLAIN: four pt_dbl.)
+// 4 x (4M + 5S) = 700. The neutral element has Z = 0 in the Jacobian form and is put back by hand.
 GLN pt pt_dbl4(const pt& p) {
-#ifdef EC_DBL_PLAIN
-  return pt_dbl(pt_dbl(pt_dbl(pt_dbl(p))));
-#else
   gl5 X, W, Z;
   {
     gl5 t1 = gl5_mul(p.Z, p.T), t2 = gl5_mul(t1, p.T);
@@ -302,7 +284,6 @@ GLN pt pt_dbl4(const pt& p) {
   pt r;
   r.X = X; r.Z = gl5_sqr(Z); r.U = Z; r.T = W;
   return r;
-#endif
 }
 GLD gl5 pt_encode(const pt& p) { return gl5_mul(p.T, gl5_inv(p.U)); }  // neutral -> 0
 // decode(w): x^2 - (w^2 - a) x + b = 0, keep the non-square root; (x, 1, 1, w)
@@ -338,19 +319,10 @@ GLD void pt_to_weierstrass(const pt& p, u64 out[11]) {
 // Signed 4-bit windows: the scalar recoded into 33 digits in [-8, 8], {0..8} * p in the lane's scratch, four doublings (pt_dbl4:
 // a run in Jacobian coordinates) and one complete addition (of +-table[|digit|]; -P = (X : Z : -U : T)) per digit: 128 doublings +
 // 32 additions + 7 for the table. The
-// bit-serial double-and-add this replaces (EC_MUL_BITSERIAL) paid close to 128 additions: a wave takes the "bit set" branch
+// bit-serial double-and-add this replaces paid close to 128 additions: a wave takes the "bit set" branch
 // whenever any of its 64 lanes has the bit. The projective representative differs from the bit-serial one; every consumer reads
 // points through the canonical encodings (pt_emit / pt_to_weierstrass) or adds them.
 GLD pt pt_mul128(const pt& p, const u32 k[4]) {
-#ifdef EC_MUL_BITSERIAL
-  pt acc = pt_neutral();
-#pragma unroll 1
-  for (int i = 127; i >= 0; i--) {
-    acc = pt_dbl(acc);
-    if ((k[i >> 5] >> (i & 31)) & 1) acc = pt_add(acc, p);
-  }
-  return acc;
-#else
   pt tab[9];
   tab[0] = pt_neutral(); tab[1] = p; tab[2] = pt_dbl(p); tab[3] = pt_add(tab[2], p); tab[4] = pt_dbl(tab[2]);
   tab[5] = pt_add(tab[4], p); tab[6] = pt_dbl(tab[3]); tab[7] = pt_add(tab[6], p); tab[8] = pt_dbl(tab[4]);
@@ -374,7 +346,6 @@ GLD pt pt_mul128(const pt& p, const u32 k[4]) {
     }
   }
   return acc;
-#endif
 }
 
 // sswu_value.rs:31-77
@@ -394,13 +365,6 @@ GLN pt simple_swu(gl5 u) {
   gl5 x2 = gl5_mul(denom_part, x1);
   gl5 gx1 = gl5_add(gl5_add(gl5_mul(x1, gl5_sqr(x1)), gl5_mul(a_sw, x1)), b_sw);
   gl5 x_sw = x1, y_pos;
-#ifdef EC_SWU_PLAIN
-  if (!gl5_sqrt(gx1, y_pos)) {
-    gl5 gx2 = gl5_add(gl5_add(gl5_mul(x2, gl5_sqr(x2)), gl5_mul(a_sw, x2)), b_sw);
-    x_sw = x2;
-    gl5_sqrt(gx2, y_pos);
-  }
-#else
   // which candidate has a square g(x) is a Legendre symbol (a norm to GF(p) and 63 base-field squarings), an eighth of the square
   // root whose failure would say the same. Every lane computes g(x2) (three products) and the wave takes ONE square root, of the
   // lane's own choice: branching on the symbol would send a wave through gl5_sqrt twice, its lanes split over the two candidates.
@@ -412,13 +376,9 @@ GLN pt simple_swu(gl5 u) {
     for (int i = 0; i < 5; i++) { g.c[i] = first ? gx1.c[i] : gx2.c[i]; x_sw.c[i] = first ? x1.c[i] : x2.c[i]; }
     gl5_sqrt(g, y_pos);
   }
-#endif
   gl5 x_cand = gl5_sub(x_sw, two_thirds);
   gl5 y_cand = gl5_sgn0(u) == gl5_sgn0(y_pos) ? y_pos : gl5_neg(y_pos);
   pt p;
-#ifdef EC_SWU_PLAIN
-  pt_decode(gl5_mul(y_cand, gl5_inv(x_cand)), p);
-#else
   // Point::decode(w), w = y / x, without its square root: (x_cand, y_cand) is on y^2 = x (x^2 + a x + b), so w^2 - a = x + b / x and
   // the two roots of decode's quadratic x^2 - (w^2 - a) x + b are x_cand and b / x_cand; decode keeps the non-square one (their
   // product b = 263 z is a non-square, so exactly one is). The general path stays for the degenerate encodings.
@@ -430,7 +390,6 @@ GLN pt simple_swu(gl5 u) {
     p.X = gl5_is_square(x_cand) ? gl5_mul_kz(xi, EC_B1) : x_cand;
     p.Z = gl5_from(1); p.U = gl5_from(1); p.T = w;
   }
-#endif
   return p;
 }
 template <int V>
@@ -462,8 +421,10 @@ GLD void pt_emit(const pt& p, u64* w, u64* wei) {
 }
 
 // ---- kernels ----------------------------------------------------------------------------------
+// The heavy kernels declare the 128 lanes they are launched with; the bound reaches the out-of-line bodies too, and larger bounds
+// (fewer VGPRs, more waves) were measured slower.
 template <int V>
-__global__ void __launch_bounds__(EC_LB) EC_WAVES_ATTR map_to_curve_kernel(const u64* in, u32 in_len, u32 count, u64* w_out, u64* wei_out, u64* frac_out) {
+__global__ void __launch_bounds__(128) map_to_curve_kernel(const u64* in, u32 in_len, u32 count, u64* w_out, u64* wei_out, u64* frac_out) {
   u32 i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= count) return;
   pt p = map_to_curve<V>(in + (u64)i * in_len, in_len);
@@ -524,7 +485,7 @@ __global__ void emit_kernel(const u64* frac, u32 count, u64* w_out, u64* wei_out
   pt p = pt_load(frac + 20 * (u64)i);
   pt_emit(p, w_out ? w_out + 5 * (u64)i : nullptr, wei_out ? wei_out + 11 * (u64)i : nullptr);
 }
-__global__ void __launch_bounds__(EC_LB) EC_WAVES_ATTR scalar_mul_kernel(const u64* frac_in, const u32* scalars, u32 count, u64* frac_out) {
+__global__ void __launch_bounds__(128) scalar_mul_kernel(const u64* frac_in, const u32* scalars, u32 count, u64* frac_out) {
   u32 i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= count) return;
   u32 k[4];
@@ -533,7 +494,7 @@ __global__ void __launch_bounds__(EC_LB) EC_WAVES_ATTR scalar_mul_kernel(const u
 }
 // one lane per table row: sum_c D(id_c || value_c), row id, row_id * row digest
 template <int V>
-__global__ void __launch_bounds__(EC_LB) EC_WAVES_ATTR row_digest_kernel(const u64* col_ids, u32 n_cols, const u32* values, const u32* unique,
+__global__ void __launch_bounds__(128) row_digest_kernel(const u64* col_ids, u32 n_cols, const u32* values, const u32* unique,
                                                           u32 n_unique, u32 rows, u64* frac_out) {
   u32 r = blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= rows) return;

@@ -468,18 +468,16 @@ int mp2g_forest_prove(mp2g_forest* f, const uint64_t* unit_nodes, const uint32_t
 // nodes, never fewer units than workers -- and SHRINKING towards the end of the wave (half of what is left per worker, down to a
 // sixth of group_nodes): the workers pull units in order, and a wave ends when the last unit does; with units of one size the last
 // ones run beside idle workers (a 2^16-row block: the last 9 % of the proofs at 0.73 of the rate, profiles/r05/block_2p16_progress.txt).
-// MP2G_FOREST_FIXED_UNITS=1 keeps one size (the A/B switch). unit u = items [unit_first_item[u], unit_first_item[u + 1]).
+// Unit u = items [unit_first_item[u], unit_first_item[u + 1]).
 int mp2g_forest_group_units(const uint32_t* item_sizes, uint32_t n_items, uint32_t n_workers, uint32_t group_nodes, uint32_t* unit_first_item,
                             uint32_t* n_units) {
   NEED((item_sizes || !n_items) && unit_first_item && n_units && n_workers >= 1, "items / outputs / workers");
-  static const bool fixed_units = [] { const char* e = getenv("MP2G_FOREST_FIXED_UNITS"); return e && atoi(e); }();
   size_t total = 0;
   for (uint32_t i = 0; i < n_items; i++) total += item_sizes[i];
   const size_t cap = std::max<size_t>(1, std::min<size_t>(group_nodes ? group_nodes : 1, (total + n_workers - 1) / n_workers));
   const size_t floor_nodes = std::max<size_t>(1, (group_nodes ? group_nodes : 1) / 6);
   size_t assigned = 0, in_group = 0;
   auto target_now = [&]() -> size_t {
-    if (fixed_units) return cap;
     return std::min(cap, std::max(floor_nodes, (total - assigned) / (2 * (size_t)n_workers)));
   };
   size_t target = target_now();

@@ -10,7 +10,6 @@
 // constraints and the filter multiplies the reduced value -- the same field element with
 // (#constraints - 1) fewer multiplications per gate and challenge.
 #include "gates.h"
-#include <cstdlib>
 #include "poseidon.cuh"
 
 namespace mp2g {
@@ -822,19 +821,16 @@ hipError_t gate_constraints_lde(hipStream_t s, u32 B, const GateTable& t, const 
   const u64 N = (u64)1 << lg;
   const dim3 grid((u32)((N + 255) / 256), B), block(256);
   int first = 1;
-  // the light gates first, in one launch (MP2G_GATES_UNFUSED=1: one launch per gate, for A/B runs)
-  static int unfused = -1;
-  if (unfused < 0) { const char* e = getenv("MP2G_GATES_UNFUSED"); unfused = e ? atoi(e) : 0; }
+  // the light gates first, in one launch
   LightGates lgs{};
   u32 light_cons = 0;
-  if (!unfused)
-    for (u32 gi = 0; gi < t.n_gates; gi++) {
-      const u32 n_cons = gate_num_constraints(t.g[gi]);
-      if (n_cons && gate_is_light(t.g[gi]) && lgs.n < MP2G_MAX_LIGHT_GATES) {
-        lgs.g[lgs.n] = t.g[gi]; lgs.gi[lgs.n] = gi; lgs.n++;
-        if (n_cons > light_cons) light_cons = n_cons;
-      }
+  for (u32 gi = 0; gi < t.n_gates; gi++) {
+    const u32 n_cons = gate_num_constraints(t.g[gi]);
+    if (n_cons && gate_is_light(t.g[gi]) && lgs.n < MP2G_MAX_LIGHT_GATES) {
+      lgs.g[lgs.n] = t.g[gi]; lgs.gi[lgs.n] = gi; lgs.n++;
+      if (n_cons > light_cons) light_cons = n_cons;
     }
+  }
   if (lgs.n < 2) lgs.n = 0;  // a lone light gate goes the ordinary way
   if (lgs.n) {
     hipLaunchKernelGGL(gate_constraints_lde_light_kernel, grid, block, 0, s, lgs, t.num_selectors, t.num_selectors + t.num_lookup_selectors,

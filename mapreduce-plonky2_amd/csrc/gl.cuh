@@ -61,16 +61,17 @@ GLHD u64 gl_dbl(u64 a) { return gl_add(a, a); }
 // canonicalisation is paid once where a value leaves the kernel. Each routine states its needs.
 // a: any u64, b: canonical. (a + b wraps to < p - 1, so the +EPS fix-up cannot wrap again.)
 GLHD u64 gl_addw(u64 a, u64 b) {
-  u32 c0, c1, d0, d1;
+  u32 c0, c1;
   u32 s0 = __builtin_addc((u32)a, (u32)b, 0u, &c0);
   u32 s1 = __builtin_addc((u32)(a >> 32), (u32)(b >> 32), c0, &c1);
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(GL_REDUCE_CARRYCHAIN)
+#if defined(__HIP_DEVICE_COMPILE__)
   return gl_mk(s0, s1) + (u64)(c1 ? 0xFFFFFFFFu : 0u);
-#endif
-  u32 m = c1 ? 0xFFFFFFFFu : 0u;
+#else
+  u32 m = c1 ? 0xFFFFFFFFu : 0u, d0, d1;
   u32 t0 = __builtin_addc(s0, m, 0u, &d0);
   u32 t1 = __builtin_addc(s1, 0u, d0, &d1);
   return gl_mk(t0, t1);
+#endif
 }
 // hi*2^64 + lo -> some u64 congruent to it (2^64 = EPS, 2^96 = -1 mod p); any lo, hi.
 // With hi = hh 2^32 + hl: x = lo + hl EPS - hh. Device code spells the sequence out: one
@@ -83,29 +84,15 @@ GLHD u64 gl_addw(u64 a, u64 b) {
 GLHD u64 gl_reduce128w(u64 lo, u64 hi) {
 #if defined(__HIP_DEVICE_COMPILE__)
   u32 hl = (u32)hi, hh = (u32)(hi >> 32);
-#ifdef GL_REDUCE_VCC
-  // A/B of round 6 (variant builds only): the multiply-add leaves its carry in VCC and the mask is selected by VCC in the VOP2
-  // encoding (a v_cndmask_b32 that selects by an SGPR pair costs 4.2 cycles as a stream, a VOP2 one 2.3: profiles/r06)
-  {
-    u64 tv;
-    u32 mcv, q0, q1, mbv;
-    const u32 ones = 0xFFFFFFFFu;
-    asm("v_mad_u64_u32 %0, vcc, %2, -1, %3\n\t"
-        "v_cndmask_b32_e32 %1, 0, %4, vcc"
-        : "=&v"(tv), "=&v"(mcv) : "v"(hl), "v"(lo), "v"(ones) : "vcc");
-    asm("v_sub_co_u32 %0, vcc, %3, %5\n\t"
-        "v_subbrev_co_u32 %1, vcc, 0, %4, vcc\n\t"
-        "v_subb_co_u32 %2, vcc, %0, %0, vcc"
-        : "=&v"(q0), "=&v"(q1), "=&v"(mbv) : "v"((u32)tv), "v"((u32)(tv >> 32)), "v"(hh) : "vcc");
-    return gl_mk(q0, q1) + gl_mk(mcv - mbv, mbv & ~mcv);
-  }
-#endif
   u64 t, c;
   asm("v_mad_u64_u32 %0, %1, %2, -1, %3" : "=&v"(t), "=s"(c) : "v"(hl), "v"(lo));
   u32 t0 = (u32)t, t1 = (u32)(t >> 32), r0, r1, mb, mc;
-#ifndef GL_REDUCE_CARRYCHAIN
   // both corrections as ONE signed 64-bit addend K = (c - b) EPS, added with a carry-less 64-bit add (v_lshl_add_u64): three
   // carry-chain instructions instead of seven. K = [mc - mb, mb & ~mc] for the masks mc = -c, mb = -b.
+  // Hazard discipline (gfx90a+: a VALU-written SGPR / VCC needs 2 wait states before another VALU reads it
+  // as an explicit operand; the compiler cannot see inside asm): VCC is only consumed through the implicit
+  // carry-in of VOP2 forms, the borrow mask is made by u0 - u0 - borrow, and the mad's carry pair %7 is
+  // first read three VALU instructions into this block.
   asm("v_sub_co_u32 %0, vcc, %4, %6\n\t"
       "v_subbrev_co_u32 %1, vcc, 0, %5, vcc\n\t"
       "v_subb_co_u32 %2, vcc, %0, %0, vcc\n\t"
@@ -114,23 +101,6 @@ GLHD u64 gl_reduce128w(u64 lo, u64 hi) {
       : "v"(t0), "v"(t1), "v"(hh), "s"(c)
       : "vcc");
   return gl_mk(r0, r1) + gl_mk(mc - mb, mb & ~mc);
-#endif
-  // Hazard discipline (gfx90a+: a VALU-written SGPR / VCC needs 2 wait states before another VALU reads it
-  // as an explicit operand; the compiler cannot see inside asm): VCC is only consumed through the implicit
-  // carry-in of VOP2 forms, the borrow mask is made by u0 - u0 - borrow, and the mad's carry pair %7 is
-  // first read three VALU instructions into this block.
-  asm("v_sub_co_u32 %0, vcc, %4, %6\n\t"
-      "v_subbrev_co_u32 %1, vcc, 0, %5, vcc\n\t"
-      "v_subb_co_u32 %2, vcc, %0, %0, vcc\n\t"
-      "v_cndmask_b32 %3, 0, -1, %7\n\t"
-      "v_add_co_u32 %0, vcc, %0, %3\n\t"
-      "v_addc_co_u32 %1, vcc, 0, %1, vcc\n\t"
-      "v_sub_co_u32 %0, vcc, %0, %2\n\t"
-      "v_subbrev_co_u32 %1, vcc, 0, %1, vcc"
-      : "=&v"(r0), "=&v"(r1), "=&v"(mb), "=&v"(mc)
-      : "v"(t0), "v"(t1), "v"(hh), "s"(c)
-      : "vcc");
-  return gl_mk(r0, r1);
 #else
   u64 hi_hi = hi >> 32, hi_lo = hi & GL_EPS;
   u64 t0;
@@ -145,36 +115,12 @@ GLHD u64 gl_reduce128w(u64 lo, u64 hi) {
 // hi*2^64 + lo with hi < 2^32
 GLHD u64 gl_reduce96w(u64 lo, u64 hi) {
 #if defined(__HIP_DEVICE_COMPILE__)
-#ifdef GL_REDUCE_VCC
-  {
-    u64 tv;
-    u32 mv;
-    const u32 ones = 0xFFFFFFFFu;
-    asm("v_mad_u64_u32 %0, vcc, %2, -1, %3\n\t"
-        "v_cndmask_b32_e32 %1, 0, %4, vcc"
-        : "=&v"(tv), "=&v"(mv) : "v"((u32)hi), "v"(lo), "v"(ones) : "vcc");
-    return tv + (u64)mv;
-  }
-#endif
   u64 t, c;
   asm("v_mad_u64_u32 %0, %1, %2, -1, %3" : "=&v"(t), "=s"(c) : "v"((u32)hi), "v"(lo));
-#ifndef GL_REDUCE_CARRYCHAIN
-  {
-    u32 m;
-    asm("s_nop 1\n\t"
-        "v_cndmask_b32 %0, 0, -1, %1" : "=v"(m) : "s"(c));
-    return t + (u64)m;  // + c EPS cannot wrap (see gl_reduce128w): a carry-less 64-bit add
-  }
-#endif
-  u32 t0 = (u32)t, t1 = (u32)(t >> 32), r0, r1, mc;
+  u32 m;
   asm("s_nop 1\n\t"  // 2 wait states between the mad's SGPR carry and its first VALU reader
-      "v_cndmask_b32 %2, 0, -1, %5\n\t"
-      "v_add_co_u32 %0, vcc, %3, %2\n\t"
-      "v_addc_co_u32 %1, vcc, 0, %4, vcc"
-      : "=&v"(r0), "=&v"(r1), "=&v"(mc)
-      : "v"(t0), "v"(t1), "s"(c)
-      : "vcc");
-  return gl_mk(r0, r1);
+      "v_cndmask_b32 %0, 0, -1, %1" : "=v"(m) : "s"(c));
+  return t + (u64)m;  // + c EPS cannot wrap (see gl_reduce128w): a carry-less 64-bit add
 #else
   u64 t1 = (hi << 32) - hi;
   u64 r;
@@ -184,20 +130,7 @@ GLHD u64 gl_reduce96w(u64 lo, u64 hi) {
 }
 GLHD u64 gl_reduce128(u64 lo, u64 hi) { return gl_canon(gl_reduce128w(lo, hi)); }
 GLHD void gl_mul_wide(u64 a, u64 b, u64& lo, u64& hi) {
-#if defined(__HIP_DEVICE_COMPILE__) && defined(GL_MULWIDE_CARRY)
-  // four independent 32x32->64 products (v_mad_u64_u32 with a zero addend), summed word by word with two carry chains:
-  // no 64-bit addend has to be assembled from 32-bit halves (tools/ubench A/B)
-  u64 p00 = (u64)(u32)a * (u32)b, x = (u64)(u32)a * (u32)(b >> 32), y = (u64)(u32)(a >> 32) * (u32)b, p11 = (u64)(u32)(a >> 32) * (u32)(b >> 32);
-  u32 c0, c1, c2;
-  u32 w1 = __builtin_addc((u32)(p00 >> 32), (u32)x, 0u, &c0);
-  u32 w2 = __builtin_addc((u32)p11, (u32)(x >> 32), c0, &c1);
-  u32 w3 = (u32)(p11 >> 32) + c1;
-  w1 = __builtin_addc(w1, (u32)y, 0u, &c0);
-  w2 = __builtin_addc(w2, (u32)(y >> 32), c0, &c2);
-  w3 += c2;
-  lo = gl_mk((u32)p00, w1);
-  hi = gl_mk(w2, w3);
-#elif defined(__HIP_DEVICE_COMPILE__)
+#if defined(__HIP_DEVICE_COMPILE__)
   // four 32x32->64 products; hipcc lowers the accumulations to v_mad_u64_u32
   u64 a0 = (u32)a, a1 = a >> 32, b0 = (u32)b, b1 = b >> 32;
   u64 p00 = a0 * b0;
@@ -275,82 +208,17 @@ GLHD u32 bitrev32(u32 x, unsigned bits) {
 #endif
 }
 
-#if defined(__HIP_DEVICE_COMPILE__) && defined(GL_MUL_FUSED_TAIL)
-// A/B of round 6 (variant builds only; MEASURED SLOWER, profiles/r06/ubench_fused_tail.txt: 2.55-2.67 against 2.83 G permutations/s --
-// fewer instructions, 37.2 against 38.9 G wave-instructions per run, but 3.42 cycles each instead of 2.97: a carry that travels through an
-// SGPR pair costs more than the move and the 64-bit add it replaces).
-// lo + (g + w) 2^64 -> some u64 congruent to it, for g any u64 and w < 2^32 with g + w < 2^64 + 2^32 (round 6). What gl_mul_wide adds
-// last to the high half of a product -- the high word w of the second middle term -- is not added at all: with s = g0 + w (carry k)
-// and 2^32 EPS = -1 (mod p) the value is lo + s EPS - g1 - k, so w enters through ONE 32-bit add whose carry-out k is the carry-IN of
-// the subtraction that takes g1 off anyway (v_subb_co_u32 with an SGPR-pair carry operand). That replaces a register move and a
-// 64-bit add (2 + 4 SIMD cycles) by one carry-chain instruction (~3.2), and the mask of the multiply-add's carry comes from a
-// subtract-with-borrow of a register from itself (~3.2) instead of a v_cndmask_b32 selecting by a scalar mask (4). Corrections as in
-// gl_reduce128w: c = 1, b = 0: t <= 2^64 - 2^33, + EPS cannot wrap; c = 0, b = 1: g1 + k <= 2^32, so t - g1 - k + 2^64 >= p - 1 and
-// - EPS cannot wrap. Hazards: k and c are VALU-written SGPR pairs read by later VALU instructions: two wait states (s_nop 1) stand
-// in front of k's reader, three instructions in front of c's.
-GLD u64 gl_reduce128w_split(u64 lo, u64 g, u32 w) {
-  u32 g0 = (u32)g, g1 = (u32)(g >> 32), s;
-  u64 k, t, c;
-#ifdef GL_SPLIT_TAIL_SGPR
-  asm("v_add_co_u32_e64 %0, %1, %2, %3" : "=v"(s), "=s"(k) : "v"(g0), "v"(w));
-  asm("v_mad_u64_u32 %0, %1, %2, -1, %3" : "=&v"(t), "=s"(c) : "v"(s), "v"(lo));
-  u32 t0 = (u32)t, t1 = (u32)(t >> 32), r0, r1, mb, mc;
-  asm("s_nop 1\n\t"
-      "v_subb_co_u32_e64 %0, vcc, %4, %6, %8\n\t"
-      "v_subbrev_co_u32 %1, vcc, 0, %5, vcc\n\t"
-      "v_subb_co_u32 %2, vcc, %0, %0, vcc\n\t"
-      "v_subb_co_u32_e64 %3, vcc, %0, %0, %7"
-      : "=&v"(r0), "=&v"(r1), "=&v"(mb), "=&v"(mc)
-      : "v"(t0), "v"(t1), "v"(g1), "s"(c), "s"(k)
-      : "vcc");
-#else
-  // variant B: k through an SGPR pair, the multiply-add's carry mask by v_cndmask_b32 as in gl_reduce128w, no explicit wait states in
-  // front of k's reader (the multiply-add stands between its writer and its reader)
-  asm("v_add_co_u32_e64 %0, %1, %2, %3" : "=v"(s), "=s"(k) : "v"(g0), "v"(w));
-  asm("v_mad_u64_u32 %0, %1, %2, -1, %3" : "=&v"(t), "=s"(c) : "v"(s), "v"(lo));
-  u32 t0 = (u32)t, t1 = (u32)(t >> 32), r0, r1, mb, mc;
-  asm(
-#ifdef GL_SPLIT_TAIL_NOP
-      "s_nop 0\n\t"
-#endif
-      "v_subb_co_u32_e64 %0, vcc, %4, %6, %8\n\t"
-      "v_subbrev_co_u32 %1, vcc, 0, %5, vcc\n\t"
-      "v_subb_co_u32 %2, vcc, %0, %0, vcc\n\t"
-      "v_cndmask_b32 %3, 0, -1, %7"
-      : "=&v"(r0), "=&v"(r1), "=&v"(mb), "=&v"(mc)
-      : "v"(t0), "v"(t1), "v"(g1), "s"(c), "s"(k)
-      : "vcc");
-#endif
-  return gl_mk(r0, r1) + gl_mk(mc - mb, mb & ~mc);
-}
-#endif
 // a * b + c as some u64 representative (any u64 a, b, c)
 GLHD u64 gl_mul_addw(u64 a, u64 b, u64 c) {
-#if defined(__HIP_DEVICE_COMPILE__) && defined(GL_MUL_FUSED_TAIL)
-  u64 a0 = (u32)a, a1 = a >> 32, b0 = (u32)b, b1 = b >> 32;
-  u64 p00 = a0 * b0 + (u64)(u32)c;
-  u64 m1 = a0 * b1 + ((p00 >> 32) + (c >> 32));
-  u64 m2 = a1 * b0 + (m1 & GL_EPS);
-  return gl_reduce128w_split((m2 << 32) | (p00 & GL_EPS), a1 * b1 + (m1 >> 32), (u32)(m2 >> 32));
-#else
   u64 lo, hi;
   gl_mul_add_wide(a, b, c, lo, hi);
   return gl_reduce128w(lo, hi);
-#endif
 }
 GLHD u64 gl_mul_add(u64 a, u64 b, u64 c) { return gl_canon(gl_mul_addw(a, b, c)); }  // canonical a b + c, any u64 inputs
 GLHD u64 gl_mulw(u64 a, u64 b) {
-#if defined(__HIP_DEVICE_COMPILE__) && defined(GL_MUL_FUSED_TAIL)
-  u64 a0 = (u32)a, a1 = a >> 32, b0 = (u32)b, b1 = b >> 32;
-  u64 p00 = a0 * b0;
-  u64 m1 = a0 * b1 + (p00 >> 32);
-  u64 m2 = a1 * b0 + (m1 & GL_EPS);
-  return gl_reduce128w_split((m2 << 32) | (p00 & GL_EPS), a1 * b1 + (m1 >> 32), (u32)(m2 >> 32));
-#else
   u64 lo, hi;
   gl_mul_wide(a, b, lo, hi);
   return gl_reduce128w(lo, hi);
-#endif
 }
 
 // ---- sums of products without carry chains ------------------------------------------------------------------------------

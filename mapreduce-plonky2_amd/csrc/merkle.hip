@@ -12,18 +12,12 @@
 // 8 B/lane stream (no transposed copy of the 8n x w matrix is ever materialised).
 #include "merkle.h"
 #include <atomic>
-#include <cstdlib>
 #include "poseidon_wave.cuh"
 
 namespace mp2g {
 
-#ifdef MP2G_EXPERIMENT_LEAF_PREFETCH
-#define LEAF_KERNEL_ATTR __attribute__((amdgpu_waves_per_eu(4, 4)))  // the prefetched limbs must not cost the fourth wave (161 VGPRs unconstrained)
-#else
-#define LEAF_KERNEL_ATTR
-#endif
 template <int V>
-__global__ void __launch_bounds__(256) LEAF_KERNEL_ATTR leaf_hash_poly_major_kernel(const u64* __restrict__ values, u32 w, u64 stride, u64 n, u64* __restrict__ digests,
+__global__ void __launch_bounds__(256) leaf_hash_poly_major_kernel(const u64* __restrict__ values, u32 w, u64 stride, u64 n, u64* __restrict__ digests,
                                                                    u64 in_bstride, u64 out_bstride) {
   u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -36,40 +30,8 @@ __global__ void __launch_bounds__(256) LEAF_KERNEL_ATTR leaf_hash_poly_major_ker
     for (u32 p = 0; p < w; p++) s[p] = values[p * stride + i];
   } else {
     const u64* v = values + i;
-#ifdef LEAF_ONE_COPY
-    // ONE copy of the permutation in the kernel's text (46 KB instead of 92: the instruction cache two CUs share holds 64 KB, and
-    // inside a proving step other streams' kernels compete for it): the short last chunk takes the same loop body, its loads
-    // guarded by wave-uniform compares
-#pragma clang loop unroll(disable)
-    for (u32 p = 0; p < w; p += 8) {
-#pragma unroll
-      for (int k = 0; k < 8; k++)
-        if (p + k < w) s[k] = v[(u64)(p + k) * stride];
-      perm<V>(s);
-    }
-#elif defined(MP2G_EXPERIMENT_LEAF_PREFETCH)
-    // A/B of round 6 (variant libraries only): the next chunk's 8 limbs are requested BEFORE the permutation of the current one, so
-    // that their latency passes under ~19 k instructions instead of in front of them (one generation of blocks starts in lockstep:
-    // every wave of the chip waits for its loads at the same moments)
-    u64 nx[8];
-#pragma unroll
-    for (int k = 0; k < 8; k++) nx[k] = k < (int)w ? v[(u64)k * stride] : 0;
-    u32 p = 0;
-    for (; p + 8 <= w; p += 8) {
-#pragma unroll
-      for (int k = 0; k < 8; k++) s[k] = nx[k];
-#pragma unroll
-      for (int k = 0; k < 8; k++)
-        if (p + 8 + k < w) nx[k] = v[(u64)(p + 8 + k) * stride];
-      perm<V>(s);
-    }
-    if (p < w) {
-#pragma unroll
-      for (int k = 0; k < 8; k++)
-        if (p + k < w) s[k] = nx[k];
-      perm<V>(s);
-    }
-#else
+    // measured and dropped: one copy of the permutation in the text, requesting the next chunk's limbs
+    // before the current permutation (profiles/r06/README.md), two sponges per lane (2-3 % slower in the table build)
     u32 p = 0;
     for (; p + 8 <= w; p += 8) {
 #pragma unroll
@@ -82,48 +44,11 @@ __global__ void __launch_bounds__(256) LEAF_KERNEL_ATTR leaf_hash_poly_major_ker
         if (p + k < w) s[k] = v[(u64)(p + k) * stride];
       perm<V>(s);
     }
-#endif
   }
   ulonglong2* d = reinterpret_cast<ulonglong2*>(digests + 4 * i);
   d[0] = make_ulonglong2(s[0], s[1]);
   d[1] = make_ulonglong2(s[2], s[3]);
 }
-#ifdef MP2G_EXPERIMENT_LEAF_ILP2  // compiled into variant libraries only (tools/dbg/build_variant.sh ilp2 "-DMP2G_EXPERIMENT_LEAF_ILP2" merkle.hip)
-// Two sponges per lane (leaves i and i + n/2: both loads stay coalesced streams): the experiment the round-3 review asked for
-// (MP2G_LEAF_ILP2=1; tools/dbg/sponge_ilp2.sh holds the numbers). Poseidon2 only, n even, w > 4.
-// the body shared by the two builds below
-#define LEAF_ILP2_BODY                                                                                      \
-  const u64 half = n >> 1;                                                                                  \
-  u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;                                                       \
-  if (i >= half) return;                                                                                    \
-  values += blockIdx.y * in_bstride;                                                                        \
-  digests += blockIdx.y * out_bstride;                                                                      \
-  u64 s[12], t[12];                                                                                         \
-  _Pragma("unroll") for (int k = 0; k < 12; k++) s[k] = t[k] = 0;                                           \
-  const u64* v = values + i;                                                                                \
-  u32 p = 0;                                                                                                \
-  for (; p + 8 <= w; p += 8) {                                                                              \
-    _Pragma("unroll") for (int k = 0; k < 8; k++) { s[k] = v[(u64)(p + k) * stride]; t[k] = v[(u64)(p + k) * stride + half]; } \
-    poseidon2_perm2(s, t);                                                                                  \
-  }                                                                                                         \
-  if (p < w) {                                                                                              \
-    _Pragma("unroll") for (int k = 0; k < 8; k++)                                                           \
-      if (p + k < w) { s[k] = v[(u64)(p + k) * stride]; t[k] = v[(u64)(p + k) * stride + half]; }           \
-    poseidon2_perm2(s, t);                                                                                  \
-  }                                                                                                         \
-  ulonglong2* d = reinterpret_cast<ulonglong2*>(digests + 4 * i);                                           \
-  d[0] = make_ulonglong2(s[0], s[1]);                                                                       \
-  d[1] = make_ulonglong2(s[2], s[3]);                                                                       \
-  d = reinterpret_cast<ulonglong2*>(digests + 4 * (i + half));                                              \
-  d[0] = make_ulonglong2(t[0], t[1]);                                                                       \
-  d[1] = make_ulonglong2(t[2], t[3]);
-// as the register allocator likes it (194 VGPRs: two waves per SIMD) ...
-__global__ void __launch_bounds__(256) leaf_hash_poly_major_ilp2_kernel(const u64* __restrict__ values, u32 w, u64 stride, u64 n, u64* __restrict__ digests,
-                                                                        u64 in_bstride, u64 out_bstride) { LEAF_ILP2_BODY }
-// ... and held to the three waves per SIMD of the single-sponge kernel (168 VGPRs, the rest spilled)
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3)))
-leaf_hash_poly_major_ilp2_w3_kernel(const u64* __restrict__ values, u32 w, u64 stride, u64 n, u64* __restrict__ digests, u64 in_bstride, u64 out_bstride) { LEAF_ILP2_BODY }
-#endif
 template <int V>
 __global__ void __launch_bounds__(256) leaf_hash_row_major_kernel(const u64* __restrict__ leaves, u32 len, u64 n, u64* __restrict__ digests) {
   u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
@@ -207,36 +132,6 @@ __global__ void __launch_bounds__(256) merkle_level_wave_kernel(const u64* __res
   x = wp2_perm(x, l);
   if (active && l < 4) out[4 * i + l] = x;
 }
-#ifdef MP2G_EXPERIMENT_MERKLE_FUSED
-// A/B of round 6 (variant libraries only; tools/dbg/merkle_fused_ab.sh, profiles/r06/merkle_fused_ab.txt): SEVERAL levels of a tree
-// in one launch -- a block owns 2^s consecutive nodes of the input level and the whole subtree above them, s <= 6; every 16-lane
-// group hashes one node at a time (wp2_perm), a level's digests go to global memory (Merkle paths are read from the levels array)
-// and, through LDS, to the block's next level: one barrier per level instead of one launch per level. MEASURED SLOWER than one launch
-// per level: the 14 levels of a 2^18-leaf tree 0.324 ms against 0.302 ms, the 11 levels of a 2^15-leaf tree 0.199 against 0.175 ms,
-// a lone 2^12-row proof 4.22 against 4.19-4.23 ms, the table block 919 against 920 proofs/s. A level as a launch of its own costs
-// ~16-21 us (the launches of a stream queue behind one another: their overhead overlaps the running kernel), a level inside the
-// fused kernel a full lane-cooperative permutation plus the barrier. The product keeps one launch per level.
-__global__ void __launch_bounds__(256) merkle_subtree_wave_kernel(const u64* __restrict__ in, u64 n_in, u32 s, u64 bstride) {
-  __shared__ u64 buf[2][32 * 4];
-  const int l = (int)(threadIdx.x & 15), g = (int)(threadIdx.x >> 4);
-  const u64* src_g = in + blockIdx.y * bstride + ((u64)blockIdx.x << s) * 4;   // this block's 2^s input nodes
-  u64* lvl = const_cast<u64*>(in) + blockIdx.y * bstride + 4 * n_in;          // level 1 of the tree (n_in / 2 nodes)
-  u64 n_lvl = n_in >> 1;
-  for (u32 j = 1; j <= s; j++) {
-    const u32 m = 1u << (s - j);                                               // nodes of this block at level j
-    u64* dst_g = lvl + (u64)blockIdx.x * m * 4;
-    for (u32 node = g; node < m; node += 16) {
-      u64 x = 0;
-      if (l < 8) x = j == 1 ? src_g[8 * node + l] : buf[j & 1][8 * node + l];
-      x = wp2_perm(x, l);
-      if (l < 4) { dst_g[4 * node + l] = x; buf[(j + 1) & 1][4 * node + l] = x; }
-    }
-    __syncthreads();
-    lvl += 4 * n_lvl;
-    n_lvl >>= 1;
-  }
-}
-#endif
 template <int V>
 __global__ void __launch_bounds__(256) hash_no_pad_batch_kernel(const u64* __restrict__ in, u32 in_len, u64 count, u32 out_len, u64* __restrict__ out) {
   u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
@@ -315,15 +210,6 @@ hipError_t leaf_hash_poly_major(hipStream_t st, int variant, const u64* values, 
                                 u32 batch, u64 in_bstride, u64 out_bstride) {
   if (!n || !batch) return hipSuccess;
   if (w > 4) g_leaf_perms.fetch_add((unsigned long long)n * batch * ((w + 7) / 8), std::memory_order_relaxed);
-#ifdef MP2G_EXPERIMENT_LEAF_ILP2
-  // A/B switch of the two-sponges-per-lane kernels: exists in variant libraries only, the product has one leaf kernel and no switch
-  static const int ilp2 = [] { const char* e = getenv("MP2G_LEAF_ILP2"); return e ? atoi(e) : 0; }();
-  if (ilp2 && variant == MP2G_POSEIDON2 && w > 4 && (n & 1) == 0) {
-    if (ilp2 == 2) hipLaunchKernelGGL(leaf_hash_poly_major_ilp2_w3_kernel, grid1(n >> 1, 256, batch), dim3(256), 0, st, values, w, stride, n, digests, in_bstride, out_bstride);
-    else hipLaunchKernelGGL(leaf_hash_poly_major_ilp2_kernel, grid1(n >> 1, 256, batch), dim3(256), 0, st, values, w, stride, n, digests, in_bstride, out_bstride);
-    return hipGetLastError();
-  }
-#endif
   LAUNCH_V(leaf_hash_poly_major_kernel, grid1(n, 256, batch), dim3(256), st, values, w, stride, n, digests, in_bstride, out_bstride);
   return hipGetLastError();
 }
@@ -346,15 +232,7 @@ hipError_t merkle_reduce(hipStream_t st, int variant, u64* levels, u32 log_leave
     u64* nxt = cur + 4 * n_in;
     // below ~2^14 nodes in flight the level is latency-bound: spread each permutation over 16 lanes
     if (variant == MP2G_POSEIDON2 && (n_in / 2) * (u64)batch <= 16384) {
-#ifdef MP2G_EXPERIMENT_MERKLE_FUSED  // the remaining levels in as few launches as 6 levels a block allow (measured slower: see the kernel)
-      const u32 left = lv - cap_h, launches = (left + 5) / 6, sl = (left + launches - 1) / launches;
-      if (sl >= 2) {
-        hipLaunchKernelGGL(merkle_subtree_wave_kernel, dim3((u32)(n_in >> sl), batch), dim3(256), 0, st, cur, n_in, sl, bstride);
-        for (u32 j = 0; j < sl; j++) { cur += 4 * (n_in >> j); }
-        lv -= sl - 1;  // the loop's own step takes the last of the sl levels
-        continue;
-      }
-#endif
+      // one launch per level: several levels per launch were measured slower
       hipLaunchKernelGGL(merkle_level_wave_kernel, grid1(n_in / 2 * 16, 256, batch), dim3(256), 0, st, cur, nxt, n_in / 2, bstride);
     } else
       LAUNCH_V(merkle_level_kernel, grid1(n_in / 2, 256, batch), dim3(256), st, cur, nxt, n_in / 2, bstride);

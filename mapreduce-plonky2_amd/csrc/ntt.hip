@@ -51,21 +51,10 @@ struct NttArgs {
   const u64* tc;         // shift-twiddle scheme (ShiftGeom): [64][2^(LT-6)] merged twiddles w_T^(b (r + 8 r')) of this pass; null = classic tables
 };
 
-// lanes per block: one radix-2^NTT_RMAX item per lane and round
-// 8 waves per SIMD (64 VGPRs) for the one-barrier kernels unless built with -DNTT_WAVES_ATTR= (tools/dbg A/B)
-#ifndef NTT_WAVES_ATTR
-#define NTT_WAVES_ATTR __attribute__((amdgpu_waves_per_eu(8)))
-#endif
-// NTT_DBG (tools/dbg only): 1 = no butterflies (memory phases alone), 2 = no global traffic (butterflies alone)
-#ifndef NTT_DBG
-#define NTT_DBG 0
-#endif
-#ifndef NTT_RMAX
-#define NTT_RMAX 3
-#endif
+// lanes per block: one radix-8 item per lane and round
 template <int LT, int LW> struct NttGeom {
   static constexpr int E = (1 << LT) << LW;
-  static constexpr int NT = (E >> NTT_RMAX) < 64 ? 64 : ((E >> NTT_RMAX) > 1024 ? 1024 : (E >> NTT_RMAX));
+  static constexpr int NT = (E >> 3) < 64 ? 64 : ((E >> 3) > 1024 ? 1024 : (E >> 3));
 };
 // Twiddles of the inner DFT, one table per radix-8 round. Round rho works on index bits HI = LT-1-3 rho
 // .. HI-2 of the transform; a lane's 8 points share the low bits `below` (< 2^LO, LO = HI-2), and output m
@@ -110,11 +99,7 @@ __device__ __forceinline__ u64 gl_sub_mul_2p72(u64 u, u64 v) {
   return gl_sub(gl_reduce128(gl_mk(0u, c1 ? 0x100u : 0u), s << 8), (s >> 56) << 32);
 }
 template <int K> __device__ __forceinline__ u64 gl_sub_mul_w8(u64 u, u64 v) {  // (u - v) * w_8^K
-#ifdef NTT_UNFUSED_SUB
-  return gl_mul_w8<K>(gl_sub(u, v));
-#else
   return K == 1 ? gl_mul_2p24(gl_sub(u, v)) : (K == 2 ? gl_sub_mul_2p48(u, v) : gl_sub_mul_2p72(u, v));
-#endif
 }
 // (u - v) * w_8^K for the forward transform, (u - v) * w_8^-K = (v - u) * w_8^(4-K) for the inverse (w_8^4 = -1)
 template <int K> __device__ __forceinline__ u64 bfly_lo(u64 u, u64 v, bool inverse) {
@@ -297,11 +282,7 @@ __global__ void __launch_bounds__((NttGeom<LT, LW>::NT)) ntt_rows_kernel(NttArgs
     if (g < total_rows) {
       u32 b = (u32)(g >> a.log_n1), jr = (u32)(g & (n1 - 1));
       if (two_pass) {
-#if NTT_DBG == 2
-        v = (u64)e * 0x9E3779B97F4A7C15ull + jr;
-#else
         v = out_base(a, b)[((u64)jr << LT) + j];  // pass A left row jr in place
-#endif
       } else {
         v = in_base(a, b)[j];
         if (a.pre_lo) v = gl_mul(v, a.pre_lo[((u64)(b & ((1u << a.logK) - 1)) << LT) + j]);
@@ -310,9 +291,7 @@ __global__ void __launch_bounds__((NttGeom<LT, LW>::NT)) ntt_rows_kernel(NttArgs
     s[lds_pad(e)] = v;
   }
   __syncthreads();
-#if NTT_DBG != 1
   dif_all<LT, LT - 1, false, LW, NT>(s, tw, a.tw, tid, a.inverse != 0);
-#endif
   for (int e = tid; e < E; e += NT) {
     int r = e >> LT, p = e & (T - 1);
     u64 g = row0 + r;
@@ -320,9 +299,6 @@ __global__ void __launch_bounds__((NttGeom<LT, LW>::NT)) ntt_rows_kernel(NttArgs
     u32 b = (u32)(g >> a.log_n1), jr = (u32)(g & (n1 - 1));
     u64 v = a.bitrev_out ? s[lds_pad(e)] : s[lds_pad((r << LT) + (int)bitrev32((u32)p, LT))];
     if (a.post) v = gl_mul(v, a.post);
-#if NTT_DBG == 2
-    if (v == 0x123456789ull)
-#endif
     out_base(a, b)[((u64)jr << LT) + p] = v;
   }
 }
@@ -377,11 +353,7 @@ __global__ void __launch_bounds__((NttGeom<LT, LW>::NT)) ntt_cols_kernel(NttArgs
   const u64* src = in_base(a, b);
   for (int e = tid; e < E; e += NT) {
     int c = e & (W - 1), j = e >> LW;
-#if NTT_DBG == 2
-    u64 v = (u64)e * 0x9E3779B97F4A7C15ull + c0;
-#else
     u64 v = src[((u64)j << a.log_n2) + c0 + c];
-#endif
     if (a.pre_full) {
       v = gl_mul(v, a.pre_full[((u64)coset << a.log_n) + ((u64)j << a.log_n2) + c0 + c]);
     } else if (a.pre_lo) {
@@ -391,9 +363,7 @@ __global__ void __launch_bounds__((NttGeom<LT, LW>::NT)) ntt_cols_kernel(NttArgs
     s[lds_pad(e)] = v;
   }
   __syncthreads();
-#if NTT_DBG != 1
   dif_all<LT, LT - 1, true, LW, NT>(s, tw, a.tw, tid, a.inverse != 0);
-#endif
   // row j holds k1 = bitrev(j); multiply by w_n^(i2*k1) and leave it at row j
   u64* dst = dst_dense ? dst_dense + (u64)b * ((u64)1 << a.log_n) : out_base(a, b);
   for (int e = tid; e < E; e += NT) {
@@ -401,30 +371,19 @@ __global__ void __launch_bounds__((NttGeom<LT, LW>::NT)) ntt_cols_kernel(NttArgs
     u64 v = s[lds_pad(e)];
     u64 w;
     if (a.tw4_full) {
-#if NTT_DBG == 2
-      w = (u64)e * 0x9E3779B97F4A7C55ull + c0;
-#else
       w = a.tw4_full[((u64)j << a.log_n2) + c0 + c];
-#endif
     } else {
       u32 k1 = bitrev32((u32)j, LT);
       u32 ex = (c0 + c) * k1;  // < n <= 2^24
       w = gl_mul(a.tw4_lo[ex & 4095], a.tw4_hi[ex >> 12]);
     }
-#if NTT_DBG == 1
-    dst[((u64)j << a.log_n2) + c0 + c] = v ^ w;
-#elif NTT_DBG == 2
-    v = gl_mul(v, w);
-    if (v == 0x123456789ull) dst[((u64)j << a.log_n2) + c0 + c] = v;
-#else
     dst[((u64)j << a.log_n2) + c0 + c] = gl_mul(v, w);
-#endif
   }
 }
 
 // ---- one-barrier tiles ----------------------------------------------------------------------------
 // The kernels above put a block barrier around every round and stage the tile through LDS on the way in; measured on the
-// 2^22 transform (tools/dbg/ntt_phases.sh, tools/dbg/ntt_pmc.sh) their waves sit parked for 56 % of their cycles. Here
+// 2^22 transform (tools/dbg/ntt_pmc.sh) their waves sit parked for 56 % of their cycles. Here
 //   * the first radix-8 round takes its inputs straight from global memory (the coalesced load pattern of a tile IS the
 //     item pattern of that round: lane `below` needs elements below + m T/8) and its twiddles from the global table;
 //   * its outputs go to LDS and the one block barrier of the tile follows;
@@ -491,8 +450,9 @@ __device__ __forceinline__ void wave_rounds(u64* s, int base, const u64* tw, int
   }
 }
 
+// 8 waves per SIMD (64 VGPRs) for the one-barrier kernels
 template <int LT, int LW, bool SHIFT = false>
-__global__ void __launch_bounds__((NttGeom<LT, LW>::NT)) NTT_WAVES_ATTR ntt_rows_v2_kernel(NttArgs a) {
+__global__ void __launch_bounds__((NttGeom<LT, LW>::NT)) __attribute__((amdgpu_waves_per_eu(8))) ntt_rows_v2_kernel(NttArgs a) {
   using G = WaveGeom<LT, LW, false>;
   static_assert(!SHIFT || ShiftGeom<LT, LW, false>::OK, "tile shape without wave-uniform shift twiddles");
   constexpr int T = 1 << LT, E = T << LW, NT = NttGeom<LT, LW>::NT, LTS = G::LTS, L0 = LT - 3;
@@ -514,11 +474,7 @@ __global__ void __launch_bounds__((NttGeom<LT, LW>::NT)) NTT_WAVES_ATTR ntt_rows
       if (two_pass) {
         const u64* src = out_base(a, b) + ((u64)jr << LT);  // pass A left row jr in place
 #pragma unroll
-#if NTT_DBG == 2
-        for (int m = 0; m < 8; m++) x[m] = (u64)(tid + m) * 0x9E3779B97F4A7C15ull + (u64)(size_t)src;
-#else
         for (int m = 0; m < 8; m++) x[m] = src[below + (m << L0)];
-#endif
       } else {
         const u64* src = in_base(a, b);
 #pragma unroll
@@ -533,19 +489,16 @@ __global__ void __launch_bounds__((NttGeom<LT, LW>::NT)) NTT_WAVES_ATTR ntt_rows
 #pragma unroll
       for (int m = 0; m < 8; m++) x[m] = 0;
     }
-#if NTT_DBG != 1
     if constexpr (SHIFT) {
       butterfly<LT, 2, 3>(x, 0, nullptr, nullptr, inverse);  // the radix-8 butterfly alone (HI = 2: no table)
       shift_twiddles(x, __builtin_amdgcn_readfirstlane(below >> (L0 - 3)), inverse);
     } else {
       butterfly<LT, LT - 1, 3, true>(x, below, tw, a.tw, inverse);
     }
-#endif
 #pragma unroll
     for (int m = 0; m < 8; m++) s[lds_pad((c << LT) + below + (m << L0))] = x[m];
   }
   __syncthreads();
-#if NTT_DBG != 1
   if constexpr (G::NBR == 2) {
     dif_round<LT, LT - 4, 3, false, LW, NT>(s, tw, a.tw, tid, inverse);
     __syncthreads();
@@ -557,7 +510,6 @@ __global__ void __launch_bounds__((NttGeom<LT, LW>::NT)) NTT_WAVES_ATTR ntt_rows
   } else {
     wave_rounds<LT, LTS, LTS - 1, false, G::LWL, 0>(s, wave << 9, tw, lane, inverse);
   }
-#endif
   if (a.bitrev_out) {
     wave_sync();
     u64 v[8];  // all eight LDS reads in flight before the first store (one read - wait - store per point otherwise)
@@ -574,9 +526,6 @@ __global__ void __launch_bounds__((NttGeom<LT, LW>::NT)) NTT_WAVES_ATTR ntt_rows
       u64 g = row0 + r;
       if (g >= total_rows) continue;
       u32 b = (u32)(g >> a.log_n1), jr = (u32)(g & (n1 - 1));
-#if NTT_DBG == 2
-      if (v[k] == 0x123456789ull)
-#endif
       out_base(a, b)[((u64)jr << LT) + p] = v[k];
     }
   } else {
@@ -594,7 +543,7 @@ __global__ void __launch_bounds__((NttGeom<LT, LW>::NT)) NTT_WAVES_ATTR ntt_rows
 }
 
 template <int LT, int LW, bool SHIFT = false>
-__global__ void __launch_bounds__((NttGeom<LT, LW>::NT)) NTT_WAVES_ATTR ntt_cols_v2_kernel(NttArgs a, u64* dst_dense) {
+__global__ void __launch_bounds__((NttGeom<LT, LW>::NT)) __attribute__((amdgpu_waves_per_eu(8))) ntt_cols_v2_kernel(NttArgs a, u64* dst_dense) {
   using G = WaveGeom<LT, LW, true>;
   static_assert(!SHIFT || ShiftGeom<LT, LW, true>::OK, "tile shape without wave-uniform shift twiddles");
   constexpr int W = 1 << LW, E = (1 << LT) << LW, NT = NttGeom<LT, LW>::NT, LTS = G::LTS, LWL = G::LWL;
@@ -614,11 +563,7 @@ __global__ void __launch_bounds__((NttGeom<LT, LW>::NT)) NTT_WAVES_ATTR ntt_cols
     const int c = tid & (W - 1), below = tid >> LW;
     u64 x[8];
 #pragma unroll
-#if NTT_DBG == 2
-    for (int m = 0; m < 8; m++) x[m] = (u64)(tid + m) * 0x9E3779B97F4A7C15ull + (u64)(size_t)src + c0;
-#else
     for (int m = 0; m < 8; m++) x[m] = src[((u64)(below + (m << LTS)) << a.log_n2) + c0 + c];
-#endif
     if (a.pre_full) {
       const u64* pre = a.pre_full + ((u64)coset << a.log_n) + c0 + c;
 #pragma unroll
@@ -628,19 +573,16 @@ __global__ void __launch_bounds__((NttGeom<LT, LW>::NT)) NTT_WAVES_ATTR ntt_cols
 #pragma unroll
       for (int m = 0; m < 8; m++) x[m] = gl_mul(gl_mul(x[m], pl), a.pre_hi[((u64)coset << LT) + below + (m << LTS)]);
     }
-#if NTT_DBG != 1
     if constexpr (SHIFT) {
       butterfly<LT, 2, 3>(x, 0, nullptr, nullptr, inverse);
       shift_twiddles(x, __builtin_amdgcn_readfirstlane(below >> (LTS - 3)), inverse);
     } else {
       butterfly<LT, LT - 1, 3, true>(x, below, tw, a.tw, inverse);
     }
-#endif
 #pragma unroll
     for (int m = 0; m < 8; m++) s[lds_pad(((below + (m << LTS)) << LW) + c)] = x[m];
   }
   __syncthreads();
-#if NTT_DBG != 1
   {
     constexpr int GW = W >> LWL;  // column groups of a tile; wave = (top three row bits, column group)
     const int cg = wave & (GW - 1), jh = wave / GW;
@@ -651,7 +593,6 @@ __global__ void __launch_bounds__((NttGeom<LT, LW>::NT)) NTT_WAVES_ATTR ntt_cols
       wave_rounds<LT, LTS, LTS - 1, true, LWL, LW>(s, ((jh << LTS) << LW) + (cg << LWL), tw, lane, inverse);
     }
   }
-#endif
   __syncthreads();
   // row j holds k1 = bitrev(j); multiply by w_n^(i2*k1) and leave it at row j
   u64* dst = dst_dense ? dst_dense + (u64)b * ((u64)1 << a.log_n) : out_base(a, b);
@@ -664,24 +605,13 @@ __global__ void __launch_bounds__((NttGeom<LT, LW>::NT)) NTT_WAVES_ATTR ntt_cols
     u64 v = s[lds_pad(e)];
     u64 w;
     if (a.tw4_full) {
-#if NTT_DBG == 2
-      w = (u64)e * 0x9E3779B97F4A7C55ull + c0;
-#else
       w = a.tw4_full[((u64)j << a.log_n2) + c0 + c];
-#endif
     } else {
       u32 k1 = bitrev32((u32)j, LT);
       u32 ex = (c0 + c) * k1;  // < n <= 2^24
       w = gl_mul(a.tw4_lo[ex & 4095], a.tw4_hi[ex >> 12]);
     }
-#if NTT_DBG == 1
-    dst[((u64)j << a.log_n2) + c0 + c] = v ^ w;
-#elif NTT_DBG == 2
-    v = gl_mul(v, w);
-    if (v == 0x123456789ull) dst[((u64)j << a.log_n2) + c0 + c] = v;
-#else
     dst[((u64)j << a.log_n2) + c0 + c] = gl_mul(v, w);
-#endif
   }
 }
 
@@ -752,31 +682,20 @@ CosetTables::~CosetTables() { (void)hipFree(lo); (void)hipFree(hi); (void)hipFre
 static u32 split_log_n1(u32 log_n) {
   if (log_n <= 13) return 0;  // 2^13 points = one 64 KB tile of 1024 lanes: a single pass over HBM
   u32 l1 = (log_n + 1) / 2;
-  if (log_n >= 22) l1 = log_n - 12;  // measured (tools/dbg/ntt22.py): 2^10 x 2^12 runs 5-9 % faster than 2^11 x 2^11 at 2^22
-  if (const char* e = getenv("MP2G_NTT_N1")) {  // tuning aid: the strided dimension's size
-    int v = atoi(e);
-    if (v >= 7 && v <= 12 && (int)log_n - v >= 1 && (int)log_n - v <= 12) l1 = (u32)v;
-  }
+  if (log_n >= 22) l1 = log_n - 12;  // measured: 2^10 x 2^12 runs 5-9 % faster than 2^11 x 2^11 at 2^22
   return l1;
 }
 // points per block (measured on MI355X, tools/dbg/ntt_only.py): 4096 (256 lanes) for T <= 2^10 and
 // T = 2^12, 8192 (512 lanes, two blocks per CU) for T = 2^11 where the twiddle table is amortised
 template <int LT> static constexpr int rows_lw() { return LT >= 12 ? 0 : (LT == 11 ? 2 : 12 - LT); }  // 2^13: one row of 8192 points
-template <int LT> static constexpr int cols_lw() { return LT >= 11 ? 2 : (LT == 10 ? 3 : 12 - LT); }  // 2^10 x 8 columns: +4 % at 2^22 (ntt22.py)
-// pass sizes whose default tile shape runs the shift-twiddle scheme (ShiftGeom); MP2G_NTT_NOSHIFT=1 keeps the classic tables (A/B)
-static bool shift_enabled() {
-  static int v = -1;
-  if (v < 0) { const char* e = getenv("MP2G_NTT_NOSHIFT"); v = (e && atoi(e)) ? 0 : 1; }
-  return v != 0;
-}
+template <int LT> static constexpr int cols_lw() { return LT >= 11 ? 2 : (LT == 10 ? 3 : 12 - LT); }  // 2^10 x 8 columns: +4 % at 2^22
+// pass sizes whose tile shape runs the shift-twiddle scheme (ShiftGeom)
 template <int LT> static constexpr bool shift_rows_lt() { return ShiftGeom<LT, rows_lw<LT>(), false>::OK; }
 template <int LT> static constexpr bool shift_cols_lt() { return ShiftGeom<LT, cols_lw<LT>(), true>::OK; }
 static bool shift_rows_ok(u32 lt) {
-  if (!shift_enabled()) return false;
   switch (lt) { case 12: return shift_rows_lt<12>(); case 13: return shift_rows_lt<13>(); default: return false; }
 }
 static bool shift_cols_ok(u32 lt) {
-  if (!shift_enabled()) return false;
   switch (lt) { case 9: return shift_cols_lt<9>(); case 10: return shift_cols_lt<10>(); case 11: return shift_cols_lt<11>(); case 12: return shift_cols_lt<12>(); default: return false; }
 }
 hipError_t NttEngine::plan(u32 log_n, bool inverse, NttPlan** out) {
@@ -822,7 +741,7 @@ hipError_t NttEngine::plan(u32 log_n, bool inverse, NttPlan** out) {
     if (shift_cols_ok(p->log_n1)) HIPCHK(merged_tw(&p->tc_a, w1, p->log_n1));
     HIPCHK(powers(&p->tw4_lo, wn, 4096));
     HIPCHK(powers(&p->tw4_hi, gl_pow(wn, 4096), log_n > 12 ? (1u << (log_n - 12)) : 1));
-    if (log_n <= 22 && !getenv("MP2G_NTT_NOFULL")) {  // full 4-step table (<= 32 MB): one multiply per point instead of two
+    if (log_n <= 22) {  // full 4-step table (<= 32 MB): one multiply per point instead of two
       HIPCHK(dev_alloc(&p->tw4_full, (size_t)1 << log_n));
       hipLaunchKernelGGL(tw4_full_kernel, dim3((u32)((((u64)1 << log_n) + 255) / 256)), dim3(256), 0, stream, p->tw4_full, wn, p->log_n1, p->log_n2);
       HIPCHK(hipGetLastError());
@@ -886,12 +805,6 @@ static bool* attr_flag(bool* flags) {
   (void)hipGetDevice(&dev);
   return &flags[dev >= 0 && dev < MP2G_MAX_DEVICES ? dev : 0];
 }
-// tuning aid: MP2G_NTT_LW11=1|2|3 overrides the tile width (log2 of rows / columns per block) of the T = 2^11 passes
-static int lw11_override() {
-  static int v = -1;
-  if (v < 0) { const char* e = getenv("MP2G_NTT_LW11"); v = e ? atoi(e) : 0; }
-  return v;
-}
 // tuning / A-B aid: MP2G_NTT_V1=1 runs the barrier-per-round kernels everywhere
 static bool use_v1() {
   static int v = -1;
@@ -899,7 +812,7 @@ static bool use_v1() {
   return v != 0;
 }
 template <int LT, int LW>
-static hipError_t launch_rows_lw(const NttArgs& a, bool nat_two_pass, hipStream_t st) {
+static hipError_t launch_rows(const NttArgs& a, bool nat_two_pass, hipStream_t st) {
   constexpr int NT = NttGeom<LT, LW>::NT;
   size_t lds = lds_bytes<LT, LW>();
   u64 total_rows = (u64)a.batch << a.log_n1;
@@ -934,16 +847,8 @@ static hipError_t launch_rows_lw(const NttArgs& a, bool nat_two_pass, hipStream_
   }
   return hipGetLastError();
 }
-template <int LT>
-static hipError_t launch_rows(const NttArgs& a, bool nat_two_pass, hipStream_t st) {
-  if constexpr (LT == 11) {
-    if (lw11_override() == 1) return launch_rows_lw<LT, 1>(a, nat_two_pass, st);
-    if (lw11_override() == 3) return launch_rows_lw<LT, 3>(a, nat_two_pass, st);
-  }
-  return launch_rows_lw<LT, rows_lw<LT>()>(a, nat_two_pass, st);
-}
 template <int LT, int LW>
-static hipError_t launch_cols_lw(const NttArgs& a, u64* dst_dense, hipStream_t st) {
+static hipError_t launch_cols(const NttArgs& a, u64* dst_dense, hipStream_t st) {
   constexpr int NT = NttGeom<LT, LW>::NT;
   size_t lds = lds_bytes<LT, LW>();
   if constexpr (ShiftGeom<LT, LW, true>::OK) {
@@ -970,22 +875,7 @@ static hipError_t launch_cols_lw(const NttArgs& a, u64* dst_dense, hipStream_t s
   hipLaunchKernelGGL((ntt_cols_kernel<LT, LW>), dim3(a.batch << (a.log_n2 - LW)), dim3(NT), lds, st, a, dst_dense);
   return hipGetLastError();
 }
-
-template <int LT>
-static hipError_t launch_cols(const NttArgs& a, u64* dst_dense, hipStream_t st) {
-  if constexpr (LT == 10) {  // tuning aid: MP2G_NTT_LW10=1|2
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("MP2G_NTT_LW10"); v = e ? atoi(e) : 0; }
-    if (v == 1) return launch_cols_lw<LT, 1>(a, dst_dense, st);
-    if (v == 2) return launch_cols_lw<LT, 2>(a, dst_dense, st);
-  }
-  if constexpr (LT == 11) {
-    if (lw11_override() == 1) return launch_cols_lw<LT, 1>(a, dst_dense, st);
-    if (lw11_override() == 3) return launch_cols_lw<LT, 3>(a, dst_dense, st);
-  }
-  return launch_cols_lw<LT, cols_lw<LT>()>(a, dst_dense, st);
-}
-#define ROWS_CASE(N) case N: return launch_rows<N>(a, nat, st);
+#define ROWS_CASE(N) case N: return launch_rows<N, rows_lw<N>()>(a, nat, st);
 static hipError_t dispatch_rows(u32 lt, const NttArgs& a, bool nat, hipStream_t st) {
   switch (lt) {
     ROWS_CASE(1) ROWS_CASE(2) ROWS_CASE(3) ROWS_CASE(4) ROWS_CASE(5) ROWS_CASE(6)
@@ -993,7 +883,7 @@ static hipError_t dispatch_rows(u32 lt, const NttArgs& a, bool nat, hipStream_t 
     default: return hipErrorInvalidValue;
   }
 }
-#define COLS_CASE(N) case N: return launch_cols<N>(a, dense, st);
+#define COLS_CASE(N) case N: return launch_cols<N, cols_lw<N>()>(a, dense, st);
 static hipError_t dispatch_cols(u32 lt, const NttArgs& a, u64* dense, hipStream_t st) {
   switch (lt) {
     COLS_CASE(7) COLS_CASE(8) COLS_CASE(9) COLS_CASE(10) COLS_CASE(11) COLS_CASE(12)
@@ -1001,26 +891,8 @@ static hipError_t dispatch_cols(u32 lt, const NttArgs& a, u64* dense, hipStream_
   }
 }
 
-#ifdef MP2G_EXPERIMENT_NTT_PRIORITY
 hipError_t NttEngine::run(const u64* in, u64* out, u32 log_n, u32 polys, u32 logK, u64 in_poly_stride,
                           u64 out_poly_stride, bool inverse, const CosetTables* pre, bool bitrev_out) {
-  if (!hi_stream) return run_impl(in, out, log_n, polys, logK, in_poly_stride, out_poly_stride, inverse, pre, bitrev_out);
-  hipStream_t base = stream;
-  HIPCHK(hipEventRecord(ev_fork, base));
-  HIPCHK(hipStreamWaitEvent(hi_stream, ev_fork, 0));
-  stream = hi_stream;
-  hipError_t e = run_impl(in, out, log_n, polys, logK, in_poly_stride, out_poly_stride, inverse, pre, bitrev_out);
-  stream = base;
-  if (e != hipSuccess) return e;
-  HIPCHK(hipEventRecord(ev_join, hi_stream));
-  return hipStreamWaitEvent(base, ev_join, 0);
-}
-hipError_t NttEngine::run_impl(const u64* in, u64* out, u32 log_n, u32 polys, u32 logK, u64 in_poly_stride,
-                               u64 out_poly_stride, bool inverse, const CosetTables* pre, bool bitrev_out) {
-#else
-hipError_t NttEngine::run(const u64* in, u64* out, u32 log_n, u32 polys, u32 logK, u64 in_poly_stride,
-                          u64 out_poly_stride, bool inverse, const CosetTables* pre, bool bitrev_out) {
-#endif
   if (log_n == 0 || log_n > 24) return hipErrorInvalidValue;
   NttPlan* p;
   HIPCHK(plan(log_n, inverse, &p));

@@ -56,7 +56,7 @@ GLHD void p2_external_rc(u64 s[12], const u64* rc) {
   for (int i = 0; i < 12; i++) { lo[i] = (u32)s[i]; hi[i] = s[i] >> 32; }
   p2_external_half(lo);
   p2_external_half(hi);
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(P2_EXTERNAL_CARRY)
+#if defined(__HIP_DEVICE_COMPILE__)
 #pragma unroll
   for (int i = 0; i < 12; i++) {
     // value = lo + hi * 2^32 (+ rc), lo, hi < 2^39: carry-less 64-bit adds of the halves, the high part of the low half moves up
@@ -65,8 +65,7 @@ GLHD void p2_external_rc(u64 s[12], const u64* rc) {
     H += L >> 32;  // < 2^41
     s[i] = gl_reduce96w(gl_mk((u32)L, (u32)H), H >> 32);
   }
-  return;
-#endif
+#else
 #pragma unroll
   for (int i = 0; i < 12; i++) {
     // value = lo + hi * 2^32, lo, hi < 2^39
@@ -82,6 +81,7 @@ GLHD void p2_external_rc(u64 s[12], const u64* rc) {
     }
     s[i] = gl_reduce96w(gl_mk(l0, l1), top);
   }
+#endif
 }
 GLHD void p2_external(u64 s[12]) { p2_external_rc<false>(s, nullptr); }
 // x^7 for a limb whose round constant is already in (p2_external_rc)
@@ -90,49 +90,23 @@ GLHD u64 p2_sbox0(u64 t) {
   return gl_mulw(t3, t4);
 }
 // s_i <- d_i s_i + sum_j s_j. Device code: sum reduced once, then a weak multiply and a weak add per limb (2.60 -> 2.71 G perm/s against the
-// fused form below -- 128-bit product plus the 68-bit sum, one reduction --, whose carry chains cost more than the second reduction saves;
-// -DP2_INTERNAL_FUSED / -DP2_EXTERNAL_CARRY restore the carry-chain forms for A/B runs)
+// fused form of the host code below -- 128-bit product plus the 68-bit sum, one reduction --, whose carry chains cost more than the second
+// reduction saves)
 GLHD void p2_internal(u64 s[12]) {
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(P2_INTERNAL_FUSED)
+#if defined(__HIP_DEVICE_COMPILE__)
   // the 68-bit sum from the 32-bit halves (each v_mad_u64_u32 adds a zero-extended word into a 64-bit accumulator: no carry
-  // chains), reduced ONCE to a canonical element; every limb is then weak multiply + weak add
+  // chains), reduced ONCE to some representative; every limb is then weak multiply + weak add
   u64 al = 0, ah = 0;
-#ifdef P2_INTERNAL_MADSUM
-  // A/B (round 6, variant builds only): every 32-bit word enters its 64-bit accumulator through the addend path of a multiply-add
-  // by 1 -- one v_mad_u64_u32 (1.7 slots) instead of the two register moves + v_lshl_add_u64 (2.4 slots) hipcc makes of a
-  // zero-extended 64-bit add; two accumulators per half keep the chains at six
-  {
-    u64 l0 = 0, l1 = 0, h0 = 0, h1 = 0, dmy;
-#pragma unroll
-    for (int i = 0; i < 12; i += 2) {
-      asm("v_mad_u64_u32 %0, %1, %2, 1, %3" : "=v"(l0), "=s"(dmy) : "v"((u32)s[i]), "v"(l0));
-      asm("v_mad_u64_u32 %0, %1, %2, 1, %3" : "=v"(h0), "=s"(dmy) : "v"((u32)(s[i] >> 32)), "v"(h0));
-      asm("v_mad_u64_u32 %0, %1, %2, 1, %3" : "=v"(l1), "=s"(dmy) : "v"((u32)s[i + 1]), "v"(l1));
-      asm("v_mad_u64_u32 %0, %1, %2, 1, %3" : "=v"(h1), "=s"(dmy) : "v"((u32)(s[i + 1] >> 32)), "v"(h1));
-    }
-    al = l0 + l1; ah = h0 + h1;
-  }
-#else
 #pragma unroll
   for (int i = 0; i < 12; i++) {
     al += (u64)(u32)s[i];
     ah += s[i] >> 32;
   }
-#endif
   ah += al >> 32;  // < 2^37
-#ifdef P2_INTERNAL_ADDW
-  const u64 sum = gl_canon(gl_reduce96w(gl_mk((u32)al, (u32)ah), ah >> 32));
-#else
   const u64 sum = gl_reduce96w(gl_mk((u32)al, (u32)ah), ah >> 32);  // any representative will do below
-#endif
 #pragma unroll
-#ifdef P2_INTERNAL_ADDW
-  for (int i = 0; i < 12; i++) s[i] = gl_addw(gl_mulw(s[i], c_p2_diag[i]), sum);
-#else
   for (int i = 0; i < 12; i++) s[i] = gl_mul_addw(s[i], c_p2_diag[i], sum);  // the sum rides in the product's addend slots
-#endif
-  return;
-#endif
+#else
   u64 acc = s[0];
   u64 top = 0;
 #pragma unroll
@@ -147,31 +121,25 @@ GLHD void p2_internal(u64 s[12]) {
     bool c = __builtin_add_overflow(lo, acc, &lo);
     s[i] = gl_reduce128w(lo, hi + top + (c ? 1 : 0));
   }
+#endif
 }
-#ifndef P2_UNROLL_EXT
-#define P2_UNROLL_EXT 1
-#endif
-#ifndef P2_UNROLL_INT
-#define P2_UNROLL_INT 11  // 22 internal rounds in two unrolled halves: 2.79 -> 2.84 G perm/s against no unrolling (tools/ubench; 4: 2.82, 22: 2.82)
-#endif
-#define P2_PRAGMA(x) _Pragma(#x)
-#define P2_UNROLL(n) P2_PRAGMA(unroll n)
 GLHD void poseidon2_perm(u64 s[12]) {
   p2_external_rc<true>(s, c_p2_ext);  // the constants of a full round ride on the preceding linear layer
-P2_UNROLL(P2_UNROLL_EXT)
+#pragma unroll 1
   for (int r = 0; r < 4; r++) {
 #pragma unroll
     for (int i = 0; i < 12; i++) s[i] = p2_sbox0(s[i]);
     if (r < 3) p2_external_rc<true>(s, c_p2_ext + 12 * (r + 1)); else p2_external(s);
   }
-P2_UNROLL(P2_UNROLL_INT)
+  // the 22 internal rounds in two unrolled halves: 2.79 -> 2.84 G perm/s against no unrolling (tools/ubench; 4: 2.82, 22: 2.82)
+#pragma unroll 11
   for (int r = 0; r < 22; r++) {
     s[0] = p2_sbox(s[0], c_p2_int[r]);
     p2_internal(s);
   }
 #pragma unroll
   for (int i = 0; i < 12; i++) s[i] = gl_addw(s[i], c_p2_ext[48 + i]);  // round 4 follows an internal layer
-P2_UNROLL(P2_UNROLL_EXT)
+#pragma unroll 1
   for (int r = 4; r < 8; r++) {
 #pragma unroll
     for (int i = 0; i < 12; i++) s[i] = p2_sbox0(s[i]);
@@ -179,38 +147,6 @@ P2_UNROLL(P2_UNROLL_EXT)
   }
 #pragma unroll
   for (int i = 0; i < 12; i++) s[i] = gl_canon(s[i]);
-}
-
-// Two independent states through the permutation side by side (the two-sponges-per-lane experiment of merkle.hip: the 22 partial
-// rounds are a chain of four dependent multiplications on one limb, and a second state gives the scheduler an independent chain)
-GLHD void poseidon2_perm2(u64 s[12], u64 t[12]) {
-  p2_external_rc<true>(s, c_p2_ext);
-  p2_external_rc<true>(t, c_p2_ext);
-P2_UNROLL(P2_UNROLL_EXT)
-  for (int r = 0; r < 4; r++) {
-#pragma unroll
-    for (int i = 0; i < 12; i++) { s[i] = p2_sbox0(s[i]); t[i] = p2_sbox0(t[i]); }
-    if (r < 3) { p2_external_rc<true>(s, c_p2_ext + 12 * (r + 1)); p2_external_rc<true>(t, c_p2_ext + 12 * (r + 1)); }
-    else { p2_external(s); p2_external(t); }
-  }
-P2_UNROLL(P2_UNROLL_INT)
-  for (int r = 0; r < 22; r++) {
-    s[0] = p2_sbox(s[0], c_p2_int[r]);
-    t[0] = p2_sbox(t[0], c_p2_int[r]);
-    p2_internal(s);
-    p2_internal(t);
-  }
-#pragma unroll
-  for (int i = 0; i < 12; i++) { s[i] = gl_addw(s[i], c_p2_ext[48 + i]); t[i] = gl_addw(t[i], c_p2_ext[48 + i]); }
-P2_UNROLL(P2_UNROLL_EXT)
-  for (int r = 4; r < 8; r++) {
-#pragma unroll
-    for (int i = 0; i < 12; i++) { s[i] = p2_sbox0(s[i]); t[i] = p2_sbox0(t[i]); }
-    if (r < 7) { p2_external_rc<true>(s, c_p2_ext + 12 * (r + 1)); p2_external_rc<true>(t, c_p2_ext + 12 * (r + 1)); }
-    else { p2_external(s); p2_external(t); }
-  }
-#pragma unroll
-  for (int i = 0; i < 12; i++) { s[i] = gl_canon(s[i]); t[i] = gl_canon(t[i]); }
 }
 
 // Poseidon (WrapC), weak-representative form like Poseidon2 above. MDS: circulant

@@ -269,17 +269,8 @@ GLD void exec_one(const u64* t, u64* vals, u64* wires, u64 n, const u64* domtab)
 }
 #undef W
 
-#ifndef WIT_LANES_N
-#define WIT_LANES_N 512
-#endif
-#ifndef WIT_BOUNDS
-#define WIT_BOUNDS WIT_LANES_N
-#endif
-constexpr int WIT_LANES = WIT_LANES_N;
-#ifdef WIT_PROF
-__device__ u64 g_wit_prof[8];
-#endif
-__global__ void __launch_bounds__(WIT_BOUNDS) witness_exec_kernel(const u64* __restrict__ tape, const u32* __restrict__ sched,
+constexpr int WIT_LANES = 512;
+__global__ void __launch_bounds__(WIT_LANES) witness_exec_kernel(const u64* __restrict__ tape, const u32* __restrict__ sched,
                                                                 const u32* __restrict__ level_off, const u32* __restrict__ level_p2, u32 n_levels, u32 n_slots, u32 log_n,
                                                                 const u32* __restrict__ input_sids, u32 n_inputs, const u64* __restrict__ consts,
                                                                 u32 n_consts, const u64* __restrict__ domtab, const u32* __restrict__ probe,
@@ -292,20 +283,9 @@ __global__ void __launch_bounds__(WIT_BOUNDS) witness_exec_kernel(const u64* __r
   for (u32 i = tid; i < n_consts; i += WIT_LANES) vals[consts[2 * i]] = consts[2 * i + 1];
   for (u32 i = tid; i < n_inputs; i += WIT_LANES) vals[input_sids[i]] = inputs[(u64)b * n_inputs + i];
   __syncthreads();
-#ifdef WIT_PROF
-  // tools/dbg/witness_prof.sh: shader cycles of block 0 per class of level (0 narrow Poseidon2, 1 wide Poseidon2, 2 reducing / interpolation /
-  // inverse, 3 the rest), left in the side buffer g_wit_prof (read back with mp2g_dbg_witness_prof; nothing of the caller's is touched)
-  u64 prof[4] = {0, 0, 0, 0}, cnt[4] = {0, 0, 0, 0};
-#endif
   for (u32 l = 0; l < n_levels; l++) {
     const u32 lo = level_off[l], hi = level_off[l + 1];
     const u32 p2_lo = level_p2[2 * l], p2_n = level_p2[2 * l + 1];  // the level's Poseidon2 rows are sched[p2_lo .. p2_lo + p2_n)
-#ifdef WIT_PROF
-    const u64 t_start = __builtin_readcyclecounter();
-    u32 cls = p2_n ? (p2_n * 16 <= 2 * WIT_LANES ? 0 : 1) : 3;
-    if (!p2_n)
-      for (u32 i = lo; i < hi; i++) { const u64 op = tape[sched[i]]; if (op == OP_REDUCING || op == OP_REDUCING_EXT || op == OP_COSET || op == OP_HINT_DIV_EXT) { cls = 2; break; } }
-#endif
     if (p2_n && p2_n * 16 <= 2 * WIT_LANES) {
       // few Poseidon2 rows: one 16-lane group each (latency; up to two rounds of groups: 2 x ~23 us against ~62 us one lane per
       // row), the level's other instructions one lane each
@@ -319,15 +299,8 @@ __global__ void __launch_bounds__(WIT_BOUNDS) witness_exec_kernel(const u64* __r
       for (u32 i = lo + tid; i < hi; i += WIT_LANES) exec_one(tape + sched[i], vals, wires, n, domtab);
     }
     __syncthreads();  // the level's slot writes (global memory, this block's) are visible to the next level's reads
-#ifdef WIT_PROF
-    prof[cls] += __builtin_readcyclecounter() - t_start; cnt[cls]++;
-#endif
   }
   for (u32 i = tid; i < n_probe; i += WIT_LANES) probe_out[(u64)b * n_probe + i] = vals[probe[i]];
-#ifdef WIT_PROF
-  if (b == 0 && tid == 0)
-    for (int k = 0; k < 4; k++) { g_wit_prof[2 * k] = prof[k]; g_wit_prof[2 * k + 1] = cnt[k]; }
-#endif
 }
 }  // namespace
 
@@ -339,9 +312,3 @@ hipError_t witness_exec_launch(hipStream_t s, const WitnessDev& d, u32 n_levels,
   return hipGetLastError();
 }
 }  // namespace mp2g
-#ifdef WIT_PROF
-// debug builds only (tools/dbg/witness_prof.sh): (cycles, levels) per class of level of block 0 of the last witness launch
-extern "C" int mp2g_dbg_witness_prof(uint64_t* out8) {
-  return hipMemcpyFromSymbol(out8, HIP_SYMBOL(mp2g::g_wit_prof), 8 * sizeof(uint64_t)) == hipSuccess ? 0 : 1;
-}
-#endif

@@ -1,6 +1,6 @@
 // Host-side check of the device arithmetic headers (the GLHD functions) against the C oracle.
 // build: hipcc -x hip --offload-arch=gfx950 -O2 -std=c++17 -DMP2G_DEVCONST="static const" \
-//        -I../../mapreduce-plonky2_amd/csrc perm_host_test.cpp ../../oracle/liboracle.so -o perm_host_test
+//        -I../../mapreduce-plonky2_amd/csrc perm_host_test.cpp -x none ../../oracle/liboracle.so -o perm_host_test
 #include "poseidon.cuh"
 #include <cstdio>
 #include <cstdlib>
