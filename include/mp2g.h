@@ -225,6 +225,10 @@ int mp2g_pcs_prove(mp2g_ctx* ctx, const mp2g_fri_params* params, const uint64_t*
 /* map_to_curve_point (field_to_curve.rs:36-48) of `count` inputs of in_len limbs each */
 int mp2g_map_to_curve_batch(mp2g_ctx* ctx, int variant, const uint64_t* in, uint32_t in_len, uint32_t count,
                             uint64_t* out_w /* [count][5] */, uint64_t* out_weierstrass /* [count][11] */);
+/* simple_swu (sswu_value.rs:31-77) of `count` GF(p^5) elements u[count][5] (coefficient i of z^i), without the sponge: what
+ * mp2g_map_to_curve_batch does after its hash. Limbs may be any u64 and are read mod p, as GoldilocksField(x) reads them. */
+int mp2g_swu_batch(mp2g_ctx* ctx, const uint64_t* u /* [count][5] */, uint32_t count, uint64_t* out_w /* [count][5] */,
+                   uint64_t* out_weierstrass /* [count][11] or NULL */);
 /* add_curve_point (curve_add.rs:17-22) over `count` encoded points; fails on an invalid encoding */
 int mp2g_curve_sum(mp2g_ctx* ctx, const uint64_t* pts_w /* [count][5] */, uint32_t count, uint64_t out_w[5],
                    uint64_t out_weierstrass[11]);
@@ -458,6 +462,9 @@ int mp2g_eval_gate_constraints(mp2g_ctx* ctx, const mp2g_gate* gates, uint32_t n
  * (3) Two instructions must not write the same wire with different values (they may run in either order on the device).
  * (4) MP2G_OP_PAR brackets sections that neither read each other's written slots nor write the same slots or wires.
  *
+ * OPCODES come in two blocks: the base set [1, MP2G_OP_END) of enum mp2g_witness_op and the GF(p^5) set [32, MP2G_OP_GF5_END)
+ * of enum mp2g_witness_op_gf5; every other value (0, MP2G_OP_END .. 31, MP2G_OP_GF5_END and above) is refused.
+ *
  * What mp2g_witness_program_create VALIDATES (a tape that fails is refused with a message, nothing is run): every opcode
  * is known, no instruction is truncated, every row < 2^log_n, every column < 135, gate-operation indices and counts are in
  * the ranges given below, constants are canonical, every slot operand, input slot and constant slot is < n_slots,
@@ -542,7 +549,25 @@ enum mp2g_witness_op {
    * operands: row, n (1..66), s_base, s_bit[n] (little endian), d_out.   wire 0 base, wires 1..n bits, wire n + 1 out, wires n + 2 ..
    * the n intermediate values (most significant bit first). */
   MP2G_OP_EXP = 23,
-  MP2G_OP_END = 24 /* one past the last opcode */
+  MP2G_OP_END = 24 /* one past the last opcode of the base set */
+};
+/* The Ecgfp5 base field GF(p^5) = GF(p)[z] / (z^5 - 3). An element takes 5 slots, coefficient i of z^i first (the layout of
+ * plonky2_ecgfp5's QuinticExtensionTarget, of mp2g_swu_batch's inputs and of the hash output mp2g_map_to_curve_batch maps).
+ * Neither opcode writes a wire: a tape puts the results on wires with MP2G_OP_WIRE. Neither fails the replay: a value that cannot
+ * satisfy the circuit's constraints (no root, a zero divisor) fails that proof in prove()'s witness check, as MP2G_OP_HINT_DIV_EXT
+ * does. */
+enum mp2g_witness_op_gf5 {
+  /* QuinticSqrtGenerator (try_any_sqrt_quintic_ext / any_sqrt_quintic_ext, mp2-common/src/group_hashing/sswu_gadget.rs).
+   * x a square: root^2 = x and is_sqrt = 1, where root is THE root with sgn0(root) = 0 (the first non-zero coefficient is even;
+   * x = 0 gives root = 0). x not a square: root = 0 and is_sqrt = 0. The sgn0 rule fixes the root for every replay (host,
+   * device, a client's own); which root [dep] plonky2_ecgfp5's generator picks, and whether its is_sqrt flag comes from the
+   * generator or from an in-circuit equality, is not pinned here -- the gadget's constraint root^2 = x holds for either root.
+   * operands: s_x[5], d_root[5], d_is_sqrt. */
+  MP2G_OP_QUINTIC_SQRT = 32,
+  /* QuinticQuotientGenerator (div_quintic_ext / inverse_quintic_ext): q = a / b, 0 when b = 0.
+   * operands: s_a[5], s_b[5], d_q[5]. */
+  MP2G_OP_QUINTIC_QUOTIENT = 33,
+  MP2G_OP_GF5_END = 34 /* one past the last opcode of the GF(p^5) set */
 };
 /* create: the tape is copied. input_sids [n_inputs]: the slots the caller provides per proof, in the order of the proof's input
  * words (a framework circuit: the circuit-set digest, then per verified child its verifier data, public inputs, caps, openings, FRI

@@ -778,6 +778,17 @@ def map_to_curve_batch(ctx, inputs, variant=POSEIDON2, weierstrass=False):
     return (w, wei) if weierstrass else w
 
 
+def swu_batch(ctx, u, weierstrass=False):
+    """simple_swu (sswu_value.rs:31-77) of each row of u [count][5] (GF(p^5) elements, coefficient i of z^i; limbs are any u64, read
+    mod p), without map_to_curve_point's sponge; returns encodings [count][5] (and the 11-limb Weierstrass form when asked)."""
+    a = _arr(u).reshape(-1, 5)
+    count = a.shape[0]
+    w = np.empty((count, 5), dtype=np.uint64)
+    wei = np.empty((count, 11), dtype=np.uint64) if weierstrass else None
+    _ck(load().mp2g_swu_batch(ctx.h, _p(a), count, _p(w), _p(wei) if weierstrass else None))
+    return (w, wei) if weierstrass else w
+
+
 def curve_sum(ctx, pts_w, weierstrass=False):
     a = _arr(pts_w).reshape(-1, 5)
     w = np.empty(5, dtype=np.uint64)

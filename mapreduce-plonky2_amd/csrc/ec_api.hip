@@ -30,6 +30,18 @@ int mp2g_map_to_curve_batch(mp2g_ctx* c, int variant, const uint64_t* in, uint32
   return copy_out(c, dw, dwei, count, out_w, out_wei);
 }
 
+int mp2g_swu_batch(mp2g_ctx* c, const uint64_t* u, uint32_t count, uint64_t* out_w, uint64_t* out_wei) {
+  NEED(c && (u || !count), "ctx/u");
+  if (!count) return 0;
+  DevBuf du, dw, dwei;
+  CK(du.alloc((size_t)count * 5 * sizeof(u64)));
+  CK(dw.alloc((size_t)count * 5 * sizeof(u64)));
+  CK(dwei.alloc((size_t)count * 11 * sizeof(u64)));
+  CK(hipMemcpyAsync(du.p, u, (size_t)count * 5 * sizeof(u64), hipMemcpyHostToDevice, c->stream));
+  CK(ec_swu(c->stream, du.p, count, out_w ? dw.p : nullptr, out_wei ? dwei.p : nullptr));
+  return copy_out(c, dw, dwei, count, out_w, out_wei);
+}
+
 // decode `count` encodings into a fractional-coordinate buffer; errors on invalid encodings
 static int decode_host(mp2g_ctx* c, const uint64_t* pts_w, uint32_t count, DevBuf& frac) {
   DevBuf dw, dbad;

@@ -13,6 +13,9 @@ enum { OP_ARITH = MP2G_OP_ARITH, OP_ARITH_EXT = MP2G_OP_ARITH_EXT, OP_P2 = MP2G_
        OP_PAR = MP2G_OP_PAR, OP_POSEIDON = MP2G_OP_POSEIDON, OP_U32_ARITH = MP2G_OP_U32_ARITH, OP_U32_SUB = MP2G_OP_U32_SUB,
        OP_U32_ADD_MANY = MP2G_OP_U32_ADD_MANY, OP_U32_RANGE_CHECK = MP2G_OP_U32_RANGE_CHECK, OP_COMPARISON = MP2G_OP_COMPARISON,
        OP_BASE_SPLIT = MP2G_OP_BASE_SPLIT, OP_MUL_EXT = MP2G_OP_MUL_EXT, OP_EXP = MP2G_OP_EXP, OP_END = MP2G_OP_END };
+// the second block (include/mp2g.h enum mp2g_witness_op_gf5): GF(p^5) hints, witness_gf5.h
+enum { OP_QUINTIC_SQRT = MP2G_OP_QUINTIC_SQRT, OP_QUINTIC_QUOTIENT = MP2G_OP_QUINTIC_QUOTIENT, OP_GF5_END = MP2G_OP_GF5_END };
+GLHD bool op_is_gf5(u64 op) { return op >= OP_QUINTIC_SQRT && op < OP_GF5_END; }
 const u32 BASE_SUM_LIMBS = 63, RA_BITS = 4, RA_COPIES = 4, RED_COEFFS = 43, RED_EXT_COEFFS = 32, NUM_WIRES = 135;
 
 // the program's read-only data on one device (uploaded at the first device run there)
@@ -20,8 +23,9 @@ struct WitnessDev {
   int device = -1;
   DevBuf tape, sched, level_off, level_p2, input_sids, consts, domtab, probe;
 };
-// device executor (witness_dev.hip): one block per proof walks the level schedule
-hipError_t witness_exec_launch(hipStream_t s, const WitnessDev& d, u32 n_levels, u32 n_slots, u32 log_n, u32 n_inputs, u32 n_consts,
+// device executor (witness_dev.hip): one block per proof walks the level schedule; gf5 = the program holds GF(p^5) opcodes (a tape
+// without them runs the kernel instance that has no code for them)
+hipError_t witness_exec_launch(hipStream_t s, const WitnessDev& d, bool gf5, u32 n_levels, u32 n_slots, u32 log_n, u32 n_inputs, u32 n_consts,
                                u32 n_probe, const u64* d_inputs, u32 batch, u64* d_vals, u64* d_wires, u64* d_probe_out);
 }  // namespace mp2g
 
@@ -36,6 +40,7 @@ struct mp2g_witness_program {
   std::vector<u32> sched, level_off;
   std::vector<u32> level_p2;  // per level: first schedule index and count of its Poseidon2 rows (one opcode = one contiguous run)
   bool ssa = true;
+  bool gf5 = false;        // the tape holds GF(p^5) opcodes (include/mp2g.h enum mp2g_witness_op_gf5)
   std::vector<u32> probe;  // slots returned next to the wires by the device run (mp2g_witness_program_set_probe)
   std::mutex dev_mu;
   std::vector<mp2g::WitnessDev*> dev;  // per device

@@ -14,6 +14,7 @@
 #include "ctx.h"
 #include "witness.h"
 #include "witness_ops.h"
+#include "witness_gf5.h"
 #include <algorithm>
 #include <atomic>
 #include <cstring>
@@ -49,6 +50,8 @@ u32 op_len(u64 op, const u64* t, size_t left = ~(size_t)0) {
     case OP_BASE_SPLIT: return left >= 3 && t[2] >= 1 && t[2] <= 63 ? 4 + (u32)t[2] : ~0u;
     case OP_MUL_EXT: return 9;
     case OP_EXP: return left >= 2 && t[1] >= 1 && t[1] <= 66 ? 3 + (u32)t[1] + 1 : ~0u;
+    case OP_QUINTIC_SQRT: return 5 + 5 + 1;
+    case OP_QUINTIC_QUOTIENT: return 5 + 5 + 5;
     default: return ~0u;
   }
 }
@@ -316,8 +319,8 @@ void exec(const mp2g_witness_program& P, const u64* t, const u64* end, u64* vals
       case OP_HINT_LO63: vals[t[1]] = vals[t[0]] & (((u64)1 << 63) - 1); t += 2; break;
       case OP_HINT_HI: vals[t[1]] = vals[t[0]] >> 63; t += 2; break;
       case OP_HINT_SPLIT: vals[t[2]] = vals[t[0]] & (((u64)1 << t[1]) - 1); vals[t[3]] = vals[t[0]] >> t[1]; t += 4; break;
-      default:  // the leaf-circuit gates (witness_ops.h: shared with the device executor)
-        if (!exec_gate_op(op, t, vals, [&](u64 col, u64 row, u64 v) { W(col, row) = v; })) return;  // validated at create
+      default:  // the leaf-circuit gates (witness_ops.h) and the GF(p^5) hints (witness_gf5.h): shared with the device executor
+        if (!exec_gate_op(op, t, vals, [&](u64 col, u64 row, u64 v) { W(col, row) = v; }) && !exec_gf5_op(op, t, vals)) return;  // validated at create
         t += op_len(op, t);
         break;
     }
@@ -362,7 +365,8 @@ static int witness_program_create(const uint64_t* tape, size_t tape_len, uint32_
       if (t >= par_end) { par_end = nullptr; boundaries.clear(); next_boundary = 0; }
     }
     const u64 op = *t++;
-    if (op < OP_ARITH || op >= OP_END) return bad("unknown opcode");
+    if ((op < OP_ARITH || op >= OP_END) && !op_is_gf5(op)) return bad("unknown opcode");
+    if (op_is_gf5(op)) P->gf5 = true;
     if (op == OP_COSET && (t + 2 > end || t[1] < 2 || t[1] > 5)) return bad("CosetInterpolation bits");
     if (op == OP_PAR && (t + 1 > end || par_end)) return bad("parallel region header / nesting");
     const u32 len = op_len(op, t, (size_t)(end - t));
@@ -457,6 +461,8 @@ static int witness_program_create(const uint64_t* tape, size_t tape_len, uint32_
         case OP_BASE_SPLIT: r0 = 3; nr = 1; w0 = 4; nw = (u32)a[2]; break;
         case OP_MUL_EXT: r0 = 3; nr = 4; w0 = 7; nw = 2; break;
         case OP_EXP: r0 = 2; nr = 1 + (u32)a[1]; w0 = 3 + (u32)a[1]; nw = 1; break;
+        case OP_QUINTIC_SQRT: r0 = 0; nr = 5; w0 = 5; nw = 6; break;
+        case OP_QUINTIC_QUOTIENT: r0 = 0; nr = 10; w0 = 10; nw = 5; break;
         default: break;
       }
       u32 l = 0;
@@ -564,7 +570,7 @@ int mp2g_witness_program_run_dev(mp2g_witness_program* P, mp2g_ctx* c, const uin
   CKH(hipMemsetAsync(c->wit_rows.p, 0, wire_words * 8, c->stream));
   // the executor fills a row-major staging matrix (one contiguous run of words per gate row); the prover's polynomial-major
   // [batch][135][n] is made from it by the tiled transpose (every word of d_wires is written)
-  CKH(witness_exec_launch(c->stream, *d, (u32)P->level_off.size() - 1, P->n_slots, P->log_n, (u32)P->input_sids.size(), (u32)(P->consts.size() / 2),
+  CKH(witness_exec_launch(c->stream, *d, P->gf5, (u32)P->level_off.size() - 1, P->n_slots, P->log_n, (u32)P->input_sids.size(), (u32)(P->consts.size() / 2),
                           (u32)P->probe.size(), (const u64*)d_inputs, batch, c->wit_vals.p, c->wit_rows.p, (u64*)d_probe_out));
   {
     int rc2 = mp2g_wires_from_rows_dev(c, c->wit_rows.p, d_wires, P->log_n, NUM_WIRES, batch);

@@ -14,6 +14,7 @@
 #include "poseidon_wave.cuh"
 #include "witness.h"
 #include "witness_ops.h"
+#include "witness_gf5.h"
 
 namespace mp2g {
 namespace {
@@ -152,6 +153,7 @@ GLD void exec_poseidon(const u64* t, u64* vals, u64* wires, u64 n) {
   for (int i = 0; i < 12; i++) { const u64 o = gl_canon(s[i]); W(12 + i, row) = o; vals[t[14 + i]] = o; }
 }
 
+template <bool GF5>
 GLD void exec_one(const u64* t, u64* vals, u64* wires, u64 n, const u64* domtab) {
   const u64 op = *t++;
   switch (op) {
@@ -262,7 +264,11 @@ GLD void exec_one(const u64* t, u64* vals, u64* wires, u64 n, const u64* domtab)
     case OP_HINT_LO63: vals[t[1]] = vals[t[0]] & (((u64)1 << 63) - 1); break;
     case OP_HINT_HI: vals[t[1]] = vals[t[0]] >> 63; break;
     case OP_HINT_SPLIT: vals[t[2]] = vals[t[0]] & (((u64)1 << t[1]) - 1); vals[t[3]] = vals[t[0]] >> t[1]; break;
-    default:  // the leaf-circuit gates (witness_ops.h: shared with the host executor); anything else was refused at create
+    default:  // the leaf-circuit gates (witness_ops.h) and the GF(p^5) hints (witness_gf5.h): shared with the host executor;
+              // anything else was refused at create
+      if constexpr (GF5) {
+        if (exec_gf5_op(op, t, vals)) break;
+      }
       exec_gate_op(op, t, vals, [wires](u64 col, u64 row, u64 v) { W(col, row) = v; });
       break;
   }
@@ -270,6 +276,9 @@ GLD void exec_one(const u64* t, u64* vals, u64* wires, u64 n, const u64* domtab)
 #undef W
 
 constexpr int WIT_LANES = 512;
+// GF5: the program holds GF(p^5) opcodes. Only that instance carries their code (the field's square root and inverse are long
+// out-of-line bodies); a tape without them runs the instance that is the kernel as it was before they existed.
+template <bool GF5>
 __global__ void __launch_bounds__(WIT_LANES) witness_exec_kernel(const u64* __restrict__ tape, const u32* __restrict__ sched,
                                                                 const u32* __restrict__ level_off, const u32* __restrict__ level_p2, u32 n_levels, u32 n_slots, u32 log_n,
                                                                 const u32* __restrict__ input_sids, u32 n_inputs, const u64* __restrict__ consts,
@@ -293,10 +302,10 @@ __global__ void __launch_bounds__(WIT_LANES) witness_exec_kernel(const u64* __re
       const u32 rest = (hi - lo) - p2_n;
       for (u32 i = tid; i < rest; i += WIT_LANES) {
         const u32 j = lo + i;
-        exec_one(tape + sched[j < p2_lo ? j : j + p2_n], vals, wires, n, domtab);
+        exec_one<GF5>(tape + sched[j < p2_lo ? j : j + p2_n], vals, wires, n, domtab);
       }
     } else {
-      for (u32 i = lo + tid; i < hi; i += WIT_LANES) exec_one(tape + sched[i], vals, wires, n, domtab);
+      for (u32 i = lo + tid; i < hi; i += WIT_LANES) exec_one<GF5>(tape + sched[i], vals, wires, n, domtab);
     }
     __syncthreads();  // the level's slot writes (global memory, this block's) are visible to the next level's reads
   }
@@ -304,9 +313,9 @@ __global__ void __launch_bounds__(WIT_LANES) witness_exec_kernel(const u64* __re
 }
 }  // namespace
 
-hipError_t witness_exec_launch(hipStream_t s, const WitnessDev& d, u32 n_levels, u32 n_slots, u32 log_n, u32 n_inputs, u32 n_consts,
-                               u32 n_probe, const u64* d_inputs, u32 batch, u64* d_vals, u64* d_wires, u64* d_probe_out) {
-  hipLaunchKernelGGL(witness_exec_kernel, dim3(batch), dim3(WIT_LANES), 0, s, d.tape.p, (const u32*)d.sched.p, (const u32*)d.level_off.p,
+hipError_t witness_exec_launch(hipStream_t s, const WitnessDev& d, bool gf5, u32 n_levels, u32 n_slots, u32 log_n, u32 n_inputs,
+                               u32 n_consts, u32 n_probe, const u64* d_inputs, u32 batch, u64* d_vals, u64* d_wires, u64* d_probe_out) {
+  hipLaunchKernelGGL(gf5 ? witness_exec_kernel<true> : witness_exec_kernel<false>, dim3(batch), dim3(WIT_LANES), 0, s, d.tape.p, (const u32*)d.sched.p, (const u32*)d.level_off.p,
                      (const u32*)d.level_p2.p, n_levels, n_slots, log_n, (const u32*)d.input_sids.p, n_inputs, d.consts.p, n_consts, d.domtab.p,
                      (const u32*)d.probe.p, n_probe, d_inputs, d_vals, d_wires, d_probe_out);
   return hipGetLastError();

@@ -22,6 +22,7 @@ import numpy as np
 
 from . import Gate, MULT_GEN
 from . import circuits as C
+from . import gf5
 
 P = C.P
 W7 = 7  # quadratic extension X^2 = 7
@@ -77,6 +78,7 @@ class T:
  OP_HINT_LO63, OP_HINT_HI, OP_HINT_SPLIT, OP_PAR, OP_POSEIDON,
  # the leaf circuits' user-logic gates (round 6; include/mp2g.h enum mp2g_witness_op documents every operand layout)
  OP_U32_ARITH, OP_U32_SUB, OP_U32_ADD_MANY, OP_U32_RANGE_CHECK, OP_COMPARISON, OP_BASE_SPLIT, OP_MUL_EXT, OP_EXP) = range(1, 24)
+# The GF(p^5) hints are the header's second block (enum mp2g_witness_op_gf5, 32..33): gf5.OP_QUINTIC_SQRT, gf5.OP_QUINTIC_QUOTIENT.
 
 
 class E:
@@ -104,7 +106,7 @@ def tape_instructions(tape):
     """(position, opcode) of every instruction of a recorded witness program (the lengths csrc/witness.hip's op_len gives)"""
     fixed = {OP_ARITH: 8, OP_ARITH_EXT: 12, OP_P2: 26, OP_POSEIDON: 26, OP_BASE_SUM: 2 + 63, OP_RA: 20, OP_REDUCING: 5 + 43 + 2, OP_REDUCING_EXT: 5 + 64 + 2,
              OP_WIRE: 3, OP_HINT_DIV_EXT: 6, OP_HINT_LO63: 2, OP_HINT_HI: 2, OP_HINT_SPLIT: 4, OP_U32_ARITH: 8, OP_U32_SUB: 8, OP_U32_RANGE_CHECK: 4,
-             OP_COMPARISON: 6, OP_MUL_EXT: 9}
+             OP_COMPARISON: 6, OP_MUL_EXT: 9, gf5.OP_QUINTIC_SQRT: 11, gf5.OP_QUINTIC_QUOTIENT: 15}
     t, n = 0, len(tape)
     while t < n:
         op = int(tape[t])
@@ -158,6 +160,12 @@ def instruction_slots(tape, pos):
         return [t[0]], [t[1]], [], pos + 3
     if op == OP_HINT_SPLIT:
         return [t[0]], t[2:4], [], pos + 5
+    if op == gf5.OP_QUINTIC_SQRT:
+        t = tape[pos + 1:pos + 12]
+        return t[0:5], t[5:11], [], pos + 12
+    if op == gf5.OP_QUINTIC_QUOTIENT:
+        t = tape[pos + 1:pos + 16]
+        return t[0:10], t[10:15], [], pos + 16
     t = tape[pos + 1:]
     if op in (OP_U32_ARITH, OP_U32_SUB):
         per, limbs = (6, 32) if op == OP_U32_ARITH else (5, 16)
@@ -527,6 +535,25 @@ class Builder:
         q = E(self._hint(qv[0]), self._hint(qv[1]))
         self.tape += [OP_HINT_DIV_EXT, num.a.sid, num.b.sid, den.a.sid, den.b.sid, q.a.sid, q.b.sid]
         self.connect_ext(self.mul_ext(q, den), num)
+        return q
+
+    # ---- GF(p^5) hints (QuinticSqrtGenerator / QuinticQuotientGenerator of [dep] plonky2_ecgfp5, recorded by
+    # mp2-common/src/group_hashing/sswu_gadget.rs:57-96). An element is a list of 5 targets, coefficient i of z^i (z^5 = 3).
+    # Witness values only: no gate and no constraint is placed -- the gadget that needs root^2 = x or q b = a constrains it.
+    def quintic_sqrt(self, x):
+        """(root, is_sqrt): root^2 = x with sgn0(root) = 0 and is_sqrt = 1 when x is a square, else root = 0 and is_sqrt = 0"""
+        assert len(x) == 5
+        r = gf5.sqrt(tuple(t.v for t in x))
+        root = [self._hint(v) for v in (gf5.ZERO if r is None else r)]
+        is_sqrt = self._hint(0 if r is None else 1)
+        self.tape += [gf5.OP_QUINTIC_SQRT] + [t.sid for t in x] + [t.sid for t in root] + [is_sqrt.sid]
+        return root, is_sqrt
+
+    def quintic_quotient(self, a, b):
+        """q = a / b, 0 when b = 0"""
+        assert len(a) == 5 and len(b) == 5
+        q = [self._hint(v) for v in gf5.div(tuple(t.v for t in a), tuple(t.v for t in b))]
+        self.tape += [gf5.OP_QUINTIC_QUOTIENT] + [t.sid for t in a] + [t.sid for t in b] + [t.sid for t in q]
         return q
 
     def exp_power_of_2_ext(self, x, k):
