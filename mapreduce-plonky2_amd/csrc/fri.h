@@ -52,9 +52,12 @@ struct FriLayers {
 hipError_t challenger_init(hipStream_t s, ChState* st, u32 B);
 hipError_t challenger_step(hipStream_t s, int variant, ChState* st, u32 B, const u64* obs, u64 obs_bstride, u32 n_obs,
                            u64* out, u64 out_bstride, u32 n_get);
-hipError_t fri_openings(hipStream_t s, const FriShape& sh, u32 B, const u64* zeta, u64 zeta_bstride, u64* out);
+// zpw: scratch of B * 4n words (the powers of zeta and g zeta, built here)
+hipError_t fri_openings(hipStream_t s, const FriShape& sh, u32 B, const u64* zeta, u64 zeta_bstride, u64* zpw, u64* out);
+// apw: scratch of B * 2 * fri_alpha_powers_len(sh) words (the powers of alpha, built here)
+GLHD u32 fri_alpha_powers_len(const FriShape& sh) { return sh.n_polys + 1; }
 hipError_t fri_final_poly(hipStream_t s, const FriShape& sh, u32 B, const u64* alpha, u64 alpha_bstride, const u64* zeta,
-                          u64 zeta_bstride, u64* comp, u64* quot, u64* final_poly);
+                          u64 zeta_bstride, u64* apw, u64* comp, u64* quot, u64* final_poly);
 hipError_t fri_fold_values(hipStream_t s, u32 B, u32 log_m, u32 ab, const u64* in, u64 in_bstride, u64* out, u64 out_bstride,
                            const u64* beta, u64 beta_bstride, u64 shift);
 hipError_t fri_fold_coeffs(hipStream_t s, u32 B, u32 n_in, u32 ab, const u64* in, u64 in_bstride, u64* out, u64 out_bstride,

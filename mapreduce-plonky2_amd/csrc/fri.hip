@@ -115,68 +115,111 @@ hipError_t challenger_step(hipStream_t s, int variant, ChState* st, u32 B, const
   return hipGetLastError();
 }
 
+// ---- power tables of a batch: out[b] = [x_b^e, e < count] as [c0: count][c1: count] --------------
+// x_b = scale * x[b]. Lane t of block k writes e = 256 EP_RUN k + t + 256 r, r < EP_RUN: one gl2_pow per lane, then one
+// gl2_mul per entry.
+#define EP_RUN 16
+__global__ void __launch_bounds__(256) ext_powers_kernel(const u64* __restrict__ x, u64 x_bstride, u64 scale, u32 count,
+                                                         u64* __restrict__ out, u64 out_bstride) {
+  const u32 b = blockIdx.y, e0 = blockIdx.x * 256 * EP_RUN + threadIdx.x;
+  if (e0 >= count) return;
+  const gl2 xb = gl2_scale(gl2_make(x[b * x_bstride], x[b * x_bstride + 1]), scale);
+  const gl2 step = gl2_pow(xb, 256);
+  gl2 pw = gl2_pow(xb, e0);
+  u64* o = out + b * out_bstride;
+  for (u32 r = 0, e = e0; r < EP_RUN && e < count; r++, e += 256) {
+    o[e] = pw.a;
+    o[count + e] = pw.b;
+    pw = gl2_mul(pw, step);
+  }
+}
+static hipError_t ext_powers(hipStream_t s, u32 B, const u64* x, u64 x_bstride, u64 scale, u32 count, u64* out, u64 out_bstride) {
+  hipLaunchKernelGGL(ext_powers_kernel, dim3((count + 256 * EP_RUN - 1) / (256 * EP_RUN), B), dim3(256), 0, s, x, x_bstride, scale, count, out,
+                     out_bstride);
+  return hipGetLastError();
+}
+
 // ---- openings: every polynomial at zeta, the Z polynomials also at g*zeta ---------------------
-// grid (n_open, B), block 256. out[b][j] = sum_i c_i x^i as [c0,c1].
-__global__ void __launch_bounds__(256) openings_kernel(FriShape sh, const u64* zeta /*[B][2]*/, u64 zeta_bstride, u64* out /*[B][n_open][2]*/) {
-  const u32 j = blockIdx.x, b = blockIdx.y, t = threadIdx.x;
-  const u32 n = 1u << sh.log_n;
-  u32 o, p;
-  gl2 x = gl2_make(zeta[b * zeta_bstride], zeta[b * zeta_bstride + 1]);
-  if (j >= sh.n_polys) {
-    fri_batch_poly(sh, 1, j - sh.n_polys, o, p);
-    x = gl2_scale(x, gl_root_of_unity(sh.log_n));
-  } else {
-    fri_batch_poly(sh, 0, j, o, p);
+// out[b][j] = sum_i c_i x^i as [c0,c1], x^i read from the batch's power table zpw[b] = [zeta^i][(g zeta)^i] (each [c0: n][c1: n]).
+// A block takes OP_POLYS polynomials of one opening point, lane t the coefficients i = t + 256k (coalesced loads); the base x
+// extension products accumulate in carry-free columns (gl_cols) and are reduced once per polynomial and lane.
+// grid (ceil(n_polys / OP_POLYS) + ceil((zs_count + lookup_count) / OP_POLYS), B), block 256.
+#define OP_POLYS 4
+__global__ void __launch_bounds__(256) openings_kernel(FriShape sh, const u64* __restrict__ zpw, u64 zpw_bstride, u64* out /*[B][n_open][2]*/) {
+  const u32 b = blockIdx.y, t = threadIdx.x;
+  const u32 n = 1u << sh.log_n, n_open = sh.n_polys + sh.zs_count + sh.lookup_count;
+  const u32 blocks0 = (sh.n_polys + OP_POLYS - 1) / OP_POLYS;
+  const bool shifted = blockIdx.x >= blocks0;
+  const u32 j0 = shifted ? sh.n_polys + (blockIdx.x - blocks0) * OP_POLYS : blockIdx.x * OP_POLYS;
+  const u32 nq = min(OP_POLYS, (shifted ? n_open : sh.n_polys) - j0);
+  const u64* pa = zpw + b * zpw_bstride + (shifted ? 2 * (u64)n : 0);
+  const u64* pb = pa + n;
+  const u64* c[OP_POLYS];
+#pragma unroll
+  for (u32 q = 0; q < OP_POLYS; q++) {
+    u32 o, p;
+    const u32 j = j0 + (q < nq ? q : 0);
+    if (shifted) fri_batch_poly(sh, 1, j - sh.n_polys, o, p);
+    else fri_batch_poly(sh, 0, j, o, p);
+    c[q] = sh.o[o].coeffs + b * sh.o[o].coeff_bstride + ((u64)p << sh.log_n);
   }
-  const u64* c = sh.o[o].coeffs + b * sh.o[o].coeff_bstride + ((u64)p << sh.log_n);
-  // lane t owns i = t + 256k: Horner in x^256, then weight by x^t
-  gl2 x256 = gl2_pow(x, 256), acc = gl2_make(0, 0);
-  if (t < n) {
-    u32 top = ((n - 1 - t) >> 8);
-    for (int k = (int)top; k >= 0; k--) {
-      acc = gl2_mul(acc, x256);
-      acc.a = gl_add(acc.a, c[t + ((u32)k << 8)]);
-    }
-    acc = gl2_mul(acc, gl2_pow(x, t));
+  gl_cols sa[OP_POLYS], sb[OP_POLYS];
+  for (u32 i = t; i < n; i += 256) {
+    const u64 za = pa[i], zb = pb[i];
+#pragma unroll
+    for (u32 q = 0; q < OP_POLYS; q++)
+      if (q < nq) {
+        const u64 v = c[q][i];
+        sa[q].add(v, za);
+        sb[q].add(v, zb);
+      }
   }
-  __shared__ u64 ra[256], rb[256];
-  ra[t] = acc.a; rb[t] = acc.b;
+  __shared__ u64 ra[OP_POLYS][256], rb[OP_POLYS][256];
+#pragma unroll
+  for (u32 q = 0; q < OP_POLYS; q++) { ra[q][t] = sa[q].value(); rb[q][t] = sb[q].value(); }
   __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if ((int)t < s) { ra[t] = gl_add(ra[t], ra[t + s]); rb[t] = gl_add(rb[t], rb[t + s]); }
+  for (u32 s = 128; s > 0; s >>= 1) {
+    if (t < s)
+#pragma unroll
+      for (u32 q = 0; q < OP_POLYS; q++) { ra[q][t] = gl_add(ra[q][t], ra[q][t + s]); rb[q][t] = gl_add(rb[q][t], rb[q][t + s]); }
     __syncthreads();
   }
-  if (t == 0) {
-    u64* d = out + ((u64)b * (sh.n_polys + sh.zs_count + sh.lookup_count) + j) * 2;
-    d[0] = ra[0]; d[1] = rb[0];
+  if (t < nq) {
+    u64* d = out + ((u64)b * n_open + j0 + t) * 2;
+    d[0] = ra[t][0]; d[1] = rb[t][0];
   }
 }
 
-// ---- batch composition: comp[b][batch][c][i] = sum_j alpha^j f_j[i] ----------------------------
-__global__ void __launch_bounds__(256) compose_kernel(FriShape sh, const u64* alpha, u64 alpha_bstride, u64* comp) {
+// ---- batch composition: comp[b][batch][c][i] = sum_m alpha^m f_m[i] ----------------------------
+// m runs over the batch in fri_batch_poly order; apw[b] = [alpha^m][c0: apw_len][c1: apw_len] (ext_powers). Base x extension
+// products in carry-free columns, one reduction per point and component.
+__global__ void __launch_bounds__(256) compose_kernel(FriShape sh, const u64* __restrict__ apw, u64 apw_bstride, u32 apw_len, u64* comp) {
   const u32 n = 1u << sh.log_n;
   const u32 i = blockIdx.x * 256 + threadIdx.x, b = blockIdx.y, batch = blockIdx.z;
   if (i >= n) return;
-  gl2 al = gl2_make(alpha[b * alpha_bstride], alpha[b * alpha_bstride + 1]);
-  gl2 acc = gl2_make(0, 0);
-  // Horner from the back of the batch: runs of consecutive polynomials of one oracle (fri_batch_poly order)
+  const u64* pa = apw + b * apw_bstride;
+  const u64* pb = pa + apw_len;
+  gl_cols sa, sb;
+  u32 m = 0;
+  // runs of consecutive polynomials of one oracle (fri_batch_poly order)
   const u32 zo = sh.zs_oracle, wz = sh.o[zo].w - sh.lookup_count;
   auto run = [&](u32 o, u32 first, u32 count) {
     const u64* base = sh.o[o].coeffs + b * sh.o[o].coeff_bstride + i;
-    for (int p = (int)(first + count) - 1; p >= (int)first; p--) {
-      acc = gl2_mul(acc, al);
-      acc.a = gl_add(acc.a, base[(u64)p << sh.log_n]);
+    for (u32 p = first; p < first + count; p++, m++) {
+      const u64 v = base[(u64)p << sh.log_n];
+      sa.add(v, pa[m]);
+      sb.add(v, pb[m]);
     }
   };
-  if (sh.lookup_count) run(zo, wz, sh.lookup_count);
   if (batch == 0) {
-    for (int o = (int)sh.n_oracles - 1; o >= 0; o--) run((u32)o, 0, (u32)o == zo ? wz : sh.o[o].w);
+    for (u32 o = 0; o < sh.n_oracles; o++) run(o, 0, o == zo ? wz : sh.o[o].w);
   } else {
     run(zo, 0, sh.zs_count);
   }
+  if (sh.lookup_count) run(zo, wz, sh.lookup_count);
   u64* d = comp + (((u64)b * 2 + batch) * 2) * n;
-  d[i] = acc.a;
-  d[n + i] = acc.b;
+  d[i] = sa.value();
+  d[n + i] = sb.value();
 }
 
 // ---- divide_by_linear: q_i = sum_{k>i} c_k z^(k-i-1) -------------------------------------------
@@ -227,10 +270,11 @@ __global__ void __launch_bounds__(1024) divide_kernel(u32 log_n, const u64* zeta
   }
 }
 // final[b][c][i] = q_zeta[i] * alpha^zs_count + q_gzeta[i]
-__global__ void __launch_bounds__(256) combine_kernel(u32 log_n, u32 zs_count, const u64* alpha, u64 alpha_bstride, const u64* quot, u64* final_poly) {
+__global__ void __launch_bounds__(256) combine_kernel(u32 log_n, u32 zs_count, const u64* __restrict__ apw, u64 apw_bstride, u32 apw_len,
+                                                      const u64* quot, u64* final_poly) {
   const u32 n = 1u << log_n, i = blockIdx.x * 256 + threadIdx.x, b = blockIdx.y;
   if (i >= n) return;
-  gl2 sh = gl2_pow(gl2_make(alpha[b * alpha_bstride], alpha[b * alpha_bstride + 1]), zs_count);
+  const gl2 sh = gl2_make(apw[b * apw_bstride + zs_count], apw[b * apw_bstride + apw_len + zs_count]);  // alpha^zs_count
   const u64* q = quot + (u64)b * 4 * n;
   gl2 r = gl2_add(gl2_mul(gl2_make(q[i], q[n + i]), sh), gl2_make(q[2 * n + i], q[3 * n + i]));
   final_poly[(u64)b * 2 * n + i] = r.a;
@@ -412,17 +456,22 @@ __global__ void bind_pi_kernel(u64* wires, u64 wires_bstride, u64 n, u32 row, co
 // ---- launchers --------------------------------------------------------------------------------
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return e_; } while (0)
 
-hipError_t fri_openings(hipStream_t s, const FriShape& sh, u32 B, const u64* zeta, u64 zeta_bstride, u64* out) {
-  hipLaunchKernelGGL(openings_kernel, dim3(sh.n_polys + sh.zs_count + sh.lookup_count, B), dim3(256), 0, s, sh, zeta, zeta_bstride, out);
+hipError_t fri_openings(hipStream_t s, const FriShape& sh, u32 B, const u64* zeta, u64 zeta_bstride, u64* zpw, u64* out) {
+  const u32 n = 1u << sh.log_n, n_shifted = sh.zs_count + sh.lookup_count;
+  HIPCHK(ext_powers(s, B, zeta, zeta_bstride, 1, n, zpw, 4 * (u64)n));
+  if (n_shifted) HIPCHK(ext_powers(s, B, zeta, zeta_bstride, gl_root_of_unity(sh.log_n), n, zpw + 2 * (u64)n, 4 * (u64)n));
+  const u32 blocks = (sh.n_polys + OP_POLYS - 1) / OP_POLYS + (n_shifted + OP_POLYS - 1) / OP_POLYS;
+  hipLaunchKernelGGL(openings_kernel, dim3(blocks, B), dim3(256), 0, s, sh, zpw, 4 * (u64)n, out);
   return hipGetLastError();
 }
 hipError_t fri_final_poly(hipStream_t s, const FriShape& sh, u32 B, const u64* alpha, u64 alpha_bstride, const u64* zeta, u64 zeta_bstride,
-                          u64* comp, u64* quot, u64* final_poly) {
-  const u32 n = 1u << sh.log_n;
-  hipLaunchKernelGGL(compose_kernel, dim3((n + 255) / 256, B, 2), dim3(256), 0, s, sh, alpha, alpha_bstride, comp);
+                          u64* apw, u64* comp, u64* quot, u64* final_poly) {
+  const u32 n = 1u << sh.log_n, apw_len = fri_alpha_powers_len(sh);
+  HIPCHK(ext_powers(s, B, alpha, alpha_bstride, 1, apw_len, apw, 2 * (u64)apw_len));
+  hipLaunchKernelGGL(compose_kernel, dim3((n + 255) / 256, B, 2), dim3(256), 0, s, sh, apw, 2 * (u64)apw_len, apw_len, comp);
   hipLaunchKernelGGL(divide_kernel, dim3(2, B), dim3(1024), 0, s, sh.log_n, zeta, zeta_bstride, comp, quot);
-  hipLaunchKernelGGL(combine_kernel, dim3((n + 255) / 256, B), dim3(256), 0, s, sh.log_n, sh.zs_count + sh.lookup_count, alpha, alpha_bstride, quot,
-                     final_poly);
+  hipLaunchKernelGGL(combine_kernel, dim3((n + 255) / 256, B), dim3(256), 0, s, sh.log_n, sh.zs_count + sh.lookup_count, apw, 2 * (u64)apw_len,
+                     apw_len, quot, final_poly);
   return hipGetLastError();
 }
 hipError_t fri_fold_values(hipStream_t s, u32 B, u32 log_m, u32 ab, const u64* in, u64 in_bstride, u64* out, u64 out_bstride,

@@ -15,8 +15,12 @@ u32 gate_degree(const mp2g_gate& g);
 // q[b][a][i] (natural order i) = sum_g filter_g sum_j alpha_a^j c_{g,j} at the LDE point of memory column
 // p = bitrev(i): C / W are the bit-reversed LDE value matrices [.][N] of the constants (shared) and the
 // wires (per proof), N = 8n. quotient_perm_values(..., gates = true) folds q into the vanishing sum.
+// apw: the batch's alpha powers [B][2][MP2G_MAX_GATE_CONSTRAINTS] (alpha_powers).
 hipError_t gate_constraints_lde(hipStream_t s, u32 B, const GateTable& t, const u64* C, const u64* W, u64 w_bstride, u32 lg,
-                                const u64* alphas, u64 al_bstride, u32 nc, const u64* pi_hash, u64* q);
+                                const u64* apw, u32 nc, const u64* pi_hash, u64* q);
+// apw[b][a][e] = alpha_a^e for the nc <= 2 challenges alphas[b * al_bstride + a] (0 for a >= nc), e < MP2G_MAX_GATE_CONSTRAINTS:
+// the powers every alpha-reduction of the quotient reads (gate_constraints_lde, quotient_perm_values)
+hipError_t alpha_powers(hipStream_t s, u32 B, const u64* alphas, u64 al_bstride, u32 nc, u64* apw);
 // out[j][p] = C_j at point p (device pointers; consts [.][npts], wires [.][npts])
 hipError_t gate_constraints_points(hipStream_t s, const GateTable& t, const u64* consts, const u64* wires, u64 npts, u32 max_j,
                                    const u64* pi_hash, u64* out);

@@ -647,15 +647,15 @@ GLD u64 gate_filter(const GateTable& t, u32 gi, ConstAll call) {
 template <u32 KIND>
 __global__ void __launch_bounds__(256) gate_constraints_lde_kernel(mp2g_gate g, u32 gi, u32 num_selectors, u32 cst_off, u32 n_cons,
                                                                    const u64* __restrict__ C, const u64* __restrict__ W,
-                                                                   u64 w_bstride, u32 lg, const u64* __restrict__ alphas,
-                                                                   u64 al_bstride, u32 nc, const u64* __restrict__ pi_hash,
+                                                                   u64 w_bstride, u32 lg, const u64* __restrict__ apw_tab,
+                                                                   u32 nc, const u64* __restrict__ pi_hash,
                                                                    u64* __restrict__ q, int first) {
   __shared__ u64 apw[2][MP2G_MAX_GATE_CONSTRAINTS];
   const u64 N = (u64)1 << lg;
   const u32 p = blockIdx.x * 256 + threadIdx.x, b = blockIdx.y;
   for (u32 j = threadIdx.x; j < 2 * n_cons; j += 256) {
     const u32 a = j >= n_cons ? 1 : 0, e = j - a * n_cons;
-    apw[a][e] = a < nc ? gl_pow(alphas[b * al_bstride + a], e) : 0;
+    apw[a][e] = apw_tab[((u64)b * 2 + a) * MP2G_MAX_GATE_CONSTRAINTS + e];
   }
   __syncthreads();
   if (p >= N) return;
@@ -709,15 +709,15 @@ static bool gate_is_light(const mp2g_gate& g) {
 }
 __global__ void __launch_bounds__(256) gate_constraints_lde_light_kernel(LightGates lg_, u32 num_selectors, u32 cst_off, u32 max_cons,
                                                                          const u64* __restrict__ C, const u64* __restrict__ W,
-                                                                         u64 w_bstride, u32 lg, const u64* __restrict__ alphas,
-                                                                         u64 al_bstride, u32 nc, const u64* __restrict__ pi_hash,
+                                                                         u64 w_bstride, u32 lg, const u64* __restrict__ apw_tab,
+                                                                         u32 nc, const u64* __restrict__ pi_hash,
                                                                          u64* __restrict__ q, int first) {
   __shared__ u64 apw[2][MP2G_MAX_GATE_CONSTRAINTS];
   const u64 N = (u64)1 << lg;
   const u32 p = blockIdx.x * 256 + threadIdx.x, b = blockIdx.y;
   for (u32 j = threadIdx.x; j < 2 * max_cons; j += 256) {
     const u32 a = j >= max_cons ? 1 : 0, e = j - a * max_cons;
-    apw[a][e] = a < nc ? gl_pow(alphas[b * al_bstride + a], e) : 0;
+    apw[a][e] = apw_tab[((u64)b * 2 + a) * MP2G_MAX_GATE_CONSTRAINTS + e];
   }
   __syncthreads();
   if (p >= N) return;
@@ -815,8 +815,22 @@ hipError_t gate_check(hipStream_t s, u32 B, const GateTable& t, const u64* const
   return hipGetLastError();
 }
 
+// apw[b][a][e] = alpha_a^e (0 for a >= nc), e < MP2G_MAX_GATE_CONSTRAINTS: one lane per entry, once per batch
+__global__ void alpha_powers_kernel(const u64* __restrict__ alphas, u64 al_bstride, u32 nc, u32 B, u64* __restrict__ apw) {
+  const u32 t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= B * 2 * MP2G_MAX_GATE_CONSTRAINTS) return;
+  const u32 e = t % MP2G_MAX_GATE_CONSTRAINTS, a = (t / MP2G_MAX_GATE_CONSTRAINTS) & 1, b = t / (2 * MP2G_MAX_GATE_CONSTRAINTS);
+  apw[t] = a < nc ? gl_pow(alphas[b * al_bstride + a], e) : 0;
+}
+hipError_t alpha_powers(hipStream_t s, u32 B, const u64* alphas, u64 al_bstride, u32 nc, u64* apw) {
+  if (nc < 1 || nc > 2) return hipErrorInvalidValue;
+  const u32 total = B * 2 * MP2G_MAX_GATE_CONSTRAINTS;
+  hipLaunchKernelGGL(alpha_powers_kernel, dim3((total + 255) / 256), dim3(256), 0, s, alphas, al_bstride, nc, B, apw);
+  return hipGetLastError();
+}
+
 hipError_t gate_constraints_lde(hipStream_t s, u32 B, const GateTable& t, const u64* C, const u64* W, u64 w_bstride, u32 lg,
-                                const u64* alphas, u64 al_bstride, u32 nc, const u64* pi_hash, u64* q) {
+                                const u64* apw, u32 nc, const u64* pi_hash, u64* q) {
   if (nc < 1 || nc > 2) return hipErrorInvalidValue;
   const u64 N = (u64)1 << lg;
   const dim3 grid((u32)((N + 255) / 256), B), block(256);
@@ -834,7 +848,7 @@ hipError_t gate_constraints_lde(hipStream_t s, u32 B, const GateTable& t, const 
   if (lgs.n < 2) lgs.n = 0;  // a lone light gate goes the ordinary way
   if (lgs.n) {
     hipLaunchKernelGGL(gate_constraints_lde_light_kernel, grid, block, 0, s, lgs, t.num_selectors, t.num_selectors + t.num_lookup_selectors,
-                       light_cons, C, W, w_bstride, lg, alphas, al_bstride, nc, pi_hash, q, first);
+                       light_cons, C, W, w_bstride, lg, apw, nc, pi_hash, q, first);
     first = 0;
   }
   for (u32 gi = 0; gi < t.n_gates; gi++) {
@@ -847,7 +861,7 @@ hipError_t gate_constraints_lde(hipStream_t s, u32 B, const GateTable& t, const 
 #define GATE_CASE(K)                                                                                                        \
   case K:                                                                                                                   \
     hipLaunchKernelGGL(gate_constraints_lde_kernel<K>, grid, block, 0, s, g, gi, t.num_selectors,                          \
-                       t.num_selectors + t.num_lookup_selectors, n_cons, C, W, w_bstride, lg, alphas, al_bstride, nc, pi_hash, q, \
+                       t.num_selectors + t.num_lookup_selectors, n_cons, C, W, w_bstride, lg, apw, nc, pi_hash, q,             \
                        first);                                                                                              \
     break;
     switch (g.kind) {

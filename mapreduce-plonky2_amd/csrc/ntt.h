@@ -42,6 +42,8 @@ struct NttEngine {
                  u64 out_poly_stride, bool inverse, const CosetTables* pre, bool bitrev_out);
   // data[b][i] *= first * base^i
   hipError_t scale_powers(u64* data, u32 log_n, u32 batch, u64 base, u64 first);
+  // data[b][i] *= table[i] (a power table built once, e.g. the quotient's coset unshift)
+  hipError_t scale_table(u64* data, u32 log_n, u32 batch, const u64* table);
 };
 
 }  // namespace mp2g

@@ -666,6 +666,12 @@ __global__ void scale_powers_kernel(u64* data, u32 log_n, u32 batch, u64 base, u
   u64 k = i & (((u64)1 << log_n) - 1);
   data[i] = gl_mul(data[i], gl_mul(first, gl_pow(base, k)));
 }
+__global__ void scale_table_kernel(u64* __restrict__ data, u32 log_n, u32 batch, const u64* __restrict__ table) {
+  // data[b][i] *= table[i]
+  u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= ((u64)batch << log_n)) return;
+  data[i] = gl_mul(data[i], table[i & (((u64)1 << log_n) - 1)]);
+}
 
 // ---- host side ------------------------------------------------------------------------------
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return e_; } while (0)
@@ -926,6 +932,11 @@ hipError_t NttEngine::run(const u64* in, u64* out, u32 log_n, u32 polys, u32 log
 hipError_t NttEngine::scale_powers(u64* data, u32 log_n, u32 batch, u64 base, u64 first) {
   u64 total = (u64)batch << log_n;
   hipLaunchKernelGGL(scale_powers_kernel, dim3((u32)((total + 255) / 256)), dim3(256), 0, stream, data, log_n, batch, base, first);
+  return hipGetLastError();
+}
+hipError_t NttEngine::scale_table(u64* data, u32 log_n, u32 batch, const u64* table) {
+  u64 total = (u64)batch << log_n;
+  hipLaunchKernelGGL(scale_table_kernel, dim3((u32)((total + 255) / 256)), dim3(256), 0, stream, data, log_n, batch, table);
   return hipGetLastError();
 }
 

@@ -35,10 +35,13 @@ struct mp2g_prover {
   DevBuf coeffs[8], values[8], levels[8];
   DevBuf ch, chal, zeta, alpha, betas, comp, quot, final_poly, witness, qchal;
   DevBuf fvals[9], flevels[8], fcoeffs[9];
+  DevBuf zpw, fapw;  // per batch: powers of zeta and g zeta (openings), of the FRI alpha (batch composition)
   // permutation argument computed on the device (mp2g_prover_enable_permutation)
   uint32_t num_routed = 0, degree = 0;
   bool quotient = false;
   DevBuf pre_values, zs_values, chunk_q, bg, alphas, qvals;
+  DevBuf ptab, qtab;  // per circuit, built at set-up (zperm.h): subgroup powers and k_j; the quotient coset's x, L_0, 1/Z_H, unshift
+  DevBuf apw;         // per batch: alpha powers of the quotient's reductions [B][2][MP2G_MAX_GATE_CONSTRAINTS] (alpha_powers)
   // gate constraints (mp2g_prover_set_gates)
   GateTable gates{};
   // lookup argument (mp2g_prover_set_lookups): tables on the device, per-proof table polynomials
@@ -90,6 +93,16 @@ struct ProverGuard {
   mp2g_prover* pr = nullptr;
   ~ProverGuard();
 };
+// a table computed on the host and uploaded once, when the prover is set up (waits for the copy: the host memory goes away)
+template <class F>
+hipError_t upload_table(mp2g_ctx* c, DevBuf& d, size_t words, F fill) {
+  std::vector<u64> h(words);
+  fill(h.data());
+  hipError_t e = d.alloc(words * sizeof(u64));
+  if (e == hipSuccess) e = hipMemcpyAsync(d.p, h.data(), words * sizeof(u64), hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  return e;
+}
 }  // namespace
 
 namespace mp2g {
@@ -272,6 +285,7 @@ static int prover_create_impl(mp2g_ctx* c, const mp2g_fri_params* params, uint32
   if (e == hipSuccess) e = pr->ch.alloc(B * sizeof(ChState));
   A(pr->chal, B * 8); A(pr->zeta, B * 2); A(pr->alpha, B * 2); A(pr->betas, B * 16);
   S(pr->comp, B * 4 * n); S(pr->quot, B * 4 * n); S(pr->final_poly, B * 2 * n);
+  S(pr->zpw, B * 4 * n); A(pr->fapw, B * 2 * (pr->n_open + 1));
   A(pr->witness, B * FRI_POW_STRIDE); A(pr->qchal, B * (P.num_queries ? P.num_queries : 1));
   size_t m = N, nc = n;
   uint32_t clg = lg;
@@ -350,6 +364,7 @@ int mp2g_prover_enable_permutation(mp2g_prover* pr, uint32_t num_routed, uint32_
   CK(pr->want(pr->chunk_q, (size_t)pr->Bcap * P.zs_count * (num_routed / degree) * n * sizeof(u64)));
   CK(pr->bg.alloc((size_t)pr->Bcap * 8 * sizeof(u64)));  // betas, gammas (+ the 2 * num_challenges extra lookup challenges)
   CK(pr->alphas.alloc((size_t)pr->Bcap * 2 * sizeof(u64)));
+  CK(upload_table(pr->ctx, pr->ptab, perm_table_words(P.log_n, num_routed), [&](u64* h) { perm_tables_host(P.log_n, num_routed, h); }));
   pr->num_routed = num_routed; pr->degree = degree;
   pr->drop_graph();
   return 0;
@@ -361,6 +376,8 @@ int mp2g_prover_enable_quotient(mp2g_prover* pr) {
   NEED(P.oracle_w[3] == P.zs_count * 8, "oracle_w[3] must be zs_count * 8 quotient chunks");
   NEED(P.log_n + 3 <= 24, "log_n <= 21");
   CK(pr->want(pr->qvals, (size_t)pr->Bcap * P.zs_count * ((size_t)8 << P.log_n) * sizeof(u64)));
+  CK(pr->apw.alloc((size_t)pr->Bcap * 2 * MP2G_MAX_GATE_CONSTRAINTS * sizeof(u64)));
+  CK(upload_table(pr->ctx, pr->qtab, quotient_table_words(P.log_n), [&](u64* h) { quotient_tables_host(P.log_n, h); }));
   pr->quotient = true;
   pr->drop_graph();
   return 0;
@@ -401,7 +418,7 @@ static int fri_tail(mp2g_prover* pr, const FriShape& sh, ChState* st, u64* d_pro
   const size_t capw = pr->capw;
   u64* chal = pr->chal.p;
   CK(challenger_step(s, V, st, B, chal, 0, 0, pr->alpha.p, 2, 2));  // alpha
-  CK(fri_final_poly(s, sh, B, pr->alpha.p, 2, pr->zeta.p, 2, pr->comp.p, pr->quot.p, pr->final_poly.p));
+  CK(fri_final_poly(s, sh, B, pr->alpha.p, 2, pr->zeta.p, 2, pr->fapw.p, pr->comp.p, pr->quot.p, pr->final_poly.p));
   CosetTables* pre;
   CK(c->ntt.coset(P.log_n, P.rate_bits, GL_MULT_GEN, &pre));
   CK(c->ntt.run(pr->final_poly.p, pr->fvals[0].p, P.log_n, 2 * B, P.rate_bits, n, N, false, pre, true));
@@ -557,8 +574,8 @@ static int prove_impl(mp2g_prover* pr, const uint64_t* const* d_values, const ui
       // betas = bg[0..nc), gammas = bg[nc..2nc) of every transcript (drawn after the wires cap:
       // get_n_challenges(num_challenges) twice)
       CK(zpp_compute(s, B, (const u64*)d_values[0], (u64)P.oracle_w[1] * n, pr->pre_values.p + (u64)(P.oracle_w[0] - pr->num_routed) * n,
-                     P.log_n, pr->num_routed, pr->degree, pr->bg.p, pr->bg.p + P.zs_count, 8, P.zs_count, pr->chunk_q.p, pr->zs_values.p,
-                     (u64)P.oracle_w[2] * n));
+                     P.log_n, pr->num_routed, pr->degree, pr->bg.p, pr->bg.p + P.zs_count, 8, P.zs_count, pr->ptab.p, pr->chunk_q.p,
+                     pr->zs_values.p, (u64)P.oracle_w[2] * n));
       if (pr->lookups.n_luts) {
         // compute_all_lookup_polys: deltas of round c = bg[4c .. 4c+4) (betas ++ gammas ++ the extra challenges)
         CK(lookup_table_polys(s, B, pr->lookups, pr->bg.p, 8, P.zs_count, pr->lut_eval.p));
@@ -575,9 +592,10 @@ static int prove_impl(mp2g_prover* pr, const uint64_t* const* d_values, const ui
       // compute_quotient_polys (gate constraints first, then folded into the permutation terms): values on the coset, coset iFFT, and the
       // 8n coefficients of each challenge are its 8 degree-n chunks, already laid out as oracle 3's coeffs
       const u32 nc = P.zs_count;
+      CK(alpha_powers(s, B, pr->alphas.p, 2, nc, pr->apw.p));
       if (pr->gates.n_gates)
-        CK(gate_constraints_lde(s, B, pr->gates, pr->values[0].p, pr->values[1].p, (u64)P.oracle_w[1] * N, P.log_n + 3, pr->alphas.p, 2,
-                                nc, (const u64*)d_pi_hash, pr->qvals.p));
+        CK(gate_constraints_lde(s, B, pr->gates, pr->values[0].p, pr->values[1].p, (u64)P.oracle_w[1] * N, P.log_n + 3, pr->apw.p, nc,
+                                (const u64*)d_pi_hash, pr->qvals.p));
       // vanishing_all_lookup_terms sit between the partial-product and the gate terms of the alpha-reduction
       if (pr->lookups.n_luts)
         CK(quotient_lookup_values(s, B, pr->lookups, pr->values[0].p, pr->gates.num_selectors, pr->values[1].p, (u64)P.oracle_w[1] * N,
@@ -585,9 +603,9 @@ static int prove_impl(mp2g_prover* pr, const uint64_t* const* d_values, const ui
                                   pr->lut_eval.p, pr->alphas.p, 2, nc, pr->qvals.p));
       CK(quotient_perm_values(s, B, pr->values[1].p, (u64)P.oracle_w[1] * N, pr->values[0].p + (u64)(P.oracle_w[0] - pr->num_routed) * N,
                               pr->values[2].p, (u64)P.oracle_w[2] * N, P.log_n, pr->num_routed, pr->degree, pr->bg.p, 8,
-                              pr->alphas.p, 2, nc, pr->gates.n_gates != 0, pr->qvals.p));
+                              pr->apw.p, MP2G_MAX_GATE_CONSTRAINTS, nc, pr->gates.n_gates != 0, pr->ptab.p, pr->qtab.p, pr->qvals.p));
       CK(c->ntt.run(pr->qvals.p, pr->coeffs[3].p, P.log_n + 3, B * nc, 0, N, N, true, nullptr, false));
-      CK(c->ntt.scale_powers(pr->coeffs[3].p, P.log_n + 3, B * nc, gl_inv(GL_MULT_GEN), 1));
+      CK(c->ntt.scale_table(pr->coeffs[3].p, P.log_n + 3, B * nc, pr->qtab.p + quotient_unshift_offset(P.log_n)));  // coefficient k times g^-k
       CK(commit_oracle_coeffs(pr, 3, B));
     } else {
       NEED(vals, "d_values[o]");
@@ -621,7 +639,7 @@ static int prove_impl(mp2g_prover* pr, const uint64_t* const* d_values, const ui
     r.level_bstride = o ? LW : 0;
     sh.n_polys += r.w;
   }
-  CK(fri_openings(s, sh, B, pr->zeta.p, 2, (u64*)d_openings));
+  CK(fri_openings(s, sh, B, pr->zeta.p, 2, pr->zpw.p, (u64*)d_openings));
   CK(challenger_step(s, V, st, B, (const u64*)d_openings, 2 * pr->n_open, (u32)(2 * pr->n_open), chal, 8, 0));
   STAGE_MARK(pr, 4);  // openings
   int rc = fri_tail(pr, sh, st, (u64*)d_proof);
@@ -749,7 +767,8 @@ int mp2g_partial_products_and_zs(mp2g_ctx* c, const uint64_t* wires, uint32_t wi
   NEED(log_n >= 1 && log_n <= 20 && nc >= 1 && nc <= 4, "log_n/nc");
   NEED(degree >= 1 && num_routed >= degree && num_routed % degree == 0 && num_routed / degree <= 16 && num_routed <= wires_w, "num_routed/degree");
   const size_t n = (size_t)1 << log_n, chunks = num_routed / degree;
-  DevBuf dw, ds, dc, dq, dout;
+  DevBuf dw, ds, dc, dq, dout, dt;
+  CK(upload_table(c, dt, perm_table_words(log_n, num_routed), [&](u64* h) { perm_tables_host(log_n, num_routed, h); }));
   CK(dw.alloc(wires_w * n * sizeof(u64)));
   CK(ds.alloc(num_routed * n * sizeof(u64)));
   CK(dc.alloc(2 * nc * sizeof(u64)));
@@ -759,7 +778,7 @@ int mp2g_partial_products_and_zs(mp2g_ctx* c, const uint64_t* wires, uint32_t wi
   CK(hipMemcpyAsync(ds.p, sigmas, num_routed * n * sizeof(u64), hipMemcpyHostToDevice, c->stream));
   CK(hipMemcpyAsync(dc.p, betas, nc * sizeof(u64), hipMemcpyHostToDevice, c->stream));
   CK(hipMemcpyAsync(dc.p + nc, gammas, nc * sizeof(u64), hipMemcpyHostToDevice, c->stream));
-  CK(zpp_compute(c->stream, 1, dw.p, 0, ds.p, log_n, num_routed, degree, dc.p, dc.p + nc, 0, nc, dq.p, dout.p, 0));
+  CK(zpp_compute(c->stream, 1, dw.p, 0, ds.p, log_n, num_routed, degree, dc.p, dc.p + nc, 0, nc, dt.p, dq.p, dout.p, 0));
   CK(hipMemcpyAsync(out, dout.p, nc * chunks * n * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
   CK(hipStreamSynchronize(c->stream));
   return 0;
@@ -806,11 +825,12 @@ int mp2g_batch_eval_ext(const mp2g_batch* b, const uint64_t point[2], uint64_t* 
   FriShape sh{};
   sh.log_n = b->log_n; sh.rate_bits = b->rate_bits; sh.cap_h = b->cap_h; sh.n_oracles = 1; sh.n_polys = b->w;
   sh.o[0].coeffs = b->coeffs.p; sh.o[0].w = b->w;
-  DevBuf dz, dout;
+  DevBuf dz, dout, dzpw;
   CK(dz.alloc(2 * sizeof(u64)));
   CK(dout.alloc((size_t)b->w * 2 * sizeof(u64)));
+  CK(dzpw.alloc(((size_t)4 << b->log_n) * sizeof(u64)));
   CK(hipMemcpyAsync(dz.p, point, 2 * sizeof(u64), hipMemcpyHostToDevice, c->stream));
-  CK(fri_openings(c->stream, sh, 1, dz.p, 0, dout.p));
+  CK(fri_openings(c->stream, sh, 1, dz.p, 0, dzpw.p, dout.p));
   CK(hipMemcpyAsync(out, dout.p, (size_t)b->w * 2 * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
   CK(hipStreamSynchronize(c->stream));
   return 0;

@@ -11,28 +11,31 @@
 // into num_routed/degree chunk quotients with one batched inversion; (2) one block per
 // (challenge, proof) turns the per-row products into running products with an in-LDS scan.
 #include "zperm.h"
+#include <vector>
 
 namespace mp2g {
 
 #define ZP_MAX_CHUNKS 16
 #define ZP_MAX_ROUTED 256
-// k_j = g^j (cosets.rs get_unique_coset_shifts) for the block, in LDS
-__device__ __forceinline__ void fill_k_is(u64* kis, u32 num_routed) {
-  for (u32 j = threadIdx.x; j < num_routed; j += blockDim.x) kis[j] = gl_pow(GL_MULT_GEN, j);
+#define ZP_MAX_TERMS (2 * (1 + ZP_MAX_CHUNKS))  // alpha-reduced permutation terms of at most two challenges
+// k_j = g^j (cosets.rs get_unique_coset_shifts) for the block, in LDS, copied from the circuit's table (zperm.h)
+__device__ __forceinline__ void fill_k_is(u64* kis, const u64* __restrict__ ktab, u32 num_routed) {
+  for (u32 j = threadIdx.x; j < num_routed; j += blockDim.x) kis[j] = ktab[j];
   __syncthreads();
 }
 
 // chunk_q[((b*nc + c)*chunks + k)*n + i] = prod_{j in chunk k} (w_j + beta k_j x + gamma) / (w_j + beta sigma_j + gamma)
 __global__ void __launch_bounds__(256) zpp_chunk_kernel(const u64* __restrict__ wires, u64 wires_bstride, const u64* __restrict__ sigmas,
                                                         u32 log_n, u32 num_routed, u32 degree, const u64* __restrict__ betas,
-                                                        const u64* __restrict__ gammas, u64 chal_bstride, u32 nc, u64* __restrict__ chunk_q) {
+                                                        const u64* __restrict__ gammas, u64 chal_bstride, u32 nc,
+                                                        const u64* __restrict__ ptab, u64* __restrict__ chunk_q) {
   const u32 n = 1u << log_n, i = blockIdx.x * 256 + threadIdx.x, c = blockIdx.y, b = blockIdx.z;
   __shared__ u64 kis[ZP_MAX_ROUTED];
-  fill_k_is(kis, num_routed);
+  fill_k_is(kis, ptab + n, num_routed);
   if (i >= n) return;
   const u32 chunks = num_routed / degree;
   const u64 beta = betas[b * chal_bstride + c], gamma = gammas[b * chal_bstride + c];
-  const u64 bx = gl_mul(beta, gl_pow(gl_root_of_unity(log_n), i));
+  const u64 bx = gl_mul(beta, ptab[i]);  // beta w^i
   const u64* w = wires + b * wires_bstride + i;
   const u64* sg = sigmas + i;
   u64 num[ZP_MAX_CHUNKS], den[ZP_MAX_CHUNKS];
@@ -109,38 +112,37 @@ __global__ void __launch_bounds__(1024) zpp_scan_kernel(const u64* __restrict__ 
 __global__ void __launch_bounds__(256) quotient_perm_kernel(const u64* __restrict__ W, u64 w_bstride, const u64* __restrict__ S,
                                                             const u64* __restrict__ Z, u64 z_bstride, u32 log_n, u32 num_routed,
                                                             u32 degree, const u64* __restrict__ bg, u64 bg_bstride,
-                                                            const u64* __restrict__ alphas, u64 al_bstride, u32 nc, bool gates,
+                                                            const u64* __restrict__ apw, u32 apw_len, u32 nc, bool gates,
+                                                            const u64* __restrict__ ptab, const u64* __restrict__ qtab,
                                                             u64* __restrict__ q) {
   const u32 lg = log_n + 3;
   const u64 N = (u64)1 << lg;
   const u32 p = blockIdx.x * 256 + threadIdx.x, b = blockIdx.y;
   const u32 i = bitrev32(p, lg);
+  const u32 chunks = num_routed / degree, num_prods = chunks - 1, n_terms = nc * (1 + chunks);
   __shared__ u64 zh_inv[8];
   __shared__ u64 kis[ZP_MAX_ROUTED];
-  fill_k_is(kis, num_routed);
-  if (threadIdx.x < 8) {
-    u64 gn = gl_pow(GL_MULT_GEN, (u64)1 << log_n);
-    zh_inv[threadIdx.x] = gl_inv(gl_sub(gl_mul(gn, gl_pow(gl_root_of_unity(3), threadIdx.x)), 1));
+  __shared__ u64 al[2][ZP_MAX_TERMS + 1];  // alpha_a^k, k <= n_terms (the last one scales the gate terms)
+  if (threadIdx.x < 8) zh_inv[threadIdx.x] = qtab[2 * N + threadIdx.x];
+  for (u32 e = threadIdx.x; e < 2 * (n_terms + 1); e += 256) {
+    const u32 a = e / (n_terms + 1), k = e % (n_terms + 1);
+    al[a][k] = apw[((u64)b * 2 + a) * apw_len + k];
   }
-  __syncthreads();
+  fill_k_is(kis, ptab + (N >> 3), num_routed);
   if (p >= N) return;
-  const u32 chunks = num_routed / degree, num_prods = chunks - 1;
   const u64 pn = bitrev32((i + 8) & (u32)(N - 1), lg);
-  const u64 x = gl_mul(GL_MULT_GEN, gl_pow(gl_root_of_unity(lg), i));
+  // the circuit's coset tables in memory order: x = g w_N^i and L_0(x) = (x^n - 1) / (n (x - 1))
+  const u64 x = qtab[p], l0 = qtab[N + p];
   const u64* w = W + b * w_bstride + p;
   const u64* sg = S + p;
   const u64* z = Z + b * z_bstride;
-  u64 acc[2] = {0, 0}, apow[2] = {1, 1}, al[2];
-  for (u32 a = 0; a < nc; a++) al[a] = alphas[b * al_bstride + a];
+  // sum_k alpha^k terms[k] in carry-free columns (gl_cols), reduced once per challenge
+  gl_cols acc[2];
+  u32 kt = 0;
   auto push = [&](u64 term) {
-    for (u32 a = 0; a < nc; a++) {
-      acc[a] = gl_mul_add(term, apow[a], acc[a]);  // term: any representative
-      apow[a] = gl_mul(apow[a], al[a]);
-    }
+    for (u32 a = 0; a < nc; a++) acc[a].add(term, al[a][kt]);
+    kt++;
   };
-  // L_0(x) = (x^n - 1) / (n (x - 1)); x^n - 1 = 1 / zh_inv
-  const u64 zh = gl_inv(zh_inv[i & 7]);
-  const u64 l0 = gl_mul(zh, gl_inv(gl_mul(((u64)1 << log_n) % GL_P, gl_sub(x, 1))));
   for (u32 c = 0; c < nc; c++) push(gl_mul(l0, gl_sub(z[((u64)c << lg) + p], 1)));
   for (u32 c = 0; c < nc; c++) {
     const u64 beta = bg[b * bg_bstride + c], gamma = bg[b * bg_bstride + nc + c];
@@ -161,18 +163,20 @@ __global__ void __launch_bounds__(256) quotient_perm_kernel(const u64* __restric
       prev = next;
     }
   }
-  // gate constraint terms follow (gates.hip left sum_j alpha^j C_j(x) in this lane's slot)
+  // gate constraint terms follow (gates.hip left sum_j alpha^j C_j(x) in this lane's slot), scaled by alpha^n_terms
   if (gates)
-    for (u32 a = 0; a < nc; a++) acc[a] = gl_add(acc[a], gl_mul(apow[a], q[(((u64)b * nc + a) << lg) + i]));
-  for (u32 a = 0; a < nc; a++) q[(((u64)b * nc + a) << lg) + i] = gl_mul(acc[a], zh_inv[i & 7]);
+    for (u32 a = 0; a < nc; a++) acc[a].add(q[(((u64)b * nc + a) << lg) + i], al[a][n_terms]);
+  for (u32 a = 0; a < nc; a++) q[(((u64)b * nc + a) << lg) + i] = gl_mul(acc[a].value(), zh_inv[i & 7]);
 }
 hipError_t quotient_perm_values(hipStream_t s, u32 B, const u64* W, u64 w_bstride, const u64* S, const u64* Z, u64 z_bstride,
-                                u32 log_n, u32 num_routed, u32 degree, const u64* bg, u64 bg_bstride, const u64* alphas,
-                                u64 al_bstride, u32 nc, bool gates, u64* q) {
-  if (nc < 1 || nc > 2 || !degree || num_routed % degree || num_routed > ZP_MAX_ROUTED) return hipErrorInvalidValue;
+                                u32 log_n, u32 num_routed, u32 degree, const u64* bg, u64 bg_bstride, const u64* apw, u32 apw_len,
+                                u32 nc, bool gates, const u64* ptab, const u64* qtab, u64* q) {
+  if (nc < 1 || nc > 2 || !degree || num_routed % degree || num_routed > ZP_MAX_ROUTED || num_routed / degree > ZP_MAX_CHUNKS ||
+      apw_len < nc * (1 + num_routed / degree) + 1)
+    return hipErrorInvalidValue;
   const u64 N = (u64)8 << log_n;
   hipLaunchKernelGGL(quotient_perm_kernel, dim3((u32)((N + 255) / 256), B), dim3(256), 0, s, W, w_bstride, S, Z, z_bstride, log_n,
-                     num_routed, degree, bg, bg_bstride, alphas, al_bstride, nc, gates, q);
+                     num_routed, degree, bg, bg_bstride, apw, apw_len, nc, gates, ptab, qtab, q);
   return hipGetLastError();
 }
 
@@ -195,14 +199,57 @@ hipError_t zpp_wrap_check(hipStream_t s, u32 B, const u64* chunk_q, const u64* z
 }
 
 hipError_t zpp_compute(hipStream_t s, u32 B, const u64* wires, u64 wires_bstride, const u64* sigmas, u32 log_n, u32 num_routed,
-                       u32 degree, const u64* betas, const u64* gammas, u64 chal_bstride, u32 nc, u64* chunk_q, u64* out,
-                       u64 out_bstride) {
+                       u32 degree, const u64* betas, const u64* gammas, u64 chal_bstride, u32 nc, const u64* ptab, u64* chunk_q,
+                       u64* out, u64 out_bstride) {
   if (!degree || num_routed % degree || num_routed / degree > ZP_MAX_CHUNKS || num_routed / degree < 1 || num_routed > ZP_MAX_ROUTED)
     return hipErrorInvalidValue;
   const u32 n = 1u << log_n, chunks = num_routed / degree;
   hipLaunchKernelGGL(zpp_chunk_kernel, dim3((n + 255) / 256, nc, B), dim3(256), 0, s, wires, wires_bstride, sigmas, log_n, num_routed,
-                     degree, betas, gammas, chal_bstride, nc, chunk_q);
+                     degree, betas, gammas, chal_bstride, nc, ptab, chunk_q);
   hipLaunchKernelGGL(zpp_scan_kernel, dim3(nc, B), dim3(1024), 0, s, chunk_q, log_n, chunks, nc, out, out_bstride);
   return hipGetLastError();
+}
+
+// ---- per-circuit tables (zperm.h): computed on the host when the prover is set up, one multiply per entry ----
+size_t perm_table_words(u32 log_n, u32 num_routed) { return ((size_t)1 << log_n) + num_routed; }
+size_t quotient_table_words(u32 log_n) { return quotient_unshift_offset(log_n) + ((size_t)8 << log_n); }
+void perm_tables_host(u32 log_n, u32 num_routed, u64* out) {
+  const size_t n = (size_t)1 << log_n;
+  const u64 w = gl_root_of_unity(log_n);
+  u64 v = 1;
+  for (size_t i = 0; i < n; i++, v = gl_mul(v, w)) out[i] = v;
+  v = 1;
+  for (u32 j = 0; j < num_routed; j++, v = gl_mul(v, GL_MULT_GEN)) out[n + j] = v;
+}
+void quotient_tables_host(u32 log_n, u64* out) {
+  const u32 lg = log_n + 3;
+  const size_t N = (size_t)1 << lg;
+  u64 *tx = out, *tl = out + N, *zh_inv = out + 2 * N, *unshift = out + quotient_unshift_offset(log_n);
+  u64 zh[8];
+  const u64 gn = gl_pow(GL_MULT_GEN, (u64)1 << log_n), w8 = gl_root_of_unity(3);
+  for (u32 r = 0; r < 8; r++) {
+    zh[r] = gl_sub(gl_mul(gn, gl_pow(w8, r)), 1);
+    zh_inv[r] = gl_inv(zh[r]);
+  }
+  // x_i = g w_N^i in natural order; the denominators n (x_i - 1) of L_0 inverted together (Montgomery), never zero: g is no root of unity
+  std::vector<u64> x(N), pre(N);
+  const u64 wN = gl_root_of_unity(lg), n_mod = ((u64)1 << log_n) % GL_P;
+  u64 v = GL_MULT_GEN, acc = 1;
+  for (size_t i = 0; i < N; i++, v = gl_mul(v, wN)) {
+    x[i] = v;
+    pre[i] = acc;
+    acc = gl_mul(acc, gl_mul(n_mod, gl_sub(v, 1)));
+  }
+  u64 inv = gl_inv(acc);
+  for (size_t i = N; i-- > 0;) {
+    const u64 d = gl_mul(n_mod, gl_sub(x[i], 1));
+    const u32 p = bitrev32((u32)i, lg);
+    tx[p] = x[i];
+    tl[p] = gl_mul(zh[i & 7], gl_mul(inv, pre[i]));
+    inv = gl_mul(inv, d);
+  }
+  const u64 g_inv = gl_inv(GL_MULT_GEN);
+  v = 1;
+  for (size_t k = 0; k < N; k++, v = gl_mul(v, g_inv)) unshift[k] = v;
 }
 }  // namespace mp2g
