@@ -11,6 +11,7 @@
 // (#constraints - 1) fewer multiplications per gate and challenge.
 #include "gates.h"
 #include "poseidon.cuh"
+#include "coset_constants.h"
 
 namespace mp2g {
 
@@ -113,12 +114,18 @@ const char* gate_table_check(const GateTable& t, u32 num_constants, u32 wires_w)
 }
 
 struct Alg { u64 a, b; };  // ExtensionAlgebra element over the evaluation field, X^2 = 7
-GLD Alg alg_mul(Alg x, Alg y) {
-  return Alg{gl_mul_add(x.a, y.a, gl_mul_small_w(gl_mulw(x.b, y.b), 7)), gl_mul_add(x.a, y.b, gl_mulw(x.b, y.a))};
+// x y + z over the algebra as weak representatives, for values that feed further products or the lazy accumulator. Every operand
+// may be any u64; y7 is some representative of 7 y.b, which the callers form once where y.b is the same for a whole loop. The
+// second product of a component and the addend ride in the addend slots of the multiply-adds (gl_mul_add_wide), so a component
+// costs two wide products and two weak reductions and no carry chain. (One carry-free column sum per component, gl_cols, was
+// tried first: placing the eight 32-bit words of two products next to a zero word for the 64-bit column adds costs more moves
+// than the second reduction does, 220 against 182 vector instructions for a ReducingGate coefficient.)
+GLD Alg alg_mul_addw(Alg x, Alg y, u64 y7, Alg z) {
+  return Alg{gl_mul_addw(x.a, y.a, gl_mul_addw(x.b, y7, z.a)), gl_mul_addw(x.a, y.b, gl_mul_addw(x.b, y.a, z.b))};
 }
-GLD Alg alg_add(Alg x, Alg y) { return Alg{gl_add(x.a, y.a), gl_add(x.b, y.b)}; }
-GLD Alg alg_sub(Alg x, Alg y) { return Alg{gl_sub(x.a, y.a), gl_sub(x.b, y.b)}; }
-GLD Alg alg_scale(Alg x, u64 c) { return Alg{gl_mul(x.a, c), gl_mul(x.b, c)}; }
+GLD Alg alg_mulw(Alg x, Alg y, u64 y7) { return Alg{gl_mul_addw(x.a, y.a, gl_mulw(x.b, y7)), gl_mul_addw(x.a, y.b, gl_mulw(x.b, y.a))}; }
+// s x + z
+GLD Alg alg_scale_addw(Alg x, u64 s, Alg z) { return Alg{gl_mul_addw(x.a, s, z.a), gl_mul_addw(x.b, s, z.b)}; }
 
 // a - b for any u64 a and canonical b, as some u64 representative
 GLD u64 gl_subw(u64 a, u64 b) {
@@ -151,7 +158,7 @@ GLD void ra_copy(WireF& wire, Emit& emit, u32 w0, u32 b0) {
 #pragma unroll
   for (int i = 0; i < BITS; i++) {
 #pragma unroll
-    for (int k = 0; k < (VS >> (i + 1)); k++) items[k] = gl_add(items[2 * k], gl_mul(bit[i], gl_sub(items[2 * k + 1], items[2 * k])));
+    for (int k = 0; k < (VS >> (i + 1)); k++) items[k] = gl_mul_add(bit[i], gl_sub(items[2 * k + 1], items[2 * k]), items[2 * k]);
   }
   emit(gl_sub(items[0], claimed));
 }
@@ -163,6 +170,9 @@ __device__ __forceinline__ void eval_gate(const mp2g_gate g, WireF wire, ConstF 
   auto diff0 = [](u64 s, u64 in) { return WEAK ? gl_subw(s, in) : gl_sub(gl_canon(s), in); };
   // product that only feeds further products or emit(): a weak representative is enough there
   auto mulx = [](u64 a, u64 b) { return WEAK ? gl_mulw(a, b) : gl_mul(a, b); };
+  // difference that only feeds emit() or a product (a: any u64 if WEAK, b canonical), and a weak value on its way to emit()
+  auto subx = [](u64 a, u64 b) { return WEAK ? gl_subw(a, b) : gl_sub(a, b); };
+  auto outx = [](u64 v) { return WEAK ? v : gl_canon(v); };
   // Up to 16 wires in flight at once. The gate bodies are loops with run-time bounds, and a loop that fetches one
   // wire per iteration exposes one global-load latency per constraint (measured: the limb-heavy gates ran at half of
   // their instruction-issue time); fetching a batch first lets the loads overlap.
@@ -180,23 +190,25 @@ __device__ __forceinline__ void eval_gate(const mp2g_gate g, WireF wire, ConstF 
     if (!WEAK) return gl_add(gl_mul_small(acc, 4), limb);
     return gl_addw(gl_reduce96w(acc << 2, acc >> 62), limb);
   };
-  auto subx = [](u64 a, u64 b) { return WEAK ? gl_subw(a, b) : gl_sub(a, b); };
+  // a constraint of the extension-algebra gates: any representative for the lazy accumulator, canonical where it leaves the kernel
+  auto emit_alg = [&](Alg d) { emit(outx(d.a)); emit(outx(d.b)); };
+  auto alg_subx = [&](Alg x, Alg y) { return Alg{subx(x.a, y.a), subx(x.b, y.b)}; };  // x any (canonical if !WEAK), y canonical
   switch (g.kind) {
     case MP2G_GATE_CONSTANT:
-      for (u32 i = 0; i < g.p0; i++) emit(gl_sub(cst(i), wire(i)));
+      for (u32 i = 0; i < g.p0; i++) emit(subx(cst(i), wire(i)));
       break;
     case MP2G_GATE_PUBLIC_INPUT:
-      for (u32 i = 0; i < 4; i++) emit(gl_sub(wire(i), pih[i]));
+      for (u32 i = 0; i < 4; i++) emit(subx(wire(i), pih[i]));
       break;
     case MP2G_GATE_ARITHMETIC: {
-      const u64 c0 = cst(0), c1 = cst(1);
+      const u64 n0 = gl_neg(cst(0)), n1 = gl_neg(cst(1));  // output - c0 m0 m1 - c1 addend as one chain of multiply-adds
       u64 lm[16];
       for (u32 i0 = 0; i0 < g.p0; i0 += 4) {  // four operations = sixteen wires in flight
         const u32 cnt = g.p0 - i0 < 4 ? g.p0 - i0 : 4;
         load16(4 * i0, 4 * cnt, lm);
 #pragma unroll
         for (u32 k = 0; k < 4; k++)
-          if (k < cnt) emit(gl_sub(lm[4 * k + 3], gl_mul_add(gl_mulw(lm[4 * k], lm[4 * k + 1]), c0, gl_mulw(lm[4 * k + 2], c1))));
+          if (k < cnt) emit(outx(gl_mul_addw(gl_mulw(lm[4 * k], lm[4 * k + 1]), n0, gl_mul_addw(lm[4 * k + 2], n1, lm[4 * k + 3]))));
       }
       break;
     }
@@ -207,10 +219,10 @@ __device__ __forceinline__ void eval_gate(const mp2g_gate g, WireF wire, ConstF 
         load16(1 + lo, cnt, lm);
 #pragma unroll
         for (int j = 15; j >= 0; j--)
-          if ((u32)j < cnt) acc = gl_add(gl_mul_small(acc, g.p1), lm[j]);
+          if ((u32)j < cnt) acc = gl_addw(gl_mul_small_w(acc, g.p1), lm[j]);  // weak Horner: the limbs are wires, canonical
         hi = lo;
       }
-      emit(gl_sub(acc, wire(0)));
+      emit(subx(outx(acc), wire(0)));
       for (u32 lo = 0; lo < g.p0; lo += 16) {
         const u32 cnt = g.p0 - lo < 16 ? g.p0 - lo : 16;
         load16(1 + lo, cnt, lm);
@@ -218,7 +230,7 @@ __device__ __forceinline__ void eval_gate(const mp2g_gate g, WireF wire, ConstF 
         for (int j = 0; j < 16; j++) {
           if ((u32)j < cnt) {
             u64 pr = lm[j];  // k = 0 factor
-            for (u32 k = 1; k < g.p1; k++) pr = mulx(pr, gl_sub(lm[j], k));
+            for (u32 k = 1; k < g.p1; k++) pr = mulx(pr, subx(lm[j], k));
             emit(pr);
           }
         }
@@ -226,7 +238,7 @@ __device__ __forceinline__ void eval_gate(const mp2g_gate g, WireF wire, ConstF 
       break;
     }
     case MP2G_GATE_ARITHMETIC_EXT: {
-      const u64 c0 = cst(0), c1 = cst(1);
+      const u64 n0 = gl_neg(cst(0)), n1 = gl_neg(cst(1));  // output - c0 m0 m1 - c1 addend as a sum of products
       u64 lm[16];
       for (u32 i0 = 0; i0 < g.p0; i0 += 2) {  // two operations = sixteen wires in flight
         const u32 cnt = g.p0 - i0 < 2 ? g.p0 - i0 : 2;
@@ -236,15 +248,14 @@ __device__ __forceinline__ void eval_gate(const mp2g_gate g, WireF wire, ConstF 
           if (k < cnt) {
             const u64* w8 = lm + 8 * k;
             Alg m0{w8[0], w8[1]}, m1{w8[2], w8[3]}, ad{w8[4], w8[5]}, o{w8[6], w8[7]};
-            Alg d = alg_sub(o, alg_add(alg_scale(alg_mul(m0, m1), c0), alg_scale(ad, c1)));
-            emit(d.a); emit(d.b);
+            emit_alg(alg_scale_addw(alg_mulw(m0, m1, gl_mul_small_w(m1.b, 7)), n0, alg_scale_addw(ad, n1, o)));
           }
         }
       }
       break;
     }
     case MP2G_GATE_MUL_EXT: {
-      const u64 c0 = cst(0);
+      const u64 n0 = gl_neg(cst(0));
       u64 lm[16];
       for (u32 i0 = 0; i0 < g.p0; i0 += 2) {  // two operations = twelve wires in flight
         const u32 cnt = g.p0 - i0 < 2 ? g.p0 - i0 : 2;
@@ -254,8 +265,7 @@ __device__ __forceinline__ void eval_gate(const mp2g_gate g, WireF wire, ConstF 
           if (k < cnt) {
             const u64* w6 = lm + 6 * k;
             Alg m0{w6[0], w6[1]}, m1{w6[2], w6[3]}, o{w6[4], w6[5]};
-            Alg d = alg_sub(o, alg_scale(alg_mul(m0, m1), c0));
-            emit(d.a); emit(d.b);
+            emit_alg(alg_scale_addw(alg_mulw(m0, m1, gl_mul_small_w(m1.b, 7)), n0, o));
           }
         }
       }
@@ -375,35 +385,36 @@ __device__ __forceinline__ void eval_gate(const mp2g_gate g, WireF wire, ConstF 
     case MP2G_GATE_COSET_INTERPOLATION: {
       // gates/coset_interpolation.rs: barycentric interpolation over the 2^p0-point subgroup in chunks of
       // `degree` (then degree - 1) points; the running (eval, prod) pair is checked against intermediate
-      // wires between chunks. For a two-adic subgroup the weights are w_i = x_i / n.
+      // wires between chunks. For a two-adic subgroup the weights are w_i = x_i / n; points and weights depend on the gate
+      // descriptor alone and come from coset_constants.h, indexed by the loop counter (wave-uniform: scalar loads). (eval, prod)
+      // stay weak inside a chunk and are canonicalised where they meet a wire.
       const u32 npts = 1u << g.p0, deg = g.p1, nint = (npts - 2) / (deg - 1);
       const u32 w_pt = 1 + 2 * npts, w_val = w_pt + 2, w_int = w_val + 2, w_sh = w_int + 4 * nint;
       const Alg pt{wire(w_pt), wire(w_pt + 1)}, sh{wire(w_sh), wire(w_sh + 1)};
-      Alg d0 = alg_sub(pt, alg_scale(sh, wire(0)));
-      emit(d0.a); emit(d0.b);
-      const u64 om = gl_root_of_unity(g.p0), ninv = gl_inv(npts);
-      u64 xi = 1;
+      emit_alg(alg_scale_addw(sh, gl_neg(wire(0)), pt));  // point - shift * wire 0
+      const u64 sh7 = gl_mul_small_w(sh.b, 7);
+      const u64* xs = COSET_POINTS + MP2G_COSET_TABLE(g.p0);
+      const u64* ws = COSET_WEIGHTS + MP2G_COSET_TABLE(g.p0);
       Alg ev{0, 0}, pr{1, 0};
       u32 start = 0, end = deg;
       for (u32 c = 0; c <= nint; c++) {
         for (u32 i = start; i < end; i++) {
-          Alg val = alg_scale(Alg{wire(1 + 2 * i), wire(2 + 2 * i)}, gl_mul(xi, ninv));
-          Alg term{gl_sub(sh.a, xi), sh.b};
-          Alg nev = alg_add(alg_mul(ev, term), alg_mul(val, pr));
-          pr = alg_mul(pr, term);
-          ev = nev;
-          xi = gl_mul(xi, om);
+          const u64 wi = ws[i];
+          const Alg val{gl_mulw(wire(1 + 2 * i), wi), gl_mulw(wire(2 + 2 * i), wi)};
+          const Alg term{subx(sh.a, xs[i]), sh.b};
+          ev = alg_mul_addw(ev, term, sh7, alg_mulw(val, pr, gl_mul_small_w(pr.b, 7)));
+          pr = alg_mulw(pr, term, sh7);
         }
+        ev = Alg{gl_canon(ev.a), gl_canon(ev.b)};
         if (c == nint) break;
+        pr = Alg{gl_canon(pr.a), gl_canon(pr.b)};
         Alg iev{wire(w_int + 2 * c), wire(w_int + 2 * c + 1)}, ipr{wire(w_int + 2 * (nint + c)), wire(w_int + 2 * (nint + c) + 1)};
-        Alg d1 = alg_sub(iev, ev), d2 = alg_sub(ipr, pr);
-        emit(d1.a); emit(d1.b); emit(d2.a); emit(d2.b);
+        emit(subx(iev.a, ev.a)); emit(subx(iev.b, ev.b)); emit(subx(ipr.a, pr.a)); emit(subx(ipr.b, pr.b));
         ev = iev; pr = ipr;
         start = 1 + (deg - 1) * (c + 1);
         end = start + deg - 1 < npts ? start + deg - 1 : npts;
       }
-      Alg d3 = alg_sub(Alg{wire(w_val), wire(w_val + 1)}, ev);
-      emit(d3.a); emit(d3.b);
+      emit(subx(wire(w_val), ev.a)); emit(subx(wire(w_val + 1), ev.b));
       break;
     }
     case MP2G_GATE_U32_ARITHMETIC: {
@@ -532,11 +543,11 @@ __device__ __forceinline__ void eval_gate(const mp2g_gate g, WireF wire, ConstF 
       const bool ext = g.kind == MP2G_GATE_REDUCING_EXT;
       const u32 start_accs = 6 + (ext ? 2 * n : n);
       Alg alpha{wire(2), wire(3)}, acc{wire(4), wire(5)};
+      const u64 alpha7 = gl_mul_small_w(alpha.b, 7);
       for (u32 i = 0; i < n; i++) {
         Alg coeff = ext ? Alg{wire(6 + 2 * i), wire(7 + 2 * i)} : Alg{wire(6 + i), 0};
         Alg nxt = i == n - 1 ? Alg{wire(0), wire(1)} : Alg{wire(start_accs + 2 * i), wire(start_accs + 2 * i + 1)};
-        Alg d = alg_sub(alg_add(alg_mul(acc, alpha), coeff), nxt);
-        emit(d.a); emit(d.b);
+        emit_alg(alg_mul_addw(acc, alpha, alpha7, alg_subx(coeff, nxt)));  // acc alpha + coeff - next accumulator, all wires
         acc = nxt;
       }
       break;
@@ -567,12 +578,12 @@ __device__ __forceinline__ void eval_gate(const mp2g_gate g, WireF wire, ConstF 
               const u64 b = wire(b0);
               for (u32 k = 0; k < vs / 2; k++) {
                 u64 x = wire(w0 + 2 + 2 * k), y = wire(w0 + 3 + 2 * k);
-                items[k] = gl_add(x, gl_mul(b, gl_sub(y, x)));
+                items[k] = gl_mul_add(b, gl_sub(y, x), x);
               }
             }
             for (u32 i = 1, len = vs / 2; i < bits; i++, len >>= 1) {
               const u64 b = wire(b0 + i);
-              for (u32 k = 0; k < len / 2; k++) items[k] = gl_add(items[2 * k], gl_mul(b, gl_sub(items[2 * k + 1], items[2 * k])));
+              for (u32 k = 0; k < len / 2; k++) items[k] = gl_mul_add(b, gl_sub(items[2 * k + 1], items[2 * k]), items[2 * k]);
             }
             emit(gl_sub(items[0], wire(w0 + 1)));
           }
