@@ -432,6 +432,51 @@ int mp2g_eval_gate_constraints(mp2g_ctx* ctx, const mp2g_gate* gates, uint32_t n
                                const uint64_t* consts, uint32_t num_constants, const uint64_t* wires, uint32_t wires_w,
                                uint64_t npts, const uint64_t pi_hash[4], uint64_t* out);
 
+/* ---- batched proof verification on the device (csrc/verifier.hip) --------------------------------
+ * Replaces [dep] plonky2 plonk/verifier.rs verify / verify_with_challenges and fri/verifier.rs verify_fri_proof -- the other half
+ * of every proving call: VerifierCircuitData::verify as reached from mp2-common/src/utils.rs:47-59 (verify_proof_tuple),
+ * verifiable-db/src/api.rs:448-452 and ProofWithVK::verify (mp2-common/src/proof.rs) -- for `count` proofs of ONE circuit per call.
+ * Everything runs on the context's stream; one synchronisation at the end reads the statuses. No CPU path.
+ *
+ * A verifier holds the VerifierCircuitData of one circuit: VerifierOnlyCircuitData (constants_sigmas cap [1 << cap_height][4], circuit
+ * digest) and what verify() reads of CommonCircuitData (FRI parameters, num_routed, the quotient degree factor `degree`, the gate
+ * table with its selector groups, the lookup tables). n_public_inputs = MP2G_PI_HASH_GIVEN: part 0 of a proof is the 4-word
+ * public-inputs hash itself instead of the list verify() hashes first. `capacity` = the most proofs one call takes.
+ * Create fails for a gate table the prover would refuse, lookup tables that do not match params->num_lookup_polys, or a table whose
+ * filtered constraints would need more than 32 line points (mp2g_gate_table_line_points).
+ *
+ * STATUS, one word per proof, the first failing check in this order (the codes of the CPU oracle's verifier, so that the two compare
+ * for equality): 20 a word >= p somewhere in the proof (checked first; such a proof takes no further part); 10 + a the PLONK
+ * identity vanishing(zeta) = Z_H(zeta) * sum_i zeta^(n i) t_i(zeta) fails for challenge round a; 1 proof of work; then the FIRST
+ * failing check of the LOWEST failing query round: 2 a Merkle path of an initial oracle, 3 a FRI layer's evaluation does not
+ * continue the previous layer, 4 a FRI layer's Merkle path, 5 the final polynomial. 0 = accept. A rejected proof never affects
+ * another proof of the batch. The functions return 0 when the call ran, whatever the statuses. */
+typedef struct mp2g_verifier mp2g_verifier;
+#define MP2G_PI_HASH_GIVEN 0xFFFFFFFFu
+int mp2g_verifier_create(mp2g_ctx* ctx, const mp2g_fri_params* params, const uint64_t* constants_sigmas_cap, const uint64_t circuit_digest[4],
+                         uint32_t num_routed, uint32_t degree, const mp2g_gate* gates, uint32_t n_gates, uint32_t num_selectors,
+                         const mp2g_lookup* luts, uint32_t n_luts, uint32_t n_public_inputs, uint32_t capacity, mp2g_verifier** out);
+/* words of one proof = the lengths of its four parts, in a parent's input order: public inputs (n_public_inputs, or 4 for the hash),
+ * caps of oracles 1 .. n_oracles - 1, openings (2 * mp2g_fri_n_openings), FRI words (mp2g_fri_proof_words). part_words (may be NULL)
+ * receives the four lengths. */
+size_t mp2g_verifier_proof_words(const mp2g_verifier* v, uint32_t part_words[4]);
+/* Proofs where the prover / chain left them: four device parts per proof, each a base pointer and a stride in words between
+ * consecutive proofs -- mp2g_prover_prove_dev's outputs (d_pi_hash; d_caps + one cap, stride n_oracles caps; d_openings; d_proof) and
+ * mp2g_chain_step_buffers fit as they are. status [count]: host memory. */
+int mp2g_verifier_verify_dev(mp2g_verifier* v, const uint64_t* const d_parts[4], const uint64_t strides[4], uint32_t count, uint32_t* status);
+/* contiguous proofs of mp2g_verifier_proof_words words each, in a parent's input order (what mp2g_forest_proof returns), host memory */
+int mp2g_verifier_verify(mp2g_verifier* v, const uint64_t* words, uint32_t count, uint32_t* status);
+/* The challenges the last call derived, per proof (so that a transcript mismatch is found by comparing a few words and not by
+ * bisecting a rejected proof): betas [2], gammas [2], alphas [2], zeta [2], the 8 lookup challenges of the two rounds (betas,
+ * gammas and 4 more; zero without lookup tables), FRI alpha [2], FRI betas [n_layers][2], the proof-of-work response, the
+ * num_queries query indices (already reduced mod the LDE size). out (may be NULL) [count of the last call][*words_per_proof]. */
+int mp2g_verifier_challenges(mp2g_verifier* v, uint64_t* out, size_t* words_per_proof);
+void mp2g_verifier_free(mp2g_verifier* v);
+/* The number T of base-field points the verifier evaluates the gate constraints at (see DESIGN.md "Verifier"): 1 + the largest
+ * degree of a filtered constraint = 1 + max over gates of degree + (selector group size - 1) + (num_selectors > 1). Pure host
+ * arithmetic: needs no GPU. 0 for an unknown gate kind. */
+uint32_t mp2g_gate_table_line_points(const mp2g_gate* gates, uint32_t n_gates, uint32_t num_selectors);
+
 /* ---- witness generation: the witness tape ------------------------------------------------------------------
  * Replaces [dep] plonky2 iop/generator.rs generate_partial_witness -- the first line of prove() at
  * recursion-framework/src/circuit_builder.rs:308 and universal_verifier_gadget/wrap_circuit.rs:143 -- for circuits whose
@@ -679,6 +724,10 @@ int mp2g_forest_prove_plan(mp2g_forest* f, struct mp2g_update_plan* plan, uint32
 int mp2g_forest_proof(mp2g_forest* f, uint64_t id, uint64_t* words, uint32_t* n_words);
 int mp2g_forest_device_proof(mp2g_forest* f, uint64_t id, const uint64_t** d_words, uint32_t* n_words);
 int mp2g_forest_release(mp2g_forest* f, uint64_t id);
+/* verify published nodes of ONE circuit where they lie in the device pool (v = the verifier of that circuit's last chain step,
+ * created on the forest's first context with n_public_inputs = the node's public inputs): status [n_ids], host. An id that is
+ * unknown, not proved or already released fails the call before anything is verified; no status is written then. */
+int mp2g_forest_verify(mp2g_forest* f, mp2g_verifier* v, const uint64_t* ids, uint32_t n_ids, uint32_t* status);
 uint64_t mp2g_forest_proved(const mp2g_forest* f);
 uint32_t mp2g_forest_free_slots(mp2g_forest* f);
 void mp2g_forest_free(mp2g_forest* f);

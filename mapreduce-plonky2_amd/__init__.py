@@ -577,6 +577,82 @@ class BatchedProver:
         self.h = None
 
 
+PI_HASH_GIVEN = 0xFFFFFFFF
+
+
+def gate_table_line_points(gates, num_selectors):
+    """mp2g_gate_table_line_points: the number of base-field points the verifier evaluates the gate constraints at (1 + the
+    largest filtered constraint degree of the table). Host arithmetic: needs no GPU."""
+    arr = (Gate * max(1, len(gates)))(*[Gate(g.kind, g.p0, g.p1, g.p2, g.selector_index, g.group_start, g.group_end) for g in gates])
+    return int(load().mp2g_gate_table_line_points(arr, len(gates), int(num_selectors)))
+
+
+def verifier_part_words(fp, n_public_inputs):
+    """the lengths of a proof's four parts in a parent's input order: public inputs (4 for PI_HASH_GIVEN: the hash), caps of
+    oracles 1.., openings, FRI words. Host arithmetic (the layout mp2g_verifier_proof_words reports)."""
+    n_pi = 4 if n_public_inputs == PI_HASH_GIVEN else int(n_public_inputs)
+    return [n_pi, (fp.n_oracles - 1) * fp.cap_words, 2 * fp.n_openings, fp.proof_words]
+
+
+class Verifier:
+    """mp2g_verifier: VerifierCircuitData::verify for batches of proofs of one circuit, on the device. Status per proof: 0 accept,
+    10 + a PLONK identity of challenge a, 1 proof of work, 2 initial Merkle path, 3 FRI layer consistency, 4 FRI layer Merkle path,
+    5 final polynomial (2..5: the first failing check of the lowest failing query), 20 a non-canonical word."""
+
+    def __init__(self, ctx, fp, constants_sigmas_cap, circuit_digest, gates, num_selectors, luts=None, num_routed=80, degree=8,
+                 n_public_inputs=PI_HASH_GIVEN, capacity=1):
+        self.ctx, self.fp, self.capacity, self.n_public_inputs = ctx, fp, int(capacity), n_public_inputs
+        cap, dig = _arr(constants_sigmas_cap).ravel(), _arr(circuit_digest)
+        assert cap.size == fp.cap_words and dig.size == 4
+        arr = (Gate * max(1, len(gates)))(*[Gate(g.kind, g.p0, g.p1, g.p2, g.selector_index, g.group_start, g.group_end) for g in gates])
+        larr, keep = lookup_array(luts or [])
+        self.h = ctypes.c_void_p()
+        _ck(load().mp2g_verifier_create(ctx.h, ctypes.byref(fp), _p(cap), _p(dig), int(num_routed), int(degree), arr, len(gates),
+                                        int(num_selectors), larr if luts else None, len(luts or []), ctypes.c_uint32(n_public_inputs),
+                                        self.capacity, ctypes.byref(self.h)))
+        ctx._adopt(self)
+        parts = (ctypes.c_uint32 * 4)()
+        f = load().mp2g_verifier_proof_words
+        f.restype = ctypes.c_size_t
+        self.proof_words = int(f(self.h, parts))
+        self.part_words = [int(x) for x in parts]
+
+    def verify_dev(self, d_parts, strides, count):
+        """d_parts: four device addresses (ints or DeviceBuffers), strides: words between consecutive proofs of each part"""
+        ptrs = (ctypes.c_void_p * 4)(*[(d.ptr.value if isinstance(d, DeviceBuffer) else (int(d) if d else None)) for d in d_parts])
+        st = (ctypes.c_uint64 * 4)(*[int(x) for x in strides])
+        status = np.full(int(count), 0xFFFFFFFF, dtype=np.uint32)
+        _ck(load().mp2g_verifier_verify_dev(self.h, ptrs, st, int(count), _p(status)))
+        return status
+
+    def verify(self, words):
+        """words [count][proof_words] (host): contiguous proofs in a parent's input order"""
+        w = _arr(words).reshape(-1, self.proof_words)
+        status = np.full(w.shape[0], 0xFFFFFFFF, dtype=np.uint32)
+        _ck(load().mp2g_verifier_verify(self.h, _p(w), w.shape[0], _p(status)))
+        return status
+
+    def challenges(self, count):
+        """[count][words]: betas[2], gammas[2], alphas[2], zeta[2], the 8 lookup challenges, FRI alpha[2], FRI betas[n_layers][2],
+        the PoW response, the query indices -- of the last verify call"""
+        n = ctypes.c_size_t()
+        _ck(load().mp2g_verifier_challenges(self.h, None, ctypes.byref(n)))
+        out = np.zeros((int(count), n.value), dtype=np.uint64)
+        _ck(load().mp2g_verifier_challenges(self.h, _p(out), ctypes.byref(n)))
+        return out
+
+    def free(self):
+        if self.h and self.ctx.h:
+            load().mp2g_verifier_free(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
 class WitnessProgram:
     """mp2g_witness_program: the witness generator of one circuit built by recursion.Builder (its recorded tape),
     replayed on the host for batches of input vectors. No GPU involved."""
@@ -745,6 +821,14 @@ class Forest:
         ptr, n = ctypes.c_void_p(), ctypes.c_uint32()
         _ck(load().mp2g_forest_device_proof(self.h, ctypes.c_uint64(int(node_id)), ctypes.byref(ptr), ctypes.byref(n)))
         return int(ptr.value), int(n.value)
+
+    def verify(self, ids, verifier):
+        """mp2g_forest_verify: the published nodes `ids` of ONE circuit verified where they lie in the device pool; `verifier` = the
+        Verifier (or framework.CircuitVerifier) of that circuit's last chain step. Raises when an id is unknown or released."""
+        ids = _arr(ids)
+        status = np.full(ids.size, 0xFFFFFFFF, dtype=np.uint32)
+        _ck(load().mp2g_forest_verify(self.h, getattr(verifier, "v", verifier).h, _p(ids), int(ids.size), _p(status)))
+        return status
 
     def release(self, node_id):
         _ck(load().mp2g_forest_release(self.h, ctypes.c_uint64(int(node_id))))

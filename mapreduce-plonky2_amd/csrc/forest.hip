@@ -27,6 +27,7 @@
 #include <unordered_map>
 #include <vector>
 #include "chain.h"
+#include "verifier.h"
 
 using namespace mp2g;
 // the error text of a worker thread travels to the caller's thread (mp2g_last_error is thread local)
@@ -596,6 +597,28 @@ int mp2g_forest_release(mp2g_forest* f, uint64_t id) {
   Node& nd = f->nodes[it->second];
   if (nd.slot >= 0) { f->free_slots.push_back(nd.slot); nd.slot = -1; }
   return 0;
+}
+
+int mp2g_forest_verify(mp2g_forest* f, mp2g_verifier* v, const uint64_t* ids, uint32_t n_ids, uint32_t* status) {
+  NEED(f && v && ids && status && n_ids >= 1, "forest / verifier / ids / status");
+  NEED(verifier_ctx(v) && verifier_ctx(v)->device == f->ctxs[0]->device, "the verifier must live on the device of the forest's pool");
+  NEED(n_ids <= verifier_capacity(v), "more ids than the verifier's capacity");
+  const size_t words = mp2g_verifier_proof_words(v, nullptr);
+  std::vector<const u64*> srcs(n_ids);
+  {
+    std::lock_guard<std::mutex> g(f->mu);
+    for (uint32_t i = 0; i < n_ids; i++) {
+      auto it = f->index.find(ids[i]);
+      if (it == f->index.end()) return fail("forest: unknown node %llu", (unsigned long long)ids[i]);
+      const Node& nd = f->nodes[it->second];
+      if (!nd.proved || nd.slot < 0) return fail("forest: node %llu is not proved (or its proof was released)", (unsigned long long)ids[i]);
+      if (nd.proof_words != words) return fail("forest: node %llu is not a proof of the verifier's circuit (%u words, the verifier takes %zu)",
+                                               (unsigned long long)ids[i], nd.proof_words, words);
+      srcs[i] = f->pool.p + (size_t)nd.slot * f->slot_words;
+    }
+  }
+  CK(hipSetDevice(f->ctxs[0]->device));
+  return verifier_verify_gathered(v, srcs.data(), n_ids, status);
 }
 
 uint64_t mp2g_forest_proved(const mp2g_forest* f) { return f ? f->proved.load() : 0; }

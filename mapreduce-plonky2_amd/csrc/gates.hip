@@ -797,6 +797,34 @@ __global__ void __launch_bounds__(256) gate_constraints_points_kernel(GateTable 
   }
 }
 
+// The same for B sets of npts points, one set per proof (the verifier's line evaluation, verifier.hip): consts / wires / out of
+// proof b start c_bstride / w_bstride / max_j * npts words after those of proof b - 1, its public-inputs hash is pih[4 b .. 4 b + 4)
+__global__ void __launch_bounds__(256) gate_constraints_points_batch_kernel(GateTable t, u32 B, const u64* __restrict__ consts, u64 c_bstride,
+                                                                            const u64* __restrict__ wires, u64 w_bstride, u32 npts,
+                                                                            u32 max_j, const u64* __restrict__ pih, u64* __restrict__ out) {
+  const u32 idx = blockIdx.x * 256 + threadIdx.x;
+  if (idx >= B * npts) return;
+  const u32 b = idx / npts, p = idx % npts;
+  const u64* cb = consts + b * c_bstride;
+  const u64* wb = wires + b * w_bstride;
+  u64* ob = out + (u64)b * max_j * npts;
+  auto wire = [&](u32 j) { return wb[(u64)j * npts + p]; };
+  auto call = [&](u32 j) { return cb[(u64)j * npts + p]; };
+  const u32 ns = t.num_selectors + t.num_lookup_selectors;
+  auto cst = [&](u32 j) { return cb[(u64)(ns + j) * npts + p]; };
+  for (u32 j = 0; j < max_j; j++) ob[(u64)j * npts + p] = 0;
+  for (u32 gi = 0; gi < t.n_gates; gi++) {
+    if (t.g[gi].kind == MP2G_GATE_NOOP) continue;
+    const u64 f = gate_filter(t, gi, call);
+    u32 j = 0;
+    eval_gate<false>(t.g[gi], wire, cst, pih + 4 * b, [&](u64 v) {
+      u64* o = ob + (u64)j * npts + p;
+      *o = gl_add(*o, gl_mul(f, v));
+      j++;
+    });
+  }
+}
+
 // Witness check on the subgroup H (what makes plonky2's prove() panic on an unsatisfied witness): on a row
 // of H only the row's own gate has a non-zero filter, so a violated constraint cannot cancel against another
 // gate's. flags[b] |= 2 when any gate constraint of proof b is non-zero somewhere.
@@ -911,6 +939,13 @@ hipError_t gate_constraints_points(hipStream_t s, const GateTable& t, const u64*
   if (!npts) return hipSuccess;
   hipLaunchKernelGGL(gate_constraints_points_kernel, dim3((u32)((npts + 255) / 256)), dim3(256), 0, s, t, consts, wires, npts, max_j,
                      pi_hash, out);
+  return hipGetLastError();
+}
+hipError_t gate_constraints_points_batch(hipStream_t s, u32 B, const GateTable& t, const u64* consts, u64 c_bstride, const u64* wires,
+                                         u64 w_bstride, u32 npts, u32 max_j, const u64* pi_hash, u64* out) {
+  if (!npts || !B) return hipSuccess;
+  hipLaunchKernelGGL(gate_constraints_points_batch_kernel, dim3((B * npts + 255) / 256), dim3(256), 0, s, t, B, consts, c_bstride, wires,
+                     w_bstride, npts, max_j, pi_hash, out);
   return hipGetLastError();
 }
 }  // namespace mp2g

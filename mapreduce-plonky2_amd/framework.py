@@ -16,7 +16,8 @@ children's proofs; recursion.py builds the real verifier circuit for small trees
 """
 import numpy as np
 
-from . import (BatchedProver, CircuitSet, Gate, POSEIDON2, PolynomialBatch, circuit_digest, standard_recursion_params)
+from . import (BatchedProver, CircuitSet, Gate, PI_HASH_GIVEN, POSEIDON2, PolynomialBatch, Verifier, circuit_digest, deserialize_proof_with_vk,
+               standard_recursion_params)
 from . import circuits as C
 
 NUM_ROUTED = C.NUM_ROUTED
@@ -70,8 +71,78 @@ class CircuitProver:
     def results(self):
         return self.pr.results()
 
+    def verifier(self, capacity=None, n_public_inputs=PI_HASH_GIVEN):
+        """the CircuitVerifier of this prover's circuit, sharing its verifier data (constants_sigmas cap, circuit digest)"""
+        return CircuitVerifier(self.ctx, self.ckt, capacity or self.batch, fp=self.fp, constants_sigmas_cap=self.constants_sigmas_cap,
+                               circuit_digest=self.circuit_digest, n_public_inputs=n_public_inputs)
+
     def free(self):
         self.pr.free()
+
+
+class CircuitVerifier:
+    """VerifierCircuitData::verify for up to `capacity` proofs of one circuit per call, on the device (mp2g_verifier). Built from the
+    fields CircuitProver uses; the verifier data is computed from the circuit's preprocessed polynomials unless given.
+    n_public_inputs = PI_HASH_GIVEN: a proof's first part is its 4-word public-inputs hash (the synthetic circuits of circuits.py
+    have a hash and no list); otherwise the list, hashed on the device as verify() does first."""
+
+    def __init__(self, ctx, ckt, capacity, variant=POSEIDON2, fp=None, constants_sigmas_cap=None, circuit_digest=None,
+                 n_public_inputs=PI_HASH_GIVEN, **fri_kw):
+        self.ctx, self.ckt, self.capacity = ctx, ckt, capacity
+        self.fp = fp if fp is not None else circuit_fri_params(ckt, variant, **fri_kw)
+        variant = self.fp.variant
+        if constants_sigmas_cap is None:
+            pre = PolynomialBatch.from_values(ctx, ckt.pre, self.fp.rate_bits, self.fp.cap_height, variant)
+            constants_sigmas_cap = pre.cap
+            pre.free()
+        if circuit_digest is None:
+            circuit_digest = globals()["circuit_digest"](ctx, constants_sigmas_cap, ckt.log_n, variant, getattr(ckt, "domain_separator", ()))
+        self.constants_sigmas_cap, self.circuit_digest = np.asarray(constants_sigmas_cap, dtype=np.uint64), np.asarray(circuit_digest, dtype=np.uint64)
+        self.n_public_inputs = n_public_inputs
+        self.v = Verifier(ctx, self.fp, self.constants_sigmas_cap, self.circuit_digest, ckt.gates, ckt.num_selectors,
+                          luts=getattr(ckt, "luts", None) or None, num_routed=NUM_ROUTED, degree=8, n_public_inputs=n_public_inputs,
+                          capacity=capacity)
+        self.num_constants = int(ckt.pre.shape[0]) - NUM_ROUTED
+
+    def pack(self, caps, openings, proofs, public_inputs_or_hash):
+        """[count][proof_words]: the proofs in a parent's input order. caps [count][n_oracles][cap words] as the prover returns them
+        (oracle 0's cap is the verifier's own and is dropped)"""
+        fp = self.fp
+        caps = np.asarray(caps, dtype=np.uint64).reshape(-1, fp.n_oracles, fp.cap_words)
+        B = caps.shape[0]
+        return np.concatenate([np.asarray(public_inputs_or_hash, dtype=np.uint64).reshape(B, -1), caps[:, 1:].reshape(B, -1),
+                               np.asarray(openings, dtype=np.uint64).reshape(B, -1), np.asarray(proofs, dtype=np.uint64).reshape(B, -1)], axis=1)
+
+    def verify(self, caps, openings, proofs, public_inputs_or_hash):
+        """status array (see Verifier) of `count` proofs given as the prover's host outputs"""
+        return self.v.verify(self.pack(caps, openings, proofs, public_inputs_or_hash))
+
+    def verify_words(self, words):
+        return self.v.verify(words)
+
+    def verify_prover_outputs(self, cp, count, d_pi_hash):
+        """the first `count` proofs of CircuitProver cp's last prove(), verified in the prover's device buffers (no download);
+        d_pi_hash: the [batch][4] device buffer prove() was given. Needs n_public_inputs = PI_HASH_GIVEN."""
+        fp, pr = self.fp, cp.pr
+        assert self.n_public_inputs == PI_HASH_GIVEN
+        return self.v.verify_dev([d_pi_hash, pr.d_caps.ptr.value + fp.cap_words * 8, pr.d_openings, pr.d_proof],
+                                 [4, fp.n_oracles * fp.cap_words, 2 * fp.n_openings, fp.proof_words], count)
+
+    def verify_with_vk(self, blob, n_public_inputs):
+        """ProofWithVK::verify (mp2-common/src/proof.rs): deserialize `blob` (ProofWithVK bytes), refuse it with status 30 -- decided
+        here, not on the device -- when its verifier key (constants_sigmas cap, circuit digest) is not this verifier's own, then
+        verify the proof. Returns the status."""
+        (caps, openings, fri, pis), vk_cap, dig = deserialize_proof_with_vk(self.fp, self.num_constants, blob, n_public_inputs)
+        if not (np.array_equal(vk_cap.ravel(), self.constants_sigmas_cap.ravel()) and np.array_equal(dig, self.circuit_digest)):
+            return 30
+        assert self.n_public_inputs == n_public_inputs, "the verifier was created for another number of public inputs"
+        return int(self.verify(caps[None], openings[None], fri[None], pis[None])[0])
+
+    def challenges(self, count):
+        return self.v.challenges(count)
+
+    def free(self):
+        self.v.free()
 
 
 def tile_witness(ctx, ckt, batch, seed, rand_row=True):
@@ -229,6 +300,7 @@ class GpuProver:
         # (mp2g_witness_program_run_rows) and an upload per step -- kept for A/B runs and as the second opinion of the parity tests
         self.device_witness = device_witness
         self.provers = {}
+        self.verifiers = {}
         self.chains = {}
         self.pinned = {}  # data address of a pinned wire matrix -> its host pointer
 
@@ -368,6 +440,20 @@ class GpuProver:
         """wires [B][135][n] and pi_hash [B][4] (host) of B witnesses of one circuit -> [(caps, openings, proof)]"""
         return self.prove_batch_finish(self.prove_batch_launch(ckt, wires, pi_hash))
 
+    def verify_batch(self, ckt, proofs, pi_hashes=None):
+        """verify [(caps, openings, proof)] of one circuit (what prove_batch returns) on the device; pi_hashes [B][4] (default: the
+        circuit's own public-inputs hash for every proof). Returns the status array (0 = accept)."""
+        cp = self._prover(ckt)
+        B = len(proofs)
+        key = (ckt.log_n, self.circuit_key(ckt))
+        cv = self.verifiers.get(key)
+        if cv is None or cv.capacity < B:
+            if cv is not None:
+                cv.free()
+            cv = self.verifiers[key] = cp.verifier(capacity=max(B, self.capacity or 1))
+        ph = np.tile(np.asarray(ckt.pi_hash, dtype=np.uint64), (B, 1)) if pi_hashes is None else np.asarray(pi_hashes, dtype=np.uint64)
+        return cv.verify(np.stack([p[0] for p in proofs]), np.stack([p[1] for p in proofs]), np.stack([p[2] for p in proofs]), ph)
+
     def two_to_one(self, left, right):
         """Hasher::two_to_one = permute([l || r || 0000])[0..4] = hash_no_pad of the 8 limbs (one absorb)"""
         return [int(x) for x in self.ctx.hash_no_pad(list(left) + list(right), self.variant)]
@@ -378,6 +464,9 @@ class GpuProver:
             for cp in ch.cps:
                 cp.free()
         self.chains = {}
+        for cv in self.verifiers.values():
+            cv.free()
+        self.verifiers = {}
         for cp in self.provers.values():
             cp.free()
         self.provers = {}

@@ -64,7 +64,9 @@ class ProofStore:
     temporary name and renamed, so that a key holds a whole proof WITH its own header or nothing: a call that is cut off, or two ranks
     storing under one key, cannot leave the note of one proof beside the bytes of another. The header's clear-text key is compared with
     the key asked for on every read (two keys whose 64-bit hashes collide cannot alias). The note is never read back for the proof
-    itself: a loaded proof is checked against its verifier key and public inputs. Stores written before round 6 (the proof bytes alone
+    itself. get_proof_exact returns the bytes unchecked (a caller may compare the blob's verifier key and public inputs with what it
+    expects: a comparison of bytes, not a verification); get_proof_verified hands them to a verifier first -- on the device,
+    framework.CircuitVerifier.verify_with_vk -- and refuses a proof that does not verify. Stores written before round 6 (the proof bytes alone
     in the .bin, the header in a .json beside it: profiles/r05/table_2p20_store) are still read."""
 
     def __init__(self, path):
@@ -126,6 +128,17 @@ class ProofStore:
     def get_proof_exact(self, key):
         """get_proof_exact(key): the bytes, or KeyError naming the key (proof_storage.rs:262-272 `proof with key .. not found`)"""
         return self._entry(key)[1]
+
+    def get_proof_verified(self, key, check):
+        """get_proof_exact(key) followed by a verification: check(bytes) -> status (0 = the proof verifies; the device verifier's
+        codes otherwise, e.g. lambda blob: verifier.verify_with_vk(blob, n_public_inputs)). Returns the bytes; raises ValueError
+        naming the key and the status when the proof is rejected, KeyError as get_proof_exact when there is none. A damaged stored
+        proof is then found where it is read, not as a witness error of its parent."""
+        proof = self.get_proof_exact(key)
+        status = int(check(proof))
+        if status != 0:
+            raise ValueError(f"proof with key {key!r} in {self.path} does not verify: status {status}")
+        return proof
 
     def note(self, key):
         head, _ = self._entry(key)

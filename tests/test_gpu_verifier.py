@@ -1,0 +1,402 @@
+"""Batched proof verification on the device (csrc/verifier.hip: mp2g_verifier_*, mp2g_forest_verify) against the CPU oracle's
+verifier (oracle/fri.c orc_verify_circuit): the device must give the oracle's status code for the same words -- accept and reject,
+code for code. The code under test is never compared with itself."""
+import ctypes
+import importlib
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import circuits as C
+import oracle as O
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+FW = importlib.import_module("mapreduce-plonky2_amd.framework")
+P = O.P
+
+
+def prove_batch(ctx, ckt, batch, variant=0, seed=0x5EED, rand_row=True, wires=None, pi_hash=None, **kw):
+    """`batch` device proofs of one circuit: (CircuitProver, d_pi_hash, pi hashes, caps, openings, proofs)"""
+    cp = FW.CircuitProver(ctx, ckt, batch, variant, bind_public_inputs=pi_hash is not None, **kw)
+    if wires is None:
+        d_w = FW.tile_witness(ctx, ckt, batch, seed, rand_row=rand_row)
+    else:
+        d_w = ctx.to_device(np.ascontiguousarray(wires, dtype=np.uint64))
+    ph = np.tile(np.asarray(ckt.pi_hash, dtype=np.uint64), (batch, 1)) if pi_hash is None else np.asarray(pi_hash, dtype=np.uint64).reshape(batch, 4)
+    d_ph = ctx.to_device(ph)
+    cp.prove(d_w, d_ph)
+    caps, openings, proofs = cp.results()
+    d_w.free()
+    return cp, d_ph, ph, caps, openings, proofs
+
+
+def oracle_status(ckt, ofp, digest, ph, caps, openings, proof):
+    return int(C.verify(ckt, ofp, digest, ph, caps, openings, proof))
+
+
+def bump(a, idx):
+    """v -> v + 1 mod p at flat index idx of array a (in place)"""
+    flat = a.reshape(-1)
+    flat[idx] = np.uint64((int(flat[idx]) + 1) % P)
+
+
+_built = {}
+
+
+def circuit(log_n, kinds_name, seed=3):
+    key = (log_n, kinds_name, seed)
+    if key not in _built:
+        if kinds_name == "LOOKUP":
+            _built[key] = C.build(log_n, C.ALL_KINDS + C.LOOKUP_KINDS, seed, luts=[(t, 100) for t in C.bits_lookup_tables()])
+        else:
+            _built[key] = C.build(log_n, getattr(C, kinds_name), seed)
+    return _built[key]
+
+
+ACCEPT_CASES = [(5, "ALL_KINDS", 0), (5, "ALL_KINDS", 1), (6, "ALL_KINDS", 0), (6, "ALL_KINDS", 1), (12, "ALL_KINDS", 0), (12, "ALL_KINDS", 1),
+                (7, "LOOKUP", 0), (12, "VERIFIER_KINDS", 0), (13, "LEAF_KINDS", 0)]
+
+
+@pytest.mark.parametrize("log_n,kinds,variant", ACCEPT_CASES)
+def test_accepts_device_proofs(ctx, mp2, log_n, kinds, variant):
+    """16 proofs with different transcripts per shape (0, 1 and 2 FRI layers; 24 and 26 gate kinds; both hashers): the device
+    accepts every one, in the prover's device buffers and as host words, and so does the oracle"""
+    ckt = circuit(log_n, kinds)
+    B = 16
+    cp, d_ph, ph, caps, openings, proofs = prove_batch(ctx, ckt, B, variant)
+    assert cp.fp.n_layers == {5: 0, 6: 1, 7: 1, 12: 2, 13: 2}[log_n]  # ConstantArityBits(4, 5): the zero-layer case included
+    cv = cp.verifier()
+    st_dev = cv.verify_prover_outputs(cp, B, d_ph)
+    st_host = cv.verify(caps, openings, proofs, ph)
+    ofp = C.oracle_params(ckt, variant)
+    want = [oracle_status(ckt, ofp, cp.circuit_digest, ph[b], caps[b], openings[b], proofs[b]) for b in range(B)]
+    print("accept", log_n, kinds, variant, st_dev.tolist(), st_host.tolist(), want)
+    assert len({proofs[b].tobytes() for b in range(B)}) == B, "the transcripts of the batch must differ"
+    assert want == [0] * B
+    assert st_dev.tolist() == [0] * B and st_host.tolist() == [0] * B
+    cv.free()
+    cp.free()
+
+
+def test_accepts_an_oracle_proof_and_reports_its_challenges(ctx, mp2):
+    """the circuit with lookups (26 gate kinds, 7 lookup polynomials) proved by the ORACLE's prover: the device accepts it, and
+    mp2g_verifier_challenges gives the oracle prover's betas, gammas, alphas, zeta and the 8 lookup challenges; the device prover's
+    proof of the same witness is the same proof, so the same holds for it"""
+    ckt = circuit(7, "LOOKUP")
+    cp, d_ph, ph, caps, openings, proofs = prove_batch(ctx, ckt, 1, rand_row=False)
+    ofp = C.oracle_params(ckt)
+    oc, oo, op_, chal = C.prove(ckt, ofp, cp.circuit_digest)
+    assert np.array_equal(oc, caps[0]) and np.array_equal(oo, openings[0]) and np.array_equal(op_, proofs[0]), "device proof != oracle proof"
+    cv = cp.verifier()
+    st = cv.verify(oc[None], oo[None], op_[None], ph)
+    got = cv.challenges(1)[0]
+    print("challenges", st.tolist(), got[:16].tolist(), chal.tolist())
+    assert np.array_equal(got[:16], chal)
+    assert st.tolist() == [0] and oracle_status(ckt, ofp, cp.circuit_digest, ph[0], oc, oo, op_) == 0
+    N = 1 << (ckt.log_n + 3)
+    assert got.size == 19 + 2 * ofp.n_layers + ofp.num_queries and all(int(x) < N for x in got[-ofp.num_queries:])
+    cv.free()
+    cp.free()
+
+
+def test_rejects_code_for_code(ctx, mp2):
+    """A catalogue of single-word mutations v -> v + 1 mod p of one proof of the lookup circuit at the standard parameters (pow 16,
+    28 queries): every 5th word of each cap (the verifier's own constants_sigmas cap included), every opening (alternating limb),
+    the public-inputs hash, the circuit digest, every 11th FRI word and the last three (final polynomial tail, PoW witness). The
+    device status equals the oracle's for every case, and the oracle rejects every case outside cap 0 (an entry of the
+    constants_sigmas cap that no query lands on is bound only through the circuit digest, which the verifier is given: the oracle
+    and plonky2 accept such a mutation, so must the device).
+    Code 5 (final polynomial) cannot be reached by mutating a proof: the final polynomial is observed before the PoW response and
+    the query indices are drawn, so changing it changes which queries are made -- it needs a dishonest prover and is not in the
+    catalogue; the accept tests run that evaluation on all 28 queries of every proof."""
+    ckt = circuit(7, "LOOKUP")
+    cp, d_ph, ph, caps, openings, proofs = prove_batch(ctx, ckt, 1, rand_row=False)
+    ofp, dig = C.oracle_params(ckt), cp.circuit_digest
+    caps, openings, proof, ph = caps[0], openings[0], proofs[0], ph[0]
+    assert ofp.pow_bits == 16 and ofp.num_queries == 28
+    capw = cp.fp.cap_words
+    fri_idx = sorted(set(range(0, proof.size, 11)) | {proof.size - 3, proof.size - 2, proof.size - 1})
+    tally = {}
+
+    def run(part, indices, mutate):
+        """one device batch: case i = the proof with mutate(arrays, index) applied"""
+        n = len(indices)
+        cs, os_, ps, hs = np.tile(caps, (n, 1, 1)), np.tile(openings, (n, 1, 1)), np.tile(proof, (n, 1)), np.tile(ph, (n, 1))
+        for i, idx in enumerate(indices):
+            mutate(cs[i], os_[i], ps[i], hs[i], idx)
+        cv = cp.verifier(capacity=n)
+        got = cv.verify(cs, os_, ps, hs).tolist()
+        cv.free()
+        want = [oracle_status(ckt, ofp, dig, hs[i], cs[i], os_[i], ps[i]) for i in range(n)]
+        for w in want:
+            tally.setdefault(part, {}).setdefault(w, 0)
+            tally[part][w] += 1
+        print("reject", part, n, "cases; oracle tally", tally[part])
+        bad = [(indices[i], got[i], want[i]) for i in range(n) if got[i] != want[i]]
+        assert not bad, f"{part}: (index, device, oracle) {bad[:10]}"
+        assert all(w != 0 for w in want), f"{part}: the oracle accepts a mutated proof"
+
+    run("caps 1..3", [o * capw + j for o in range(1, 4) for j in range(0, capw, 5)], lambda c, o, p, h, i: bump(c, i))
+    run("openings", list(range(openings.shape[0])), lambda c, o, p, h, i: bump(o, 2 * i + (i & 1)))
+    run("pi hash", [0], lambda c, o, p, h, i: bump(h, i))
+    run("fri", fri_idx, lambda c, o, p, h, i: bump(p, i))
+    # cap 0 and the circuit digest belong to the verifier: one verifier of capacity 1 per case
+    cap0_tally = {}
+    for j in list(range(0, capw, 5)) + ["digest"]:
+        cap0, d2, c2 = cp.constants_sigmas_cap.copy().reshape(-1), dig.copy(), caps.copy()
+        if j == "digest":
+            bump(d2, 0)
+        else:
+            bump(cap0, j)
+            c2[0] = cap0
+        cv = FW.CircuitVerifier(ctx, ckt, 1, fp=cp.fp, constants_sigmas_cap=cap0, circuit_digest=d2)
+        got = int(cv.verify(caps[None], openings[None], proof[None], ph[None])[0])
+        cv.free()
+        want = oracle_status(ckt, ofp, d2, ph, c2, openings, proof)
+        cap0_tally[want] = cap0_tally.get(want, 0) + 1
+        assert got == want, f"cap 0 / digest case {j}: device {got}, oracle {want}"
+        if j == "digest":
+            assert want != 0
+    print("reject cap 0 + digest: oracle tally", cap0_tally)
+    cp.free()
+
+
+def test_semantic_rejects(ctx, mp2):
+    """a proof under another circuit's verifier (same shape, other seed), under the other hasher, with one public input changed
+    (the list form, hashed on the device), and a proof of a witness with one gate cell changed: rejected with the oracle's code"""
+    a, b = circuit(5, "ALL_KINDS", 3), circuit(5, "ALL_KINDS", 4)
+    assert a.pre.shape == b.pre.shape
+    cp, d_ph, ph, caps, openings, proofs = prove_batch(ctx, a, 2)
+    # (1) another circuit's verifier
+    cvb = FW.CircuitVerifier(ctx, b, 2)
+    got = cvb.verify(caps, openings, proofs, ph).tolist()
+    cb = caps.copy()
+    cb[:, 0] = cvb.constants_sigmas_cap.reshape(-1)
+    want = [oracle_status(b, C.oracle_params(b), cvb.circuit_digest, ph[i], cb[i], openings[i], proofs[i]) for i in range(2)]
+    print("other circuit", got, want)
+    assert got == want and all(w != 0 for w in want)
+    cvb.free()
+    # (2) the other hash variant
+    cv1 = FW.CircuitVerifier(ctx, a, 2, variant=1)
+    got = cv1.verify(caps, openings, proofs, ph).tolist()
+    c1 = caps.copy()
+    c1[:, 0] = cv1.constants_sigmas_cap.reshape(-1)
+    want = [oracle_status(a, C.oracle_params(a, 1), cv1.circuit_digest, ph[i], c1[i], openings[i], proofs[i]) for i in range(2)]
+    print("other hasher", got, want)
+    assert got == want and all(w != 0 for w in want)
+    cv1.free()
+    cp.free()
+    # (3) public inputs as a list, hashed on the device; one of them changed
+    pis = O.rand_field((2, 11), 91)
+    hashes = np.stack([O.hash_n_to_m_no_pad(p, 4) for p in pis])
+    cp, d_ph, ph, caps, openings, proofs = prove_batch(ctx, a, 2, pi_hash=hashes)
+    cv = cp.verifier(n_public_inputs=11)
+    ofp = C.oracle_params(a)
+    assert cv.verify(caps, openings, proofs, pis).tolist() == [0, 0]
+    assert [oracle_status(a, ofp, cp.circuit_digest, hashes[i], caps[i], openings[i], proofs[i]) for i in range(2)] == [0, 0]
+    bad = pis.copy()
+    bump(bad[1], 10)
+    got = cv.verify(caps, openings, proofs, bad).tolist()
+    want = [0, oracle_status(a, ofp, cp.circuit_digest, O.hash_n_to_m_no_pad(bad[1], 4), caps[1], openings[1], proofs[1])]
+    print("public input", got, want)
+    assert got == want and want[1] != 0
+    cv.free()
+    cp.free()
+    # (4) a witness with one gate cell changed (an unrouted cell of a Poseidon2 row: only the gate constraints see it)
+    w = a.wires.copy()
+    row = a.instances.index(next(i for i, g in enumerate(a.gates) if g.kind == C.POSEIDON2))
+    w[100, row] = np.uint64((int(w[100, row]) + 1) % P)
+    cp, d_ph, ph, caps, openings, proofs = prove_batch(ctx, a, 1, wires=w[None])
+    cv = cp.verifier()
+    got = cv.verify(caps, openings, proofs, ph).tolist()
+    want = [oracle_status(a, ofp, cp.circuit_digest, ph[0], caps[0], openings[0], proofs[0])]
+    print("bad witness", got, want)
+    assert got == want and want[0] >= 10
+    cv.free()
+    cp.free()
+
+
+def test_isolation_and_batch_sizes(ctx, mp2):
+    """64 valid proofs with mutated ones at 0, 17 and 63: exactly those are rejected (with the oracle's codes), and the same proofs
+    verified with count 1, 3 and 64 get the same statuses"""
+    ckt = circuit(5, "ALL_KINDS")
+    B = 64
+    cp, d_ph, ph, caps, openings, proofs = prove_batch(ctx, ckt, B)
+    bump(openings[0], 7)
+    bump(proofs[17], 200)
+    bump(proofs[63], proofs.shape[1] - 1)
+    ofp = C.oracle_params(ckt)
+    want = [oracle_status(ckt, ofp, cp.circuit_digest, ph[b], caps[b], openings[b], proofs[b]) for b in range(B)]
+    cv = cp.verifier()
+    words = cv.pack(caps, openings, proofs, ph)
+    got = cv.verify_words(words).tolist()
+    print("isolation", got, want)
+    assert got == want
+    assert [b for b in range(B) if got[b]] == [0, 17, 63]
+    assert cv.verify_words(words[:1]).tolist() == got[:1] and cv.verify_words(words[:3]).tolist() == got[:3]
+    assert cv.verify_words(words[16:19]).tolist() == got[16:19]
+    small = cp.verifier(capacity=8)
+    with pytest.raises(mp2.Mp2gError):
+        small.verify_words(words[:9])  # count > capacity
+    small.free()
+    cv.free()
+    cp.free()
+
+
+def test_non_canonical_words(ctx, mp2):
+    """a word >= p (p, p + 5, 2^64 - 1) in each of the four parts of a proof: status 20 for that proof, 0 for the rest of the batch"""
+    ckt = circuit(5, "ALL_KINDS")
+    B = 16
+    cp, d_ph, ph, caps, openings, proofs = prove_batch(ctx, ckt, B)
+    cv = cp.verifier()
+    words = cv.pack(caps, openings, proofs, ph)
+    offs = np.cumsum([0] + cv.v.part_words)
+    assert offs[-1] == words.shape[1] == cv.v.proof_words
+    bad = {}
+    for k in range(4):
+        for j, val in enumerate((P, P + 5, (1 << 64) - 1)):
+            b = 3 * k + j
+            words[b, offs[k] + (5 * b + 1) % cv.v.part_words[k]] = np.uint64(val)
+            bad[b] = 20
+    got = cv.verify_words(words).tolist()
+    print("canonicity", got)
+    assert got == [bad.get(b, 0) for b in range(B)]
+    cv.free()
+    cp.free()
+
+
+def test_proof_with_vk_bytes(ctx, mp2):
+    """ProofWithVK::verify on serialized bytes: 0 for the prover's own blob, 30 for a blob with a foreign verifier key, non-zero for
+    a blob with one proof byte changed to another canonical value; ProofStore.get_proof_verified raises for the damaged blob"""
+    PS = importlib.import_module("mapreduce-plonky2_amd.proofstore")
+    ckt = circuit(5, "ALL_KINDS")
+    pis = O.rand_field(7, 17)
+    cp, d_ph, ph, caps, openings, proofs = prove_batch(ctx, ckt, 1, pi_hash=O.hash_n_to_m_no_pad(pis, 4))
+    numc = ckt.num_constants
+    body = mp2.serialize_proof(cp.fp, numc, caps[0], openings[0], proofs[0], pis)
+    blob = mp2.serialize_proof_with_vk(body, cp.constants_sigmas_cap, cp.circuit_digest)
+    cv = cp.verifier(n_public_inputs=7)
+    assert cv.verify_with_vk(blob, 7) == 0
+    other = cp.circuit_digest.copy()
+    bump(other, 2)
+    assert cv.verify_with_vk(mp2.serialize_proof_with_vk(body, cp.constants_sigmas_cap, other), 7) == 30
+    # flip the low byte of one opening limb inside the proof body (stays canonical: only the low byte changes)
+    o2 = openings[0].copy()
+    o2.reshape(-1)[33] ^= np.uint64(1)
+    assert int(o2.reshape(-1)[33]) < P
+    damaged = mp2.serialize_proof_with_vk(mp2.serialize_proof(cp.fp, numc, caps[0], o2, proofs[0], pis), cp.constants_sigmas_cap, cp.circuit_digest)
+    assert sum(x != y for x, y in zip(damaged, blob)) == 1
+    st = cv.verify_with_vk(damaged, 7)
+    want = oracle_status(ckt, C.oracle_params(ckt), cp.circuit_digest, ph[0], caps[0], o2, proofs[0])
+    print("with vk", st, want)
+    assert st == want != 0
+    import tempfile
+    with tempfile.TemporaryDirectory() as d:
+        store = PS.ProofStore(d)
+        k1, k2 = PS.ProofKey.index("t", 1), PS.ProofKey.index("t", 2)
+        store.store_proof(k1, blob)
+        store.store_proof(k2, damaged)
+        check = lambda data: cv.verify_with_vk(data, 7)
+        assert store.get_proof_verified(k1, check) == blob
+        with pytest.raises(ValueError, match=f"status {want}"):
+            store.get_proof_verified(k2, check)
+    cv.free()
+    cp.free()
+
+
+def test_forest_nodes_where_they_lie(ctx, mp2):
+    """a small table build through table.NativeTableBuild: the kept nodes (root, sampled rows and their children, their cells roots)
+    verified by mp2g_forest_verify where they lie in the forest's device pool, grouped by circuit with one verifier per wrap circuit
+    (params.rows.chains[name][-1] / params.cells.chains[name][-1]): all 0 and equal to the oracle on the downloaded words; a kept
+    node with one word of its slot flipped: rejected; an unknown or released id: the call fails and writes no status"""
+    T = importlib.import_module("mapreduce-plonky2_amd.table")
+    IX = importlib.import_module("mapreduce-plonky2_amd.indexing")
+    prover = FW.GpuProver(ctx, capacity=8)
+    params = T.TableParams(prover, FW.circuit_fri_params, IX.empty_poseidon_hash(ctx))
+    n = 12
+    table = T.SyntheticTable(n, 4, seed=0xC0FFEE04, block=2)
+    root, nodes, spans = T.balanced_bst(n)
+    samples, keep = T.sample_nodes(nodes, spans)
+    wit = T.TableWitness(ctx, table, spans)
+    nb = T.NativeTableBuild(params, [prover], batch=8, subtree_size=8, group_rows=16)
+    nb.run(table, wit, root, nodes, keep=samples)
+    kept_rows = sorted(nb.row_proofs)
+    assert root in kept_rows and len(kept_rows) >= 3
+    cells_root = T.sbbst_root(4)
+    groups = {}  # (set, circuit name) -> node ids
+    for k in kept_rows:
+        groups.setdefault(("rows", nb.row_proofs[k][1]), []).append(k)
+        groups.setdefault(("cells", nb.cells_roots[k][1]), []).append(nb.cell_id(k, cells_root))
+    checked = 0
+    for (which, name), ids in sorted(groups.items()):
+        fw, fp, npi = (params.rows, nb.fp_rows, nb.npi_rows) if which == "rows" else (params.cells, nb.fp_cells, nb.npi_cells)
+        wckt, wcap, wdig = fw.chains[name][-1]
+        cv = FW.CircuitVerifier(ctx, wckt, len(ids), fp=fp, constants_sigmas_cap=wcap, circuit_digest=wdig, n_public_inputs=npi)
+        got = nb.forest.verify(ids, cv).tolist()
+        ofp = C.oracle_params(wckt)
+        offs = np.cumsum([0] + cv.v.part_words)
+        want = []
+        for i in ids:
+            w = nb.forest.proof_words(i)
+            assert w.size == cv.v.proof_words
+            pis, caps13, op, fri = (w[offs[j]:offs[j + 1]] for j in range(4))
+            caps = np.concatenate([np.asarray(wcap, dtype=np.uint64).reshape(-1), caps13]).reshape(4, -1)
+            want.append(oracle_status(wckt, ofp, wdig, O.hash_n_to_m_no_pad(pis, 4), caps, op.reshape(-1, 2), fri))
+        print("forest", which, name, len(ids), got, want)
+        assert got == want == [0] * len(ids)
+        checked += len(ids)
+        if which == "rows" and root in ids:
+            # flip one word of the root's slot (an opening limb), verify, restore
+            addr, nw = nb.forest.device_proof(root)
+            at = addr + 8 * int(offs[2] + 10)
+            word = ctx.d2h_raw(at, (1,))
+            flipped = word ^ np.uint64(1)
+            h2d = lambda a: mp2.load().mp2g_h2d(ctx.h, ctypes.c_void_p(at), a.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(8))
+            assert h2d(flipped) == 0
+            st = nb.forest.verify(ids, cv).tolist()
+            assert h2d(word) == 0
+            assert [i for i, s in zip(ids, st) if s] == [root], st
+            # an unknown id fails the whole call
+            with pytest.raises(mp2.Mp2gError, match="unknown node"):
+                nb.forest.verify([(77 << 40) | 5], cv)
+        cv.free()
+    assert checked == 2 * len(kept_rows)
+    # a released node: the call fails, the status array is untouched
+    some = next(k for k in kept_rows if k != root)
+    name = nb.row_proofs[some][1]
+    wckt, wcap, wdig = params.rows.chains[name][-1]
+    cv = FW.CircuitVerifier(ctx, wckt, 2, fp=nb.fp_rows, constants_sigmas_cap=wcap, circuit_digest=wdig, n_public_inputs=nb.npi_rows)
+    assert nb.forest.verify([some], cv).tolist() == [0]
+    nb.forest.release(some)
+    status = np.full(1, 0xFFFFFFFF, dtype=np.uint32)
+    ids = np.array([some], dtype=np.uint64)
+    rc = mp2.load().mp2g_forest_verify(nb.forest.h, cv.v.h, ids.ctypes.data_as(ctypes.c_void_p), 1, status.ctypes.data_as(ctypes.c_void_p))
+    assert rc != 0 and status[0] == 0xFFFFFFFF and b"released" in mp2.load().mp2g_last_error()
+    cv.free()
+    nb.free()
+    prover.free()
+
+
+def test_c_client(tmp_path):
+    """examples/c_verify_proof.c builds with the system compiler against include/mp2g.h alone, proves a small circuit, verifies it on
+    the device (0), flips one opening word and verifies again (non-zero)"""
+    exe = os.path.join(ROOT, "examples", "c_verify_proof")
+    subprocess.check_call(["gcc", "-std=c11", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"),
+                           os.path.join(ROOT, "examples", "c_verify_proof.c"), "-L" + os.path.join(ROOT, "mapreduce-plonky2_amd"),
+                           "-lmp2gpu", "-Wl,-rpath," + os.path.join(ROOT, "mapreduce-plonky2_amd"), "-o", exe])
+    log_n, pow_bits, queries = 6, 5, 3
+    ckt = C.build(log_n, C.LEAF_KINDS, 41)
+    path = str(tmp_path / "circuit.bin")
+    with open(path, "wb") as f:
+        f.write(np.array([log_n, ckt.num_constants, C.NUM_ROUTED, C.NUM_WIRES, len(ckt.gates), ckt.num_selectors, pow_bits, queries],
+                         dtype=np.uint32).tobytes())
+        f.write(bytes(ckt.gate_array))
+        f.write(O.arr(ckt.pi_hash).tobytes() + O.arr(O.rand_field(4, 6)).tobytes() + O.arr(ckt.pre).tobytes() + O.arr(ckt.wires).tobytes())
+    out = subprocess.run([exe, path], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, out.stdout + out.stderr
+    statuses = [int(line.split("=")[1]) for line in out.stdout.splitlines() if line.startswith("status=")]
+    print(out.stdout)
+    assert len(statuses) == 2 and statuses[0] == 0 and statuses[1] != 0
