@@ -164,7 +164,8 @@ uint32_t mp2g_reduction_arity_bits(uint32_t degree_bits, uint32_t rate_bits, uin
  *   query_round_proofs [num_queries] { initial_trees_proof: per oracle { leaf[w], siblings[lg-cap][4] };
  *                                      steps: per layer { evals[1<<arity][2], siblings[..][4] } }
  *   final_poly [final_len][2]
- *   pow_witness */
+ *   pow_witness
+ * (the library's own offsets into this layout and into the openings: csrc/layout.h) */
 size_t mp2g_fri_proof_words(const mp2g_fri_params* p);
 /* sum(oracle_w) + zs_count + zs_count * num_lookup_polys extension values, in FRI batch order
  * (OpeningSet::to_fri_openings): at zeta every polynomial in oracle order except the lookup polynomials, which

@@ -470,12 +470,17 @@ def lookup_array(luts):
     return arr, tabs
 
 
+def gate_array(gates):
+    """(Gate * n) from the builder's gates or from Gates (anything with the seven fields of mp2g_gate)"""
+    return (Gate * max(1, len(gates)))(*[Gate(g.kind, g.p0, g.p1, g.p2, g.selector_index, g.group_start, g.group_end) for g in gates])
+
+
 def eval_gate_constraints(ctx, gates, num_selectors, consts, wires, pi_hash):
     """Filtered gate constraints C_j at arbitrary points: consts [num_constants][npts], wires [w][npts]
     -> [max_j][npts]. All zero on H for a satisfied witness (plonky2's prove() panics otherwise)."""
     c, w, ph = _arr(consts), _arr(wires), _arr(pi_hash)
-    arr = (Gate * len(gates))(*gates)
-    max_j = max(g.num_constraints for g in gates)
+    arr = gate_array(gates)
+    max_j = max(arr[i].num_constraints for i in range(len(gates)))
     out = np.zeros((max_j, w.shape[1]), dtype=np.uint64)
     _ck(load().mp2g_eval_gate_constraints(ctx.h, arr, len(gates), num_selectors, _p(c), c.shape[0], _p(w), w.shape[0],
                                           ctypes.c_uint64(w.shape[1]), _p(ph), _p(out)))
@@ -510,8 +515,7 @@ class BatchedProver:
     def set_gates(self, gates, num_selectors):
         """Gate table of the circuit (CommonCircuitData::gates + SelectorsInfo): the quotient then
         includes the gate constraint terms -- prove() of a circuit built from the supported gates."""
-        arr = (Gate * len(gates))(*gates)
-        _ck(load().mp2g_prover_set_gates(self.h, arr, len(gates), num_selectors))
+        _ck(load().mp2g_prover_set_gates(self.h, gate_array(gates), len(gates), num_selectors))
 
     def set_lookups(self, luts):
         """Lookup tables of the circuit (CommonCircuitData::luts + ProverOnlyCircuitData::lookup_rows): prove() then
@@ -583,8 +587,7 @@ PI_HASH_GIVEN = 0xFFFFFFFF
 def gate_table_line_points(gates, num_selectors):
     """mp2g_gate_table_line_points: the number of base-field points the verifier evaluates the gate constraints at (1 + the
     largest filtered constraint degree of the table). Host arithmetic: needs no GPU."""
-    arr = (Gate * max(1, len(gates)))(*[Gate(g.kind, g.p0, g.p1, g.p2, g.selector_index, g.group_start, g.group_end) for g in gates])
-    return int(load().mp2g_gate_table_line_points(arr, len(gates), int(num_selectors)))
+    return int(load().mp2g_gate_table_line_points(gate_array(gates), len(gates), int(num_selectors)))
 
 
 def verifier_part_words(fp, n_public_inputs):
@@ -604,7 +607,7 @@ class Verifier:
         self.ctx, self.fp, self.capacity, self.n_public_inputs = ctx, fp, int(capacity), n_public_inputs
         cap, dig = _arr(constants_sigmas_cap).ravel(), _arr(circuit_digest)
         assert cap.size == fp.cap_words and dig.size == 4
-        arr = (Gate * max(1, len(gates)))(*[Gate(g.kind, g.p0, g.p1, g.p2, g.selector_index, g.group_start, g.group_end) for g in gates])
+        arr = gate_array(gates)
         larr, keep = lookup_array(luts or [])
         self.h = ctypes.c_void_p()
         _ck(load().mp2g_verifier_create(ctx.h, ctypes.byref(fp), _p(cap), _p(dig), int(num_routed), int(degree), arr, len(gates),

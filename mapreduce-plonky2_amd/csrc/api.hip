@@ -18,8 +18,6 @@ int mp2g::fail(const char* fmt, ...) {
   va_end(ap);
   return 1;
 }
-#define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fail("%s: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
-#define NEED(c, msg) do { if (!(c)) return fail("invalid argument: %s", msg); } while (0)
 
 extern "C" {
 

@@ -2,6 +2,7 @@
 // forest.hip fills the staging buffer itself and queues its own device copies between the upload and the first witness replay.
 #pragma once
 #include "ctx.h"
+#include "layout.h"
 #include "witness.h"
 
 struct mp2g_chain {
@@ -12,8 +13,20 @@ struct mp2g_chain {
     mp2g_witness_program* prog = nullptr;
     const u64* d_digest = nullptr;
     mp2g_fri_params P{};
-    size_t n_in = 0, n_probe = 0, cap_words = 0, n_open = 0, proof_words = 0;
+    size_t n_in = 0, n_probe = 0;  // witness inputs; probe words = the public-inputs hash, then the public inputs
+    mp2g::ProofParts parts{};      // a proof of this step in a parent's input order (layout.h)
     mp2g::DevBuf in, wires, probe, pi_hash, caps, openings, proof;
+    // The step's outputs are one buffer per part (`caps` also holds the cap of oracle 0, first). Part k (k < 4, the order of `parts`)
+    // of proof j of the last prove: parts.n[k] words at part(k, j); consecutive proofs lie part_stride(k) words apart. Every
+    // hand-over of a proof (to the next step, to a pool slot, to a caller) goes through these two.
+    size_t part_stride(uint32_t k) const {
+      const size_t stride[4] = {n_probe, (size_t)parts.n[1] + parts.capw, parts.n[2], parts.n[3]};
+      return stride[k];
+    }
+    const u64* part(uint32_t k, size_t j = 0) const {
+      const u64* first[4] = {probe.p + 4, caps.p + parts.capw, openings.p, proof.p};
+      return first[k] + j * part_stride(k);
+    }
   };
   Step steps[8];  // DevBuf owns device memory and does not move
   uint32_t n_steps = 0;

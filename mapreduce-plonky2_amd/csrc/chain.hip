@@ -14,8 +14,6 @@
 #include <new>
 
 using namespace mp2g;
-#define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fail("%s: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
-#define NEED(c, msg) do { if (!(c)) return fail("invalid argument: %s", msg); } while (0)
 
 extern "C" {
 int mp2g_chain_create(mp2g_ctx* c, uint32_t n_steps, mp2g_prover* const* provers, mp2g_witness_program* const* programs,
@@ -35,23 +33,20 @@ int mp2g_chain_create(mp2g_ctx* c, uint32_t n_steps, mp2g_prover* const* provers
     st.n_in = st.prog->input_sids.size();
     st.n_probe = st.prog->probe.size();
     if (st.n_probe < 4) { delete ch; return fail("invalid argument: step %u: set the program's probe (public-inputs hash, public inputs) first", s); }
-    st.cap_words = (size_t)4 << P.cap_height;
-    st.n_open = mp2g_fri_n_openings(&P);
-    st.proof_words = mp2g_fri_proof_words(&P);
+    st.parts = proof_parts(P, (u32)(st.n_probe - 4));
     if (s > 0) {
-      const mp2g_chain::Step& pv = ch->steps[s - 1];
-      const size_t want = (pv.n_probe - 4) + 3 * pv.cap_words + 2 * pv.n_open + pv.proof_words;
+      const size_t want = ch->steps[s - 1].parts.words;
       if (st.n_in != want) { delete ch; return fail("invalid argument: step %u takes %zu inputs, a proof of step %u has %zu words", s, st.n_in, s - 1, want); }
     }
     const size_t B = capacity;
     auto A = [&](DevBuf& d, size_t words) { if (e == hipSuccess) e = d.alloc(words * sizeof(u64)); };
     A(st.in, B * st.n_in); A(st.wires, (B * NUM_WIRES) << P.log_n); A(st.probe, B * st.n_probe); A(st.pi_hash, B * 4);
-    A(st.caps, B * P.n_oracles * st.cap_words); A(st.openings, B * st.n_open * 2); A(st.proof, B * st.proof_words);
+    A(st.caps, B * st.part_stride(1)); A(st.openings, B * st.part_stride(2)); A(st.proof, B * st.part_stride(3));
   }
   if (e == hipSuccess) e = hipHostMalloc((void**)&ch->h_in, (size_t)capacity * ch->steps[0].n_in * sizeof(u64), hipHostMallocDefault);
   if (e == hipSuccess) {
     const mp2g_chain::Step& L = ch->steps[n_steps - 1];
-    e = hipHostMalloc((void**)&ch->h_out, (size_t)capacity * (L.P.n_oracles * L.cap_words + 2 * L.n_open + L.proof_words + L.n_probe) * sizeof(u64), hipHostMallocDefault);
+    e = hipHostMalloc((void**)&ch->h_out, (size_t)capacity * (L.part_stride(0) + L.part_stride(1) + L.part_stride(2) + L.part_stride(3)) * sizeof(u64), hipHostMallocDefault);
   }
   if (e != hipSuccess) { delete ch; return fail("chain_create: %s", hipGetErrorString(e)); }
   *out = ch;
@@ -83,12 +78,9 @@ static int chain_steps(mp2g_chain* ch, uint32_t batch, const u64* h_in, const mp
   for (size_t k = 0; k < ch->n_steps; k++) {
     mp2g_chain::Step& st = ch->steps[k];
     if (k > 0) {  // the previous proof becomes this step's witness inputs: public inputs, caps of oracles 1..3, openings, FRI proof words
-      mp2g_chain::Step& pv = ch->steps[k - 1];
-      const size_t n_pi = pv.n_probe - 4, cw = 3 * pv.cap_words, ow = 2 * pv.n_open, pw = pv.proof_words, pitch = st.n_in * 8;
-      CK(hipMemcpy2DAsync(st.in.p, pitch, pv.probe.p + 4, pv.n_probe * 8, n_pi * 8, batch, hipMemcpyDeviceToDevice, s));
-      CK(hipMemcpy2DAsync(st.in.p + n_pi, pitch, pv.caps.p + pv.cap_words, pv.P.n_oracles * pv.cap_words * 8, cw * 8, batch, hipMemcpyDeviceToDevice, s));
-      CK(hipMemcpy2DAsync(st.in.p + n_pi + cw, pitch, pv.openings.p, ow * 8, ow * 8, batch, hipMemcpyDeviceToDevice, s));
-      CK(hipMemcpy2DAsync(st.in.p + n_pi + cw + ow, pitch, pv.proof.p, pw * 8, pw * 8, batch, hipMemcpyDeviceToDevice, s));
+      const mp2g_chain::Step& pv = ch->steps[k - 1];
+      for (uint32_t i = 0; i < 4; i++)
+        CK(hipMemcpy2DAsync(st.in.p + pv.parts.off[i], st.n_in * 8, pv.part(i), pv.part_stride(i) * 8, pv.parts.n[i] * 8, batch, hipMemcpyDeviceToDevice, s));
     }
     int rc = mp2g_prover_set_active(st.pr, batch);
     if (rc) return rc;
@@ -152,8 +144,7 @@ int mp2g::chain_run_staged(mp2g_chain* ch, uint32_t batch, const mp2g_chain_patc
     if (rc) return rc;
   }
   mp2g_chain::Step& L = ch->steps[ch->n_steps - 1];
-  const size_t n_caps = (size_t)batch * L.P.n_oracles * L.cap_words, n_op = (size_t)batch * L.n_open * 2, n_pf = (size_t)batch * L.proof_words,
-               n_pi = L.n_probe - 4;
+  const size_t n_caps = batch * L.part_stride(1), n_op = batch * L.part_stride(2), n_pf = batch * L.part_stride(3), n_pi = L.parts.n[0];
   u64* hc = ch->h_out;
   u64* ho = hc + n_caps;
   u64* hp = ho + n_op;
@@ -161,7 +152,7 @@ int mp2g::chain_run_staged(mp2g_chain* ch, uint32_t batch, const mp2g_chain_patc
   if (caps) CK(hipMemcpyAsync(hc, L.caps.p, n_caps * 8, hipMemcpyDeviceToHost, s));
   if (openings) CK(hipMemcpyAsync(ho, L.openings.p, n_op * 8, hipMemcpyDeviceToHost, s));
   if (proof) CK(hipMemcpyAsync(hp, L.proof.p, n_pf * 8, hipMemcpyDeviceToHost, s));
-  if (public_inputs) CK(hipMemcpy2DAsync(hi, n_pi * 8, L.probe.p + 4, L.n_probe * 8, n_pi * 8, batch, hipMemcpyDeviceToHost, s));
+  if (public_inputs) CK(hipMemcpy2DAsync(hi, n_pi * 8, L.part(0), L.part_stride(0) * 8, n_pi * 8, batch, hipMemcpyDeviceToHost, s));
   if (hooks && hooks->after) { int rc = hooks->after(hooks->user, ch, s); if (rc) return rc; }
   CK(hipStreamSynchronize(s));
   if (caps) memcpy(caps, hc, n_caps * 8);
@@ -193,10 +184,7 @@ int mp2g_chain_step_buffers(const mp2g_chain* ch, uint32_t step, uint64_t** d_wi
 int mp2g_chain_device_proof(const mp2g_chain* ch, uint32_t b, const uint64_t* d_parts[4], uint32_t n_words[4]) {
   NEED(ch && d_parts && n_words && b < ch->last_batch, "chain / proof index of the last run");
   const mp2g_chain::Step& L = ch->steps[ch->n_steps - 1];
-  d_parts[0] = L.probe.p + (size_t)b * L.n_probe + 4;                      n_words[0] = (uint32_t)(L.n_probe - 4);
-  d_parts[1] = L.caps.p + ((size_t)b * L.P.n_oracles + 1) * L.cap_words;   n_words[1] = (uint32_t)(3 * L.cap_words);
-  d_parts[2] = L.openings.p + (size_t)b * L.n_open * 2;                    n_words[2] = (uint32_t)(2 * L.n_open);
-  d_parts[3] = L.proof.p + (size_t)b * L.proof_words;                      n_words[3] = (uint32_t)L.proof_words;
+  for (uint32_t k = 0; k < 4; k++) { d_parts[k] = L.part(k, b); n_words[k] = L.parts.n[k]; }
   return 0;
 }
 

@@ -6,7 +6,10 @@
 
 namespace mp2g {
 int fail(const char* fmt, ...);  // records mp2g_last_error(), returns 1
-int params_check(const mp2g_fri_params* p);  // prover.hip: every bound the layout arithmetic relies on
+int params_check(const mp2g_fri_params* p);  // prover.hip: every bound the layout arithmetic (layout.h) relies on
+// for functions that return fail()'s int: a failed HIP call / a refused argument
+#define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fail("%s: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
+#define NEED(c, msg) do { if (!(c)) return fail("invalid argument: %s", msg); } while (0)
 
 // owning device buffer of u64 words
 struct DevBuf {

@@ -4,8 +4,6 @@
 
 using namespace mp2g;
 
-#define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fail("%s: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
-#define NEED(c, msg) do { if (!(c)) return fail("invalid argument: %s", msg); } while (0)
 
 static int copy_out(mp2g_ctx* c, const DevBuf& dw, const DevBuf& dwei, size_t count, uint64_t* out_w, uint64_t* out_wei) {
   if (out_w) CK(hipMemcpyAsync(out_w, dw.p, count * 5 * sizeof(u64), hipMemcpyDeviceToHost, c->stream));

@@ -32,8 +32,6 @@
 using namespace mp2g;
 // the error text of a worker thread travels to the caller's thread (mp2g_last_error is thread local)
 extern "C" const char* mp2g_last_error(void);
-#define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fail("%s: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
-#define NEED(c, msg) do { if (!(c)) return fail("invalid argument: %s", msg); } while (0)
 
 namespace {
 constexpr uint32_t MAX_CHILDREN = 4;
@@ -226,8 +224,7 @@ int prove_unit_body(mp2g_forest* f, uint32_t w, const uint64_t* ids, uint32_t co
       const Circuit& C = f->circuits[c];
       const mp2g_chain::Step& s0 = ch->steps[0];
       const mp2g_chain::Step& L = ch->steps[ch->n_steps - 1];
-      const uint32_t n_pi = (uint32_t)(L.n_probe - 4), cw = (uint32_t)(3 * L.cap_words), ow = (uint32_t)(2 * L.n_open), pw = (uint32_t)L.proof_words;
-      const uint32_t out_words = n_pi + cw + ow + pw;
+      const uint32_t out_words = (uint32_t)L.parts.words;
       if (out_words > f->slot_words) UNIT_FAIL(fail("forest: a proof of circuit %u has %u words, the pool's slots %u", c, out_words, f->slot_words));
       for (size_t lo = 0; lo < todo.size(); lo += ch->cap) {
         const uint32_t B = (uint32_t)std::min<size_t>(ch->cap, todo.size() - lo);
@@ -310,10 +307,7 @@ int prove_unit_body(mp2g_forest* f, uint32_t w, const uint64_t* ids, uint32_t co
         // outputs -> slots, in a parent's input order: public inputs, caps of oracles 1..3, openings, FRI words
         for (uint32_t j = 0; j < B; j++) {
           u64* slot = f->pool.p + (size_t)slots[j] * f->slot_words;
-          R.h_jobs[nb++] = Copy{L.probe.p + (size_t)j * L.n_probe + 4, slot, n_pi, 0};
-          R.h_jobs[nb++] = Copy{L.caps.p + ((size_t)j * L.P.n_oracles + 1) * L.cap_words, slot + n_pi, cw, 0};
-          R.h_jobs[nb++] = Copy{L.openings.p + (size_t)j * L.n_open * 2, slot + n_pi + cw, ow, 0};
-          R.h_jobs[nb++] = Copy{L.proof.p + (size_t)j * L.proof_words, slot + n_pi + cw + ow, pw, 0};
+          for (uint32_t k = 0; k < 4; k++) R.h_jobs[nb++] = Copy{L.part(k, j), slot + L.parts.off[k], L.parts.n[k], 0};
         }
         {
           hipError_t e = hipMemcpyAsync(R.d_jobs, R.h_jobs, (size_t)nb * sizeof(Copy), hipMemcpyHostToDevice, stream);

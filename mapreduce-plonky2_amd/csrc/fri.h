@@ -1,6 +1,6 @@
 // Shapes shared by the FRI kernels (fri.hip) and the batched prover (prover.hip).
 #pragma once
-#include "gl.cuh"
+#include "layout.h"
 
 namespace mp2g {
 
@@ -27,19 +27,14 @@ struct FriShape {
   u32 lookup_count;  // the last lookup_count polynomials of oracle zs_oracle: opened at zeta AND g*zeta, last in both batches
   OracleRef o[8];
 };
-// FRI batch order (plonk/circuit_data.rs fri_all_polys / fri_next_batch_polys; also the order of the flat openings
-// and of the transcript, OpeningSet::to_fri_openings): batch 0 (zeta) = every polynomial in oracle order except the
-// lookup polynomials, which come last; batch 1 (g zeta) = the Z polynomials, then the lookup polynomials.
-GLHD u32 fri_batch_len(const FriShape& sh, u32 batch) { return batch ? sh.zs_count + sh.lookup_count : sh.n_polys; }
-GLHD void fri_batch_poly(const FriShape& sh, u32 batch, u32 j, u32& o, u32& p) {
-  const u32 zo = sh.zs_oracle, wz = sh.o[zo].w - sh.lookup_count;
-  if (batch) { o = zo; p = j < sh.zs_count ? j : wz + (j - sh.zs_count); return; }
-  for (u32 oi = 0; oi < sh.n_oracles; oi++) {
-    const u32 w = oi == zo ? wz : sh.o[oi].w;
-    if (j < w) { o = oi; p = j; return; }
-    j -= w;
-  }
-  o = zo; p = wz + j;
+// the scalars and the widths of a shape; the caller adds the oracles' pointers and strides (the batch order of the polynomials:
+// fri_batch_len / fri_batch_poly, layout.h)
+inline FriShape fri_shape(const mp2g_fri_params& P) {
+  FriShape sh{};
+  sh.log_n = P.log_n; sh.rate_bits = P.rate_bits; sh.cap_h = P.cap_height; sh.n_oracles = P.n_oracles;
+  sh.zs_oracle = P.zs_oracle; sh.zs_count = P.zs_count; sh.lookup_count = P.zs_count * P.num_lookup_polys;
+  for (u32 o = 0; o < P.n_oracles; o++) { sh.o[o].w = P.oracle_w[o]; sh.n_polys += P.oracle_w[o]; }
+  return sh;
 }
 struct FriLayers {
   u32 n_layers;
@@ -66,8 +61,9 @@ hipError_t fri_soa_to_aos(hipStream_t s, u32 B, u32 n, const u64* in, u64 in_bst
 // witness: B * FRI_POW_STRIDE words, proof b's result at witness[b * FRI_POW_STRIDE]
 #define FRI_POW_STRIDE 16
 hipError_t fri_pow(hipStream_t s, int variant, const ChState* st, u32 B, u32 bits, u64* witness);
-hipError_t fri_queries(hipStream_t s, const FriShape& sh, const FriLayers& ly, u32 B, u32 num_queries, const u64* chal,
-                       u64 chal_bstride, u64* proof, u64 proof_bstride, u64 q_off, u64 q_words);
+// writes the query sections of B flat proofs (layout.h)
+hipError_t fri_queries(hipStream_t s, const FriShape& sh, const FriLayers& ly, const FriProofLayout& L, u32 B, u32 num_queries,
+                       const u64* chal, u64 chal_bstride, u64* proof);
 hipError_t bind_public_inputs(hipStream_t s, u32 B, u64* wires, u64 wires_bstride, u64 n, u32 row, const u64* pi_hash);
 hipError_t copy_rows(hipStream_t s, u32 B, const u64* src, u64 src_bstride, u64* dst, u64 dst_bstride, u32 words);
 }  // namespace mp2g

@@ -398,47 +398,40 @@ __global__ void fill_u64_kernel(u64* p, u64 v, u32 n) {
 }
 
 // ---- query rounds -----------------------------------------------------------------------------
-// grid (num_queries, B); writes section q of proof b in the flat layout of include/mp2g.h
-__global__ void __launch_bounds__(256) query_kernel(FriShape sh, FriLayers ly, const u64* chal /*[B][num_queries]*/, u64 chal_bstride,
-                                                      u64* proof, u64 proof_bstride, u64 q_off, u64 q_words) {
+// grid (num_queries, B); writes section q of proof b in the flat layout of layout.h: path p's leaf at leaf_off[p], its siblings behind it
+__global__ void __launch_bounds__(256) query_kernel(FriShape sh, FriLayers ly, FriProofLayout L, const u64* chal /*[B][num_queries]*/,
+                                                      u64 chal_bstride, u64* proof) {
   const u32 q = blockIdx.x, b = blockIdx.y, t = threadIdx.x;
-  const u32 lg = sh.log_n + sh.rate_bits;
+  const u32 lg = L.lg;
   const u64 N = (u64)1 << lg;
   u64 x = chal[b * chal_bstride + q] % N;
-  u64* o = proof + b * proof_bstride + q_off + q * q_words;
-  const u32 depth = lg - sh.cap_h;
-  for (u32 oi = 0; oi < sh.n_oracles; oi++) {
-    const OracleRef& r = sh.o[oi];
-    const u64* vals = r.values + b * r.value_bstride;
-    for (u32 p = t; p < r.w; p += 256) o[p] = vals[(u64)p * N + x];
-    o += r.w;
-    const u64* lv = r.levels + b * r.level_bstride;
-    for (u32 e = t; e < depth * 4; e += 256) {
-      u32 l = e >> 2, k = e & 3;
-      u64 off = 0;
-      for (u32 j = 0; j < l; j++) off += (u64)4 << (lg - j);
-      o[e] = lv[off + 4 * ((x >> l) ^ 1) + k];
-    }
-    o += depth * 4;
-  }
-  u32 clg = lg;
-  for (u32 li = 0; li < ly.n_layers; li++) {
-    const u32 ab = ly.arity_bits[li], A = 1u << ab;
-    const u64 m = (u64)1 << clg;
-    x >>= ab;
-    clg -= ab;
-    const u64* v = ly.values[li] + b * ly.value_bstride[li];
-    for (u32 e = t; e < 2 * A; e += 256) o[e] = v[(e & 1) * m + (x << ab) + (e >> 1)];
-    o += 2 * A;
-    const u32 d2 = clg - sh.cap_h;
-    const u64* lv = ly.levels[li] + b * ly.level_bstride[li];
-    for (u32 e = t; e < d2 * 4; e += 256) {
+  u64* const qs = proof + b * L.proof_words + L.q_off + q * L.q_words;
+  // the siblings of leaf x on the way up a tree of 2^clg leaves (merkle_levels_words: level l lies behind the levels below it)
+  auto siblings = [&](u64* o, const u64* lv, u32 clg, u32 n_sib, u64 x) {
+    for (u32 e = t; e < n_sib * 4; e += 256) {
       u32 l = e >> 2, k = e & 3;
       u64 off = 0;
       for (u32 j = 0; j < l; j++) off += (u64)4 << (clg - j);
       o[e] = lv[off + 4 * ((x >> l) ^ 1) + k];
     }
-    o += d2 * 4;
+  };
+  for (u32 oi = 0; oi < sh.n_oracles; oi++) {
+    const OracleRef& r = sh.o[oi];
+    u64* o = qs + L.leaf_off[oi];
+    const u64* vals = r.values + b * r.value_bstride;
+    for (u32 p = t; p < r.w; p += 256) o[p] = vals[(u64)p * N + x];
+    siblings(o + r.w, r.levels + b * r.level_bstride, lg, L.n_sib[oi], x);
+  }
+  u32 clg = lg;
+  for (u32 li = 0; li < ly.n_layers; li++) {
+    const u32 ab = ly.arity_bits[li], A = 1u << ab, p = sh.n_oracles + li;
+    const u64 m = (u64)1 << clg;
+    x >>= ab;
+    clg -= ab;
+    u64* o = qs + L.leaf_off[p];
+    const u64* v = ly.values[li] + b * ly.value_bstride[li];
+    for (u32 e = t; e < 2 * A; e += 256) o[e] = v[(e & 1) * m + (x << ab) + (e >> 1)];
+    siblings(o + 2 * A, ly.levels[li] + b * ly.level_bstride[li], clg, L.n_sib[p], x);
   }
 }
 // copy caps of tree b (last cap_words of its levels) to dst[b*dst_bstride ..]
@@ -512,10 +505,10 @@ hipError_t fri_pow(hipStream_t s, int variant, const ChState* st, u32 B, u32 bit
   else hipLaunchKernelGGL((pow_kernel<MP2G_POSEIDON>), g, bl, 0, s, st, bits, (unsigned long long*)witness);
   return hipGetLastError();
 }
-hipError_t fri_queries(hipStream_t s, const FriShape& sh, const FriLayers& ly, u32 B, u32 num_queries, const u64* chal, u64 chal_bstride,
-                       u64* proof, u64 proof_bstride, u64 q_off, u64 q_words) {
+hipError_t fri_queries(hipStream_t s, const FriShape& sh, const FriLayers& ly, const FriProofLayout& L, u32 B, u32 num_queries,
+                       const u64* chal, u64 chal_bstride, u64* proof) {
   if (!num_queries) return hipSuccess;
-  hipLaunchKernelGGL(query_kernel, dim3(num_queries, B), dim3(256), 0, s, sh, ly, chal, chal_bstride, proof, proof_bstride, q_off, q_words);
+  hipLaunchKernelGGL(query_kernel, dim3(num_queries, B), dim3(256), 0, s, sh, ly, L, chal, chal_bstride, proof);
   return hipGetLastError();
 }
 hipError_t bind_public_inputs(hipStream_t s, u32 B, u64* wires, u64 wires_bstride, u64 n, u32 row, const u64* pi_hash) {

@@ -12,6 +12,26 @@ struct GateTable {
 const char* gate_table_check(const GateTable& t, u32 num_constants, u32 wires_w);
 u32 gate_num_constraints(const mp2g_gate& g);
 u32 gate_degree(const mp2g_gate& g);
+// degree of the gate's constraints times its selector filter (gates/selectors.rs: one factor per other gate of the group, one
+// more for the unused-slot value when the circuit has several selector polynomials)
+inline u32 gate_filtered_degree(const mp2g_gate& g, u32 num_selectors) {
+  return gate_degree(g) + (g.group_end - g.group_start - 1) + (num_selectors > 1 ? 1 : 0);
+}
+// the table of a caller's gate array (n_gates <= MP2G_MAX_GATES), validated when it has gates: the message of gate_table_check
+// or nullptr. max_j (may be NULL): the largest constraint count of a gate
+inline const char* gate_table_make(const mp2g_gate* gates, u32 n_gates, u32 num_selectors, u32 num_lookup_selectors, u32 num_constants,
+                                   u32 wires_w, GateTable& out, u32* max_j) {
+  out = GateTable{};
+  out.n_gates = n_gates; out.num_selectors = num_selectors; out.num_lookup_selectors = num_lookup_selectors;
+  u32 mj = 0;
+  for (u32 i = 0; i < n_gates; i++) {
+    out.g[i] = gates[i];
+    const u32 k = gate_num_constraints(gates[i]);
+    if (k > mj) mj = k;
+  }
+  if (max_j) *max_j = mj;
+  return n_gates ? gate_table_check(out, num_constants, wires_w) : nullptr;
+}
 // q[b][a][i] (natural order i) = sum_g filter_g sum_j alpha_a^j c_{g,j} at the LDE point of memory column
 // p = bitrev(i): C / W are the bit-reversed LDE value matrices [.][N] of the constants (shared) and the
 // wires (per proof), N = 8n. quotient_perm_values(..., gates = true) folds q into the vanishing sum.

@@ -1,14 +1,17 @@
 // Launchers of the lookup-argument kernels (lookup.hip).
 #pragma once
-#include "gl.cuh"
-#include "mp2g.h"
+#include "ctx.h"
 namespace mp2g {
 typedef uint16_t u16;
-// the lookup tables of a circuit as the kernels take them (by value): rows of each table (plonky2's LookupWire), the
-// table on the device, and the slot geometry (LookupGate / LookupTableGate num_slots, partial polynomial degrees)
-struct LookupDev {
+// the slot geometry of the lookup argument (LookupGate / LookupTableGate num_slots, partial polynomial degrees); n_luts = 0:
+// the circuit has no lookups
+struct LookupGeometry {
   u32 n_luts;
   u32 num_lu_slots, num_lut_slots, num_sldc, lu_degree, lut_degree;
+};
+// the lookup tables of a circuit as the kernels take them (by value): the geometry, the rows of each table (plonky2's
+// LookupWire) and the table on the device
+struct LookupDev : LookupGeometry {
   u32 last_lu_row[MP2G_MAX_LUTS], last_lut_row[MP2G_MAX_LUTS], first_lut_row[MP2G_MAX_LUTS], table_len[MP2G_MAX_LUTS];
   const u16* table[MP2G_MAX_LUTS];  // device, [table_len][2]
 };
@@ -27,4 +30,14 @@ hipError_t lookup_polys(hipStream_t s, u32 B, const LookupDev& L, const u64* wir
 hipError_t quotient_lookup_values(hipStream_t s, u32 B, const LookupDev& L, const u64* C, u32 sel_off, const u64* W, u64 w_bstride,
                                   const u64* Z, u64 z_bstride, u32 lu_off, u32 log_n, const u64* deltas, u64 d_bstride,
                                   const u64* lut_eval, const u64* alphas, u64 al_bstride, u32 nc, u64* q);
+// Set-up shared by the prover and the verifier. lookup_geometry: the slot numbers of a circuit with num_routed routed wires and
+// partial-product degree `degree` >= 2 (each side keeps its own bounds on them). lookup_upload: the caller's tables go to the
+// device (`tables` is reallocated), L gets their rows and addresses; waits for the copies, the caller's memory may go away.
+inline void lookup_geometry(u32 num_routed, u32 degree, LookupGeometry& L) {
+  L.num_lu_slots = num_routed / 2; L.num_lut_slots = num_routed / 3;
+  L.lu_degree = degree - 1;
+  L.num_sldc = L.lu_degree ? (L.num_lu_slots + L.lu_degree - 1) / L.lu_degree : 0;
+  L.lut_degree = L.num_sldc ? (L.num_lut_slots + L.num_sldc - 1) / L.num_sldc : 0;
+}
+int lookup_upload(hipStream_t s, const mp2g_lookup* luts, u32 n_luts, DevBuf& tables, LookupDev& L);
 }  // namespace mp2g

@@ -244,4 +244,19 @@ hipError_t quotient_lookup_values(hipStream_t s, u32 B, const LookupDev& L, cons
                      lu_off, log_n, deltas, d_bstride, lut_eval, alphas, al_bstride, nc, q);
   return hipGetLastError();
 }
+int lookup_upload(hipStream_t s, const mp2g_lookup* luts, u32 n_luts, DevBuf& tables, LookupDev& L) {
+  size_t total = 0, off = 0;
+  for (u32 r = 0; r < n_luts; r++) total += (size_t)luts[r].table_len * 2;
+  CK(tables.alloc(total * sizeof(u16)));
+  L.n_luts = n_luts;
+  for (u32 r = 0; r < n_luts; r++) {
+    const mp2g_lookup& u = luts[r];
+    L.last_lu_row[r] = u.last_lu_row; L.last_lut_row[r] = u.last_lut_row; L.first_lut_row[r] = u.first_lut_row; L.table_len[r] = u.table_len;
+    L.table[r] = (const u16*)tables.p + off;
+    CK(hipMemcpyAsync((u16*)tables.p + off, u.table, (size_t)u.table_len * 2 * sizeof(u16), hipMemcpyHostToDevice, s));
+    off += (size_t)u.table_len * 2;
+  }
+  CK(hipStreamSynchronize(s));
+  return 0;
+}
 }  // namespace mp2g

@@ -15,8 +15,6 @@
 
 using namespace mp2g;
 
-#define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fail("%s: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
-#define NEED(c, msg) do { if (!(c)) return fail("invalid argument: %s", msg); } while (0)
 
 struct mp2g_challenger {
   mp2g_ctx* ctx = nullptr;
@@ -31,7 +29,8 @@ struct mp2g_prover {
   uint32_t B = 0;     // proofs per prove() call (mp2g_prover_set_active: 1 .. Bcap)
   uint32_t Bcap = 0;  // proofs the buffers were allocated for
   bool have_pre = false;
-  size_t capw = 0, levels_words = 0, proof_words = 0, q_words = 0, q_off = 0, final_off = 0, final_len = 0, n_open = 0;
+  FriProofLayout L{};  // of the flat FRI proofs this prover writes (layout.h)
+  size_t levels_words = 0, n_open = 0;
   DevBuf coeffs[8], values[8], levels[8];
   DevBuf ch, chal, zeta, alpha, betas, comp, quot, final_poly, witness, qchal;
   DevBuf fvals[9], flevels[8], fcoeffs[9];
@@ -145,30 +144,8 @@ uint32_t mp2g_reduction_arity_bits(uint32_t degree_bits, uint32_t rate_bits, uin
   }
   return n;
 }
-size_t mp2g_fri_n_openings(const mp2g_fri_params* p) {
-  size_t t = p->zs_count + (size_t)p->zs_count * p->num_lookup_polys;
-  for (uint32_t o = 0; o < p->n_oracles; o++) t += p->oracle_w[o];
-  return t;
-}
-static size_t query_words(const mp2g_fri_params* p) {
-  uint32_t lg = p->log_n + p->rate_bits;
-  size_t q = 0;
-  for (uint32_t o = 0; o < p->n_oracles; o++) q += p->oracle_w[o] + 4 * (lg - p->cap_height);
-  uint32_t cur = lg;
-  for (uint32_t i = 0; i < p->n_layers; i++) {
-    cur -= p->arity_bits[i];
-    q += ((size_t)2 << p->arity_bits[i]) + 4 * (cur - p->cap_height);
-  }
-  return q;
-}
-static size_t final_poly_len(const mp2g_fri_params* p) {
-  uint32_t deg = p->log_n;
-  for (uint32_t i = 0; i < p->n_layers; i++) deg -= p->arity_bits[i];
-  return (size_t)1 << deg;
-}
-size_t mp2g_fri_proof_words(const mp2g_fri_params* p) {
-  return p->n_layers * ((size_t)4 << p->cap_height) + p->num_queries * query_words(p) + 2 * final_poly_len(p) + 1;
-}
+size_t mp2g_fri_n_openings(const mp2g_fri_params* p) { return opening_layout(*p, 0).n_open; }
+size_t mp2g_fri_proof_words(const mp2g_fri_params* p) { return fri_proof_layout(*p).proof_words; }
 
 // ---- challenger ------------------------------------------------------------------------------
 int mp2g_challenger_create(mp2g_ctx* c, int variant, uint32_t count, mp2g_challenger** out) {
@@ -264,13 +241,8 @@ static int prover_create_impl(mp2g_ctx* c, const mp2g_fri_params* params, uint32
   const mp2g_fri_params& P = pr->P;
   const size_t n = (size_t)1 << P.log_n, N = n << P.rate_bits, B = batch;
   const uint32_t lg = P.log_n + P.rate_bits;
-  pr->capw = (size_t)4 << P.cap_height;
+  pr->L = fri_proof_layout(P);
   pr->levels_words = merkle_levels_words(lg, P.cap_height);
-  pr->proof_words = mp2g_fri_proof_words(&P);
-  pr->q_words = query_words(&P);
-  pr->q_off = P.n_layers * pr->capw;
-  pr->final_len = final_poly_len(&P);
-  pr->final_off = pr->q_off + P.num_queries * pr->q_words;
   pr->n_open = mp2g_fri_n_openings(&P);
   hipError_t e = hipSuccess;
   auto A = [&](DevBuf& d, size_t words) { if (e == hipSuccess) e = d.alloc(words * sizeof(u64)); };       // the prover's own (small, or persistent)
@@ -385,21 +357,15 @@ int mp2g_prover_enable_quotient(mp2g_prover* pr) {
 int mp2g_prover_set_gates(mp2g_prover* pr, const mp2g_gate* gates, uint32_t n_gates, uint32_t num_selectors) {
   NEED(pr && pr->quotient, "call mp2g_prover_enable_quotient first");
   NEED(n_gates <= MP2G_MAX_GATES, "at most MP2G_MAX_GATES gates");
-  GateTable t{};
-  t.n_gates = n_gates; t.num_selectors = num_selectors;
-  t.num_lookup_selectors = pr->gates.num_lookup_selectors;
-  if (n_gates) {
-    NEED(gates, "gates");
-    for (uint32_t i = 0; i < n_gates; i++) t.g[i] = gates[i];
-    const char* msg = gate_table_check(t, pr->P.oracle_w[0] - pr->num_routed, pr->P.oracle_w[1]);
-    if (msg) return fail("invalid gate table: %s", msg);
-    // filter degree + gate degree <= quotient_degree_factor + 1 (gates/selectors.rs is called with that bound:
-    // a degree-9n vanishing polynomial divided by Z_H fits the 8n-point coset)
-    for (uint32_t i = 0; i < n_gates; i++) {
-      uint32_t fdeg = t.g[i].group_end - t.g[i].group_start - 1 + (num_selectors > 1 ? 1 : 0);
-      if (fdeg + gate_degree(t.g[i]) > 9) return fail("invalid gate table: filtered degree of gate %u exceeds quotient degree factor + 1 = 9", i);
-    }
-  }
+  NEED(gates || !n_gates, "gates");
+  GateTable t;
+  const char* msg = gate_table_make(gates, n_gates, num_selectors, pr->gates.num_lookup_selectors, pr->P.oracle_w[0] - pr->num_routed,
+                                    pr->P.oracle_w[1], t, nullptr);
+  if (msg) return fail("invalid gate table: %s", msg);
+  // filter degree + gate degree <= quotient_degree_factor + 1 (gates/selectors.rs is called with that bound:
+  // a degree-9n vanishing polynomial divided by Z_H fits the 8n-point coset)
+  for (uint32_t i = 0; i < n_gates; i++)
+    if (gate_filtered_degree(t.g[i], num_selectors) > 9) return fail("invalid gate table: filtered degree of gate %u exceeds quotient degree factor + 1 = 9", i);
   pr->gates = t;
   pr->drop_graph();
   return 0;
@@ -415,7 +381,7 @@ static int fri_tail(mp2g_prover* pr, const FriShape& sh, ChState* st, u64* d_pro
   const mp2g_fri_params& P = pr->P;
   const uint32_t B = pr->B, lg = P.log_n + P.rate_bits, V = P.variant;
   const u64 n = (u64)1 << P.log_n, N = n << P.rate_bits;
-  const size_t capw = pr->capw;
+  const size_t capw = pr->L.capw;
   u64* chal = pr->chal.p;
   CK(challenger_step(s, V, st, B, chal, 0, 0, pr->alpha.p, 2, 2));  // alpha
   CK(fri_final_poly(s, sh, B, pr->alpha.p, 2, pr->zeta.p, 2, pr->fapw.p, pr->comp.p, pr->quot.p, pr->final_poly.p));
@@ -435,30 +401,30 @@ static int fri_tail(mp2g_prover* pr, const FriShape& sh, ChState* st, u64* d_pro
     const size_t lw = merkle_levels_words(log_leaves, P.cap_height);
     CK(leaf_hash_ext_soa(s, V, pr->fvals[li].p, pr->fvals[li].p + m, ab, (u64)1 << log_leaves, pr->flevels[li].p, B, 2 * m, lw));
     CK(merkle_reduce(s, V, pr->flevels[li].p, log_leaves, P.cap_height, B, lw));
-    CK(copy_rows(s, B, pr->flevels[li].p + lw - capw, lw, proof + li * capw, pr->proof_words, (u32)capw));
+    CK(copy_rows(s, B, pr->flevels[li].p + lw - capw, lw, proof + li * capw, pr->L.proof_words, (u32)capw));
     u64* beta = pr->betas.p + 2 * li;
-    CK(challenger_step(s, V, st, B, proof + li * capw, pr->proof_words, (u32)capw, beta, 16, 2));
+    CK(challenger_step(s, V, st, B, proof + li * capw, pr->L.proof_words, (u32)capw, beta, 16, 2));
     ly.arity_bits[li] = ab;
     ly.values[li] = pr->fvals[li].p; ly.value_bstride[li] = 2 * m;
     ly.levels[li] = pr->flevels[li].p; ly.level_bstride[li] = lw;
     CK(fri_fold_values(s, B, clg, ab, pr->fvals[li].p, 2 * m, pr->fvals[li + 1].p, 2 * (m >> ab), beta, 16, shift));
     const bool last = li + 1 == P.n_layers;
-    if (last) CK(fri_fold_coeffs(s, B, (u32)nc, ab, cur_coeffs, 2 * nc, proof + pr->final_off, pr->proof_words, beta, 16, true));
+    if (last) CK(fri_fold_coeffs(s, B, (u32)nc, ab, cur_coeffs, 2 * nc, proof + pr->L.final_off, pr->L.proof_words, beta, 16, true));
     else CK(fri_fold_coeffs(s, B, (u32)nc, ab, cur_coeffs, 2 * nc, pr->fcoeffs[li + 1].p, 2 * (nc >> ab), beta, 16, false));
     cur_coeffs = pr->fcoeffs[li + 1].p;
     shift = gl_pow(shift, (u64)1 << ab);
     m >>= ab; nc >>= ab; clg -= ab;
   }
-  if (P.n_layers == 0) CK(fri_soa_to_aos(s, B, (u32)n, pr->final_poly.p, 2 * n, (u32)n, proof + pr->final_off, pr->proof_words));
-  CK(challenger_step(s, V, st, B, proof + pr->final_off, pr->proof_words, (u32)(2 * pr->final_len), chal, 8, 0));
+  if (P.n_layers == 0) CK(fri_soa_to_aos(s, B, (u32)n, pr->final_poly.p, 2 * n, (u32)n, proof + pr->L.final_off, pr->L.proof_words));
+  CK(challenger_step(s, V, st, B, proof + pr->L.final_off, pr->L.proof_words, (u32)(2 * pr->L.final_len), chal, 8, 0));
   STAGE_MARK(pr, 5);  // FRI batch composition + commit phase
   CK(fri_pow(s, V, st, B, P.pow_bits, pr->witness.p));
   STAGE_MARK(pr, 6);  // proof of work
-  CK(copy_rows(s, B, pr->witness.p, FRI_POW_STRIDE, proof + pr->final_off + 2 * pr->final_len, pr->proof_words, 1));
+  CK(copy_rows(s, B, pr->witness.p, FRI_POW_STRIDE, proof + pr->L.pow_off, pr->L.proof_words, 1));
   CK(challenger_step(s, V, st, B, pr->witness.p, FRI_POW_STRIDE, 1, chal, 8, 1));  // observe witness, draw pow response
   if (P.num_queries) {
     CK(challenger_step(s, V, st, B, chal, 0, 0, pr->qchal.p, P.num_queries, P.num_queries));
-    CK(fri_queries(s, sh, ly, B, P.num_queries, pr->qchal.p, P.num_queries, proof, pr->proof_words, pr->q_off, pr->q_words));
+    CK(fri_queries(s, sh, ly, pr->L, B, P.num_queries, pr->qchal.p, P.num_queries, proof));
   }
   return 0;
 }
@@ -550,7 +516,7 @@ static int prove_impl(mp2g_prover* pr, const uint64_t* const* d_values, const ui
   const mp2g_fri_params& P = pr->P;
   const uint32_t B = pr->B, V = P.variant;
   const u64 n = (u64)1 << P.log_n, N = n << P.rate_bits;
-  const size_t capw = pr->capw, LW = pr->levels_words;
+  const size_t capw = pr->L.capw, LW = pr->levels_words;
   ChState* st = (ChState*)pr->ch.p;
   u64* chal = pr->chal.p;
   const u64 caps_b = P.n_oracles * capw;
@@ -613,11 +579,9 @@ static int prove_impl(mp2g_prover* pr, const uint64_t* const* d_values, const ui
     }
     u64* cap_dst = (u64*)d_caps + o * capw;
     CK(copy_rows(s, B, pr->levels[o].p + LW - capw, LW, cap_dst, caps_b, (u32)capw));
-    // plonk/prover.rs: wires cap -> num_challenges betas, then as many gammas; zs cap -> num_challenges
-    // alphas; all other caps -> 0
     // (the PCS-only skeleton, which accepts any zs_count, draws as for two rounds)
     const uint32_t nch = P.zs_count >= 1 && P.zs_count <= 2 ? P.zs_count : 2;
-    uint32_t n_get = o == 1 ? (pr->lookups.n_luts ? 4 : 2) * nch : (o == 2 ? nch : 0);
+    const uint32_t n_get = plonk_challenges_after_cap(o, nch, pr->lookups.n_luts != 0);
     u64* dst = chal;
     u64 dst_stride = 8;
     if (pr->num_routed && o == 1) { dst = pr->bg.p; dst_stride = 8; }
@@ -628,16 +592,13 @@ static int prove_impl(mp2g_prover* pr, const uint64_t* const* d_values, const ui
   if (P.n_oracles < 4) for (uint32_t o = P.n_oracles; o <= 3; o++) STAGE_MARK(pr, o);
   CK(challenger_step(s, V, st, B, chal, 0, 0, pr->zeta.p, 2, 2));  // zeta
 
-  FriShape sh{};
-  sh.log_n = P.log_n; sh.rate_bits = P.rate_bits; sh.cap_h = P.cap_height; sh.n_oracles = P.n_oracles;
-  sh.zs_oracle = P.zs_oracle; sh.zs_count = P.zs_count; sh.lookup_count = P.zs_count * P.num_lookup_polys;
+  FriShape sh = fri_shape(P);
   for (uint32_t o = 0; o < P.n_oracles; o++) {
     OracleRef& r = sh.o[o];
-    r.coeffs = pr->coeffs[o].p; r.values = pr->values[o].p; r.levels = pr->levels[o].p; r.w = P.oracle_w[o];
+    r.coeffs = pr->coeffs[o].p; r.values = pr->values[o].p; r.levels = pr->levels[o].p;
     r.coeff_bstride = o ? (u64)r.w * n : 0;
     r.value_bstride = o ? (u64)r.w * N : 0;
     r.level_bstride = o ? LW : 0;
-    sh.n_polys += r.w;
   }
   CK(fri_openings(s, sh, B, pr->zeta.p, 2, pr->zpw.p, (u64*)d_openings));
   CK(challenger_step(s, V, st, B, (const u64*)d_openings, 2 * pr->n_open, (u32)(2 * pr->n_open), chal, 8, 0));
@@ -660,40 +621,25 @@ int mp2g_prover_set_lookups(mp2g_prover* pr, const mp2g_lookup* luts, uint32_t n
     return 0;
   }
   NEED(luts && pr->gates.n_gates, "luts; call mp2g_prover_set_gates first");
-  L.n_luts = n_luts;
-  L.num_lu_slots = pr->num_routed / 2; L.num_lut_slots = pr->num_routed / 3;
-  L.lu_degree = pr->degree - 1;
+  lookup_geometry(pr->num_routed, pr->degree, L);
   NEED(L.lu_degree >= 1 && L.num_lu_slots <= 40 && L.num_lut_slots >= 1, "slot geometry (num_routed <= 80, degree >= 2)");
-  L.num_sldc = (L.num_lu_slots + L.lu_degree - 1) / L.lu_degree;
-  L.lut_degree = (L.num_lut_slots + L.num_sldc - 1) / L.num_sldc;
   NEED(P.num_lookup_polys == L.num_sldc + 1, "params.num_lookup_polys must be ceil((num_routed/2) / (degree-1)) + 1");
   NEED(P.oracle_w[1] >= 3 * L.num_lut_slots && P.oracle_w[1] >= 2 * L.num_lu_slots, "wires");
   const uint32_t n_sel = 4 + n_luts, num_constants = P.oracle_w[0] - pr->num_routed;
   NEED(pr->gates.num_selectors + n_sel <= num_constants, "the constants must hold 4 + n_luts lookup selectors after the selectors");
   const uint64_t n = (uint64_t)1 << P.log_n;
-  size_t total = 0;
   for (uint32_t r = 0; r < n_luts; r++) {
     const mp2g_lookup& u = luts[r];
     NEED(u.table && u.table_len >= 1 && u.table_len <= 65536, "table");
     NEED(u.last_lu_row < u.last_lut_row && u.last_lut_row <= u.first_lut_row && (uint64_t)u.first_lut_row + 1 < n, "lookup rows");
     NEED((uint64_t)(u.first_lut_row - u.last_lut_row + 1) * L.num_lut_slots >= u.table_len, "the table does not fit its LookupTableGate rows");
-    total += (size_t)u.table_len * 2;
   }
   // from here on the old tables are gone: no captured graph and no LookupDev may point into them if a later step fails
   pr->drop_graph();
   pr->lookups = LookupDev{};
   pr->gates.num_lookup_selectors = 0;
-  CK(pr->lut_tables.alloc(total * sizeof(uint16_t)));
+  { int rc = lookup_upload(pr->ctx->stream, luts, n_luts, pr->lut_tables, L); if (rc) return rc; }
   CK(pr->lut_eval.alloc((size_t)pr->Bcap * P.zs_count * MP2G_MAX_LUTS * sizeof(u64)));
-  size_t off = 0;
-  for (uint32_t r = 0; r < n_luts; r++) {
-    const mp2g_lookup& u = luts[r];
-    L.last_lu_row[r] = u.last_lu_row; L.last_lut_row[r] = u.last_lut_row; L.first_lut_row[r] = u.first_lut_row; L.table_len[r] = u.table_len;
-    L.table[r] = (const uint16_t*)pr->lut_tables.p + off;
-    CK(hipMemcpyAsync((uint16_t*)pr->lut_tables.p + off, u.table, (size_t)u.table_len * 2 * sizeof(uint16_t), hipMemcpyHostToDevice, pr->ctx->stream));
-    off += (size_t)u.table_len * 2;
-  }
-  CK(hipStreamSynchronize(pr->ctx->stream));  // the caller's table memory may go away
   pr->lookups = L;
   pr->gates.num_lookup_selectors = n_sel;
   // the gate constants move behind the lookup selectors: re-validate the table against the constant count
@@ -792,15 +738,9 @@ int mp2g_eval_gate_constraints(mp2g_ctx* c, const mp2g_gate* gates, uint32_t n_g
   NEED(c && gates && consts && wires && pi_hash && out, "ctx/pointers");
   NEED(n_gates >= 1 && n_gates <= MP2G_MAX_GATES, "1..MP2G_MAX_GATES gates");
   NEED(npts >= 1 && npts <= ((uint64_t)1 << 28), "npts");
-  GateTable t{};
-  t.n_gates = n_gates; t.num_selectors = num_selectors;
+  GateTable t;
   uint32_t max_j = 0;
-  for (uint32_t i = 0; i < n_gates; i++) {
-    t.g[i] = gates[i];
-    uint32_t k = gate_num_constraints(gates[i]);
-    if (k > max_j) max_j = k;
-  }
-  const char* msg = gate_table_check(t, num_constants, wires_w);
+  const char* msg = gate_table_make(gates, n_gates, num_selectors, 0, num_constants, wires_w, t, &max_j);
   if (msg) return fail("invalid gate table: %s", msg);
   if (!max_j) return 0;
   DevBuf dc, dw, dp, dout;
@@ -847,9 +787,7 @@ int mp2g_fri_prove(mp2g_ctx* c, const mp2g_fri_params* params, mp2g_batch* const
   ProverGuard guard;
   guard.pr = pr;
   const mp2g_fri_params& P = pr->P;
-  FriShape sh{};
-  sh.log_n = P.log_n; sh.rate_bits = P.rate_bits; sh.cap_h = P.cap_height; sh.n_oracles = P.n_oracles;
-  sh.zs_oracle = P.zs_oracle; sh.zs_count = P.zs_count; sh.lookup_count = P.zs_count * P.num_lookup_polys;
+  FriShape sh = fri_shape(P);
   for (uint32_t o = 0; o < P.n_oracles; o++) {
     const mp2g_batch* b = oracles[o];
     if (!b || b->ctx != c || b->log_n != P.log_n || b->w != P.oracle_w[o] || b->rate_bits != P.rate_bits ||
@@ -857,17 +795,16 @@ int mp2g_fri_prove(mp2g_ctx* c, const mp2g_fri_params* params, mp2g_batch* const
       return fail("oracle %u does not match the FRI parameters", o);
     }
     OracleRef& r = sh.o[o];
-    r.coeffs = b->coeffs.p; r.values = b->values.p; r.levels = b->levels.p; r.w = b->w;
-    sh.n_polys += r.w;
+    r.coeffs = b->coeffs.p; r.values = b->values.p; r.levels = b->levels.p;
   }
   DevBuf dproof;
-  hipError_t e = dproof.alloc(pr->proof_words * sizeof(u64));
+  hipError_t e = dproof.alloc(pr->L.proof_words * sizeof(u64));
   if (e == hipSuccess) e = hipMemcpyAsync(pr->zeta.p, zeta, 2 * sizeof(u64), hipMemcpyHostToDevice, c->stream);
   if (e != hipSuccess) return fail("fri_prove setup: %s", hipGetErrorString(e));
   rc = bind_scratch(pr);
   if (!rc) rc = fri_tail(pr, sh, (ChState*)ch->st.p, dproof.p);
   if (!rc) {
-    e = hipMemcpyAsync(proof, dproof.p, pr->proof_words * sizeof(u64), hipMemcpyDeviceToHost, c->stream);
+    e = hipMemcpyAsync(proof, dproof.p, pr->L.proof_words * sizeof(u64), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) rc = fail("fri_prove copy-out: %s", hipGetErrorString(e));
   }
@@ -894,18 +831,18 @@ int mp2g_pcs_prove(mp2g_ctx* c, const mp2g_fri_params* params, const uint64_t* c
   }
   if (e == hipSuccess) e = dd.alloc(32);
   if (e == hipSuccess) e = dp.alloc(32);
-  if (e == hipSuccess) e = dcaps.alloc(P.n_oracles * pr->capw * sizeof(u64));
+  if (e == hipSuccess) e = dcaps.alloc(P.n_oracles * pr->L.capw * sizeof(u64));
   if (e == hipSuccess) e = dopen.alloc(pr->n_open * 2 * sizeof(u64));
-  if (e == hipSuccess) e = dproof.alloc(pr->proof_words * sizeof(u64));
+  if (e == hipSuccess) e = dproof.alloc(pr->L.proof_words * sizeof(u64));
   if (e == hipSuccess) e = hipMemcpyAsync(dd.p, circuit_digest, 32, hipMemcpyHostToDevice, c->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(dp.p, pi_hash, 32, hipMemcpyHostToDevice, c->stream);
   if (e != hipSuccess) return fail("pcs_prove setup: %s", hipGetErrorString(e));
   rc = mp2g_prover_set_preprocessed_dev(pr, dv[0].p);
   if (!rc) rc = mp2g_prover_prove_dev(pr, dptr, dd.p, dp.p, dcaps.p, dopen.p, dproof.p);
   if (!rc) {
-    e = hipMemcpyAsync(caps, dcaps.p, P.n_oracles * pr->capw * sizeof(u64), hipMemcpyDeviceToHost, c->stream);
+    e = hipMemcpyAsync(caps, dcaps.p, P.n_oracles * pr->L.capw * sizeof(u64), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(openings, dopen.p, pr->n_open * 2 * sizeof(u64), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(proof, dproof.p, pr->proof_words * sizeof(u64), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(proof, dproof.p, pr->L.proof_words * sizeof(u64), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) rc = fail("pcs_prove copy-out: %s", hipGetErrorString(e));
   }

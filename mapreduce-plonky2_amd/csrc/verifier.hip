@@ -30,11 +30,8 @@
 
 using namespace mp2g;
 
-#define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fail("%s: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
-#define NEED(c, msg) do { if (!(c)) return fail("invalid argument: %s", msg); } while (0)
 
 #define V_MAX_LINE_POINTS 32
-#define V_MAX_PATHS 16
 #define V_NO_FAIL 0xFFFFFFFFu
 
 namespace {
@@ -44,17 +41,12 @@ struct Parts {
   u64 s[4];
   u32 n[4];
 };
-// everything the kernels need of the circuit, by value
+// what the kernels need of the circuit beside the layouts (layout.h), by value: the FRI scalars and the PLONK-identity numbers
 struct VShape {
-  u32 log_n, lg, cap_h, capw, n_oracles, n_layers, num_queries, pow_bits;
-  u32 oracle_w[8], arity_bits[8];
-  u32 zs_oracle, nc, nlp, n_open;
-  u32 q_off, q_words, final_off, final_len;
-  // Merkle paths of a query: the initial oracles, then the layers
-  u32 n_paths, leaf_off[V_MAX_PATHS], leaf_len[V_MAX_PATHS], n_sib[V_MAX_PATHS], x_shift[V_MAX_PATHS];
-  // PLONK identity
+  u32 log_n, n_oracles, n_layers, num_queries, pow_bits;
+  u32 arity_bits[8];
+  u32 nc, nlp;
   u32 num_routed, degree, num_constants, num_selectors, max_j, T;
-  u32 has_lookup, n_luts, num_lut_slots, num_lu_slots, num_sldc, lu_degree, lut_degree;
 };
 
 __device__ __forceinline__ gl2 open_at(const u64* op, u32 i) { return gl2_make(op[2 * i], op[2 * i + 1]); }
@@ -93,34 +85,33 @@ __global__ void verifier_pi_hash_kernel(Parts pt, u32 n_pi, int given, u32 B, co
 
 // ---- PLONK identity ---------------------------------------------------------------------------------
 // lc [B][num_constants][T], lw [B][wires_w][T]: opening a + X b at the base points a + t b
-__global__ void __launch_bounds__(256) verifier_line_kernel(VShape sh, Parts pt, u32 B, const u32* __restrict__ status,
+__global__ void __launch_bounds__(256) verifier_line_kernel(VShape sh, OpeningLayout ol, Parts pt, u32 B, const u32* __restrict__ status,
                                                             u64* __restrict__ lc, u64* __restrict__ lw) {
-  const u32 per = (sh.num_constants + sh.oracle_w[1]) * sh.T;
+  const u32 wires_w = ol.oracle[1].len, per = (sh.num_constants + wires_w) * sh.T;
   const u32 idx = blockIdx.x * 256 + threadIdx.x;
   if (idx >= B * per) return;
   const u32 b = idx / per, r = idx % per, j = r / sh.T, t = r % sh.T;
   u64 v = 0;
   if (!status[b]) {
     const u64* op = pt.p[2] + b * pt.s[2];
-    const u32 o = j < sh.num_constants ? j : sh.oracle_w[0] + (j - sh.num_constants);
+    const u32 o = j < sh.num_constants ? ol.constants + j : ol.oracle[1].off + (j - sh.num_constants);
     v = gl_mul_add(op[2 * o + 1], t, op[2 * o]);
   }
   if (j < sh.num_constants) lc[((u64)b * sh.num_constants + j) * sh.T + t] = v;
-  else lw[((u64)b * sh.oracle_w[1] + (j - sh.num_constants)) * sh.T + t] = v;
+  else lw[((u64)b * wires_w + (j - sh.num_constants)) * sh.T + t] = v;
 }
 
 // One proof per thread: every term of the vanishing polynomial at zeta in the order of eval_vanishing_poly, accumulated into
 // sum_i term_i alpha_a^i for both challenges at once (the alphas are base-field elements).
-__global__ void __launch_bounds__(64) verifier_identity_kernel(VShape sh, Parts pt, u32 B, const u64* __restrict__ bg,
+__global__ void __launch_bounds__(64) verifier_identity_kernel(VShape sh, OpeningLayout ol, LookupGeometry lu, Parts pt, u32 B,
+                                                               const u64* __restrict__ bg,
                                                                const u64* __restrict__ alphas, const u64* __restrict__ zetas,
                                                                const u64* __restrict__ lut_eval, const u64* __restrict__ gate_vals,
                                                                const u64* __restrict__ interp, u32* __restrict__ status) {
   const u32 b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B || status[b]) return;
   const u64* op = pt.p[2] + b * pt.s[2];
-  const u32 nc = sh.nc, chunks = sh.num_routed / sh.degree, num_prods = chunks - 1, L = nc * sh.nlp;
-  const u32 o_sig = sh.num_constants, o_w = sh.oracle_w[0], o_z = o_w + sh.oracle_w[1];
-  const u32 o_q = o_z + sh.oracle_w[2] - L, o_lu = o_q + sh.oracle_w[3], o_next = o_lu + L, o_lu_next = o_next + nc;
+  const u32 nc = sh.nc, chunks = sh.num_routed / sh.degree, num_prods = chunks - 1;
   const u64* betas = bg + 8 * b;
   const u64* gammas = betas + nc;
   const gl2 zeta = gl2_make(zetas[2 * b], zetas[2 * b + 1]);
@@ -137,33 +128,33 @@ __global__ void __launch_bounds__(64) verifier_identity_kernel(VShape sh, Parts 
       apow[a] = gl_mul(apow[a], al[a]);
     }
   };
-  for (u32 c = 0; c < nc; c++) term(gl2_mul(l0, gl2_sub(open_at(op, o_z + c), gl2_from(1))));
+  for (u32 c = 0; c < nc; c++) term(gl2_mul(l0, gl2_sub(open_at(op, ol.zs + c), gl2_from(1))));
   for (u32 c = 0; c < nc; c++) {
     u64 kj = 1;
     for (u32 ch = 0; ch < chunks; ch++) {
       gl2 num = gl2_from(1), den = gl2_from(1);
       for (u32 j = ch * sh.degree; j < (ch + 1) * sh.degree; j++) {
-        const gl2 wv = open_at(op, o_w + j);
+        const gl2 wv = open_at(op, ol.wires + j);
         num = gl2_mul(num, gl2_add(gl2_add(wv, gl2_scale(zeta, gl_mul(betas[c], kj))), gl2_from(gammas[c])));
-        den = gl2_mul(den, gl2_add(gl2_add(wv, gl2_scale(open_at(op, o_sig + j), betas[c])), gl2_from(gammas[c])));
+        den = gl2_mul(den, gl2_add(gl2_add(wv, gl2_scale(open_at(op, ol.sigmas + j), betas[c])), gl2_from(gammas[c])));
         kj = gl_mul(kj, GL_MULT_GEN);
       }
-      const gl2 prev = ch == 0 ? open_at(op, o_z + c) : open_at(op, o_z + nc + c * num_prods + ch - 1);
-      const gl2 next = ch == chunks - 1 ? open_at(op, o_next + c) : open_at(op, o_z + nc + c * num_prods + ch);
+      const gl2 prev = ch == 0 ? open_at(op, ol.zs + c) : open_at(op, ol.partial_products + c * num_prods + ch - 1);
+      const gl2 next = ch == chunks - 1 ? open_at(op, ol.zs_next + c) : open_at(op, ol.partial_products + c * num_prods + ch);
       term(gl2_sub(gl2_mul(prev, num), gl2_mul(next, den)));
     }
   }
-  if (sh.has_lookup) {
+  if (lu.n_luts) {
     // vanishing_poly.rs check_lookup_constraints per round: sel = TransSre, TransLdc, InitSre, LastLdc, ends per table; zs[0] = RE,
     // zs[1..] the partial Sum / LDC polynomials; deltas = A, B, alpha, delta
-    const u32 ns = sh.num_sldc, nlp = sh.nlp;
+    const u32 ns = lu.num_sldc, nlp = sh.nlp;
     auto sel = [&](u32 i) { return open_at(op, sh.num_selectors + i); };
-    auto wire = [&](u32 i) { return open_at(op, o_w + i); };
+    auto wire = [&](u32 i) { return open_at(op, ol.wires + i); };
     for (u32 c = 0; c < nc; c++) {
       const u64* d = bg + 8 * b + 4 * c;
       const u64 dA = d[0], dB = d[1], dAl = d[2], dDe = d[3];
-      auto zs = [&](u32 q) { return open_at(op, o_lu + c * nlp + q); };
-      auto zsn = [&](u32 q) { return open_at(op, o_lu_next + c * nlp + q); };
+      auto zs = [&](u32 q) { return open_at(op, ol.lookup + c * nlp + q); };
+      auto zsn = [&](u32 q) { return open_at(op, ol.lookup_next + c * nlp + q); };
       auto combo = [&](u32 i, u32 stride) {  // alpha - (inp + A out)
         const gl2 x = gl2_add(wire(stride * i), gl2_scale(wire(stride * i + 1), dA));
         return gl2_make(gl_sub(dAl, x.a), gl_neg(x.b));
@@ -171,16 +162,16 @@ __global__ void __launch_bounds__(64) verifier_identity_kernel(VShape sh, Parts 
       term(gl2_mul(sel(3), zs(ns)));
       term(gl2_mul(sel(2), zs(1)));
       term(gl2_mul(sel(2), zs(0)));
-      for (u32 r = 0; r < sh.n_luts; r++)
+      for (u32 r = 0; r < lu.n_luts; r++)
         term(gl2_mul(sel(4 + r), gl2_sub(zs(0), gl2_from(lut_eval[((u64)b * nc + c) * MP2G_MAX_LUTS + r]))));
       gl2 cur = zsn(0);
-      for (u32 s = 0; s < sh.num_lut_slots; s++)
+      for (u32 s = 0; s < lu.num_lut_slots; s++)
         cur = gl2_add(gl2_scale(cur, dDe), gl2_add(wire(3 * s), gl2_scale(wire(3 * s + 1), dB)));
       term(gl2_mul(sel(0), gl2_sub(zs(0), cur)));
       for (u32 poly = 0; poly < ns; poly++) {
-        u32 t0 = poly * sh.lut_degree, t1 = t0 + sh.lut_degree < sh.num_lut_slots ? t0 + sh.lut_degree : sh.num_lut_slots;
-        const u32 u0 = poly * sh.lu_degree, u1 = u0 + sh.lu_degree < sh.num_lu_slots ? u0 + sh.lu_degree : sh.num_lu_slots;
-        if (t0 > sh.num_lut_slots) t0 = t1 = sh.num_lut_slots;
+        u32 t0 = poly * lu.lut_degree, t1 = t0 + lu.lut_degree < lu.num_lut_slots ? t0 + lu.lut_degree : lu.num_lut_slots;
+        const u32 u0 = poly * lu.lu_degree, u1 = u0 + lu.lu_degree < lu.num_lu_slots ? u0 + lu.lu_degree : lu.num_lu_slots;
+        if (t0 > lu.num_lut_slots) t0 = t1 = lu.num_lut_slots;
         gl2 lut_prod = gl2_from(1), lut_sum = gl2_from(0), lu_prod = gl2_from(1), lu_sum = gl2_from(0);
         for (u32 i = t0; i < t1; i++) lut_prod = gl2_mul(lut_prod, combo(i, 3));
         for (u32 i = t0; i < t1; i++) {
@@ -216,13 +207,13 @@ __global__ void __launch_bounds__(64) verifier_identity_kernel(VShape sh, Parts 
   }
   for (u32 a = 0; a < nc; a++) {
     gl2 tz = gl2_from(0);
-    for (u32 i = 8; i-- > 0;) tz = gl2_add(gl2_mul(tz, zn), open_at(op, o_q + a * 8 + i));
+    for (u32 i = 8; i-- > 0;) tz = gl2_add(gl2_mul(tz, zn), open_at(op, ol.quotient + a * 8 + i));
     if (!gl2_same(van[a], gl2_mul(zh, tz))) { status[b] = 10 + a; return; }
   }
 }
 
 // ---- proof of work, reduced openings ---------------------------------------------------------------
-__global__ void __launch_bounds__(64) verifier_pow_kernel(VShape sh, Parts pt, u32 B, const u64* __restrict__ pow_resp,
+__global__ void __launch_bounds__(64) verifier_pow_kernel(VShape sh, OpeningLayout ol, Parts pt, u32 B, const u64* __restrict__ pow_resp,
                                                           const u64* __restrict__ fri_alpha, u32* __restrict__ status,
                                                           u64* __restrict__ red) {
   const u32 b = blockIdx.x * blockDim.x + threadIdx.x;
@@ -230,12 +221,11 @@ __global__ void __launch_bounds__(64) verifier_pow_kernel(VShape sh, Parts pt, u
   if (sh.pow_bits && (pow_resp[b] >> (64 - sh.pow_bits)) != 0) { status[b] = 1; return; }
   const u64* op = pt.p[2] + b * pt.s[2];
   const gl2 alpha = gl2_make(fri_alpha[2 * b], fri_alpha[2 * b + 1]);
-  const u32 n_zeta = sh.oracle_w[0] + sh.oracle_w[1] + sh.oracle_w[2] + sh.oracle_w[3];
   gl2 acc = gl2_from(0);
-  for (u32 i = n_zeta; i-- > 0;) acc = gl2_add(gl2_mul(acc, alpha), open_at(op, i));
+  for (u32 i = ol.n_zeta; i-- > 0;) acc = gl2_add(gl2_mul(acc, alpha), open_at(op, i));
   red[4 * b] = acc.a; red[4 * b + 1] = acc.b;
   acc = gl2_from(0);
-  for (u32 i = sh.n_open; i-- > n_zeta;) acc = gl2_add(gl2_mul(acc, alpha), open_at(op, i));
+  for (u32 i = ol.n_open; i-- > ol.n_zeta;) acc = gl2_add(gl2_mul(acc, alpha), open_at(op, i));
   red[4 * b + 2] = acc.a; red[4 * b + 3] = acc.b;
 }
 
@@ -248,19 +238,19 @@ __device__ __forceinline__ void query_fail(u32* qstat, u32 b, u32 q, u32 pos, u3
 // One Merkle path per thread (merkle_proofs.rs verify_merkle_proof_to_cap; the leaf through hash_or_noop). Threads are ordered path-
 // kind major so that a wave's lanes hash leaves of one width and climb paths of one length.
 template <int V>
-__global__ void __launch_bounds__(256) verifier_paths_kernel(VShape sh, Parts pt, u32 B, const u64* __restrict__ cap0,
+__global__ void __launch_bounds__(256) verifier_paths_kernel(FriProofLayout L, VShape sh, Parts pt, u32 B, const u64* __restrict__ cap0,
                                                              const u64* __restrict__ qchal, const u32* __restrict__ status,
                                                              u32* __restrict__ qstat) {
   const u32 idx = blockIdx.x * 256 + threadIdx.x, per = B * sh.num_queries;
-  if (idx >= per * sh.n_paths) return;
+  if (idx >= per * L.n_paths) return;
   const u32 p = idx / per, r = idx % per, b = r / sh.num_queries, q = r % sh.num_queries;
   if (status[b]) return;
   const u64* proof = pt.p[3] + b * pt.s[3];
-  const u64* leaf = proof + sh.q_off + (u64)q * sh.q_words + sh.leaf_off[p];
-  const u32 len = sh.leaf_len[p];
+  const u64* leaf = proof + L.q_off + (u64)q * L.q_words + L.leaf_off[p];
+  const u32 len = L.leaf_len[p];
   const u64* sib = leaf + len;
-  u32 x = (u32)(qchal[(u64)b * sh.num_queries + q] & (((u64)1 << sh.lg) - 1)) >> sh.x_shift[p];
-  const u64* cap = p == 0 ? cap0 : p < sh.n_oracles ? pt.p[1] + b * pt.s[1] + (u64)(p - 1) * sh.capw : proof + (u64)(p - sh.n_oracles) * sh.capw;
+  u32 x = (u32)(qchal[(u64)b * sh.num_queries + q] & (((u64)1 << L.lg) - 1)) >> L.x_shift[p];
+  const u64* cap = p == 0 ? cap0 : p < sh.n_oracles ? pt.p[1] + b * pt.s[1] + (u64)(p - 1) * L.capw : proof + (u64)(p - sh.n_oracles) * L.capw;
   u64 s[12];
 #pragma unroll
   for (int i = 0; i < 12; i++) s[i] = 0;
@@ -280,7 +270,7 @@ __global__ void __launch_bounds__(256) verifier_paths_kernel(VShape sh, Parts pt
       perm<V>(s);
     }
   }
-  for (u32 i = 0; i < sh.n_sib[p]; i++) {
+  for (u32 i = 0; i < L.n_sib[p]; i++) {
     const u64* sb = sib + 4 * i;
     const bool right = x & 1;
 #pragma unroll
@@ -301,7 +291,7 @@ __global__ void __launch_bounds__(256) verifier_paths_kernel(VShape sh, Parts pt
 }
 
 // One query per thread: the field arithmetic of fri_verifier_query_round (no hashing here)
-__global__ void __launch_bounds__(64) verifier_fold_kernel(VShape sh, FriShape fs, Parts pt, u32 B, const u64* __restrict__ qchal,
+__global__ void __launch_bounds__(64) verifier_fold_kernel(VShape sh, FriShape fs, FriProofLayout L, Parts pt, u32 B, const u64* __restrict__ qchal,
                                                            const u64* __restrict__ zetas, const u64* __restrict__ fri_alpha,
                                                            const u64* __restrict__ fri_betas, const u64* __restrict__ red,
                                                            const u32* __restrict__ status, u32* __restrict__ qstat) {
@@ -310,12 +300,13 @@ __global__ void __launch_bounds__(64) verifier_fold_kernel(VShape sh, FriShape f
   const u32 b = idx / sh.num_queries, q = idx % sh.num_queries;
   if (status[b]) return;
   const u64* proof = pt.p[3] + b * pt.s[3];
-  const u64* qw = proof + sh.q_off + (u64)q * sh.q_words;
-  u32 x = (u32)(qchal[(u64)b * sh.num_queries + q] & (((u64)1 << sh.lg) - 1));
+  const u64* qw = proof + L.q_off + (u64)q * L.q_words;
+  const u32 lg = fs.log_n + fs.rate_bits;
+  u32 x = (u32)(qchal[(u64)b * sh.num_queries + q] & (((u64)1 << lg) - 1));
   const gl2 alpha = gl2_make(fri_alpha[2 * b], fri_alpha[2 * b + 1]);
   const gl2 zeta = gl2_make(zetas[2 * b], zetas[2 * b + 1]);
-  const gl2 g_zeta = gl2_scale(zeta, gl_root_of_unity(sh.log_n));
-  u64 sx = gl_mul(GL_MULT_GEN, gl_pow(gl_root_of_unity(sh.lg), bitrev32(x, sh.lg)));
+  const gl2 g_zeta = gl2_scale(zeta, gl_root_of_unity(fs.log_n));
+  u64 sx = gl_mul(GL_MULT_GEN, gl_pow(gl_root_of_unity(lg), bitrev32(x, lg)));
   // fri_combine_initial
   gl2 sum = gl2_from(0);
   for (u32 batch = 0; batch < 2; batch++) {
@@ -325,7 +316,7 @@ __global__ void __launch_bounds__(64) verifier_fold_kernel(VShape sh, FriShape f
       u32 o, p;
       fri_batch_poly(fs, batch, j, o, p);
       acc = gl2_mul(acc, alpha);
-      acc.a = gl_add(acc.a, qw[sh.leaf_off[o] + p]);
+      acc.a = gl_add(acc.a, qw[L.leaf_off[o] + p]);
     }
     const gl2 num = gl2_sub(acc, gl2_make(red[4 * b + 2 * batch], red[4 * b + 2 * batch + 1]));
     const gl2 den = gl2_sub(gl2_from(sx), batch == 0 ? zeta : g_zeta);
@@ -336,7 +327,7 @@ __global__ void __launch_bounds__(64) verifier_fold_kernel(VShape sh, FriShape f
   for (u32 li = 0; li < sh.n_layers; li++) {
     const u32 ab = sh.arity_bits[li], arity = 1u << ab;
     const u32 coset = x >> ab, within = x & (arity - 1);
-    const u64* ev = qw + sh.leaf_off[sh.n_oracles + li];
+    const u64* ev = qw + L.leaf_off[fs.n_oracles + li];
     if (ev[2 * within] != old_eval.a || ev[2 * within + 1] != old_eval.b) query_fail(qstat, b, q, 1 + 2 * li, 3);
     // compute_evaluation: the polynomial through (start g^i, ev[bitrev(i)]) at beta. The points are the roots of X^arity - S,
     // S = start^arity, so prod_{j != i} (x_i - x_j) = arity x_i^(arity - 1) = arity S / x_i: one inversion per layer.
@@ -363,9 +354,9 @@ __global__ void __launch_bounds__(64) verifier_fold_kernel(VShape sh, FriShape f
     for (u32 i = 0; i < ab; i++) sx = gl_sqr(sx);
     x = coset;
   }
-  const u64* fin = proof + sh.final_off;
+  const u64* fin = proof + L.final_off;
   gl2 fe = gl2_from(0);
-  for (u32 i = sh.final_len; i-- > 0;) fe = gl2_add(gl2_scale(fe, sx), gl2_make(fin[2 * i], fin[2 * i + 1]));
+  for (u32 i = L.final_len; i-- > 0;) fe = gl2_add(gl2_scale(fe, sx), gl2_make(fin[2 * i], fin[2 * i + 1]));
   if (!gl2_same(fe, old_eval)) query_fail(qstat, b, q, 1 + 2 * sh.n_layers, 5);
 }
 
@@ -376,7 +367,7 @@ __global__ void verifier_status_kernel(u32 B, const u32* __restrict__ qstat, u32
 }
 
 // out[b] = betas[2], gammas[2], alphas[2], zeta[2], lookup challenges[8], FRI alpha[2], FRI betas[n_layers][2], PoW response, indices
-__global__ void verifier_challenges_kernel(VShape sh, u32 B, const u64* bg, const u64* alphas, const u64* zetas, const u64* fri_alpha,
+__global__ void verifier_challenges_kernel(VShape sh, u32 lg, u32 has_lookup, u32 B, const u64* bg, const u64* alphas, const u64* zetas, const u64* fri_alpha,
                                            const u64* fri_betas, const u64* pow_resp, const u64* qchal, u64* out, u32 wpp) {
   const u32 b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
@@ -388,10 +379,10 @@ __global__ void verifier_challenges_kernel(VShape sh, u32 B, const u64* bg, cons
     o[6 + i] = zetas[2 * b + i];
     o[16 + i] = fri_alpha[2 * b + i];
   }
-  for (u32 i = 0; i < 8; i++) o[8 + i] = sh.has_lookup && i < 4 * sh.nc ? bg[8 * b + i] : 0;
+  for (u32 i = 0; i < 8; i++) o[8 + i] = has_lookup && i < 4 * sh.nc ? bg[8 * b + i] : 0;
   for (u32 i = 0; i < 2 * sh.n_layers; i++) o[18 + i] = fri_betas[16 * b + i];
   o[18 + 2 * sh.n_layers] = pow_resp[b];
-  for (u32 i = 0; i < sh.num_queries; i++) o[19 + 2 * sh.n_layers + i] = qchal[(u64)b * sh.num_queries + i] & (((u64)1 << sh.lg) - 1);
+  for (u32 i = 0; i < sh.num_queries; i++) o[19 + 2 * sh.n_layers + i] = qchal[(u64)b * sh.num_queries + i] & (((u64)1 << lg) - 1);
 }
 
 // rows of the map "values of P at t = 0 .. T - 1" -> P(X) mod X^2 - 7: out[t] and out[V_MAX_LINE_POINTS + t]
@@ -431,8 +422,9 @@ struct mp2g_verifier {
   mp2g_fri_params P{};
   uint32_t capacity = 0, n_pi = 0, last_count = 0, wpp = 0;
   bool pi_given = false;
-  size_t proof_words = 0;
-  Parts layout{};  // n[] = the part lengths
+  ProofParts parts{};  // a proof as the verifier takes it: the part lengths, and the offsets in a contiguous proof
+  FriProofLayout fl{};
+  OpeningLayout ol{};
   VShape sh{};
   FriShape fs{};
   GateTable gates{};
@@ -449,17 +441,26 @@ mp2g_ctx* verifier_ctx(const mp2g_verifier* v) { return v ? v->ctx : nullptr; }
 uint32_t verifier_capacity(const mp2g_verifier* v) { return v ? v->capacity : 0; }
 }  // namespace mp2g
 
+// `count` contiguous proofs at d_words (device)
+static Parts contiguous_parts(const mp2g_verifier* v, const u64* d_words) {
+  Parts pt{};
+  for (int k = 0; k < 4; k++) { pt.p[k] = d_words + v->parts.off[k]; pt.s[k] = v->parts.words; pt.n[k] = v->parts.n[k]; }
+  return pt;
+}
+
 static int verify_parts(mp2g_verifier* v, const Parts& pt, uint32_t B, uint32_t* status) {
   mp2g_ctx* c = v->ctx;
   hipStream_t s = c->stream;
   const mp2g_fri_params& P = v->P;
   const VShape& sh = v->sh;
+  const FriProofLayout& L = v->fl;
+  const bool has_lookup = v->lookups.n_luts != 0;
   const int V = (int)P.variant;
   ChState* st = (ChState*)v->ch.p;
   u32* d_status = (u32*)v->status.p;
   u32* d_qstat = (u32*)v->qstat.p;
   u64* chal = v->chal.p;
-  const u32 nch = sh.nc, capw = sh.capw;
+  const u32 nch = sh.nc, capw = L.capw;
   v->last_count = 0;
   CK(hipMemsetAsync(d_status, 0, B * sizeof(u32), s));
   CK(hipMemsetAsync(d_qstat, 0xFF, B * sizeof(u32), s));
@@ -476,37 +477,36 @@ static int verify_parts(mp2g_verifier* v, const Parts& pt, uint32_t B, uint32_t*
   for (u32 o = 1; o < P.n_oracles; o++) {
     u64* dst = o == 1 ? v->bg.p : o == 2 ? v->alphas.p : chal;
     const u64 dst_stride = o == 2 ? 2 : 8;
-    const u32 n_get = o == 1 ? (sh.has_lookup ? 4 : 2) * nch : (o == 2 ? nch : 0);
-    CK(challenger_step(s, V, st, B, pt.p[1] + (u64)(o - 1) * capw, pt.s[1], capw, dst, dst_stride, n_get));
+    CK(challenger_step(s, V, st, B, pt.p[1] + (u64)(o - 1) * capw, pt.s[1], capw, dst, dst_stride, plonk_challenges_after_cap(o, nch, has_lookup)));
   }
   CK(challenger_step(s, V, st, B, chal, 0, 0, v->zeta.p, 2, 2));
-  CK(challenger_step(s, V, st, B, pt.p[2], pt.s[2], 2 * sh.n_open, chal, 8, 0));
+  CK(challenger_step(s, V, st, B, pt.p[2], pt.s[2], pt.n[2], chal, 8, 0));
   CK(challenger_step(s, V, st, B, chal, 0, 0, v->fri_alpha.p, 2, 2));
   for (u32 li = 0; li < P.n_layers; li++)
     CK(challenger_step(s, V, st, B, pt.p[3] + (u64)li * capw, pt.s[3], capw, v->fri_betas.p + 2 * li, 16, 2));
-  CK(challenger_step(s, V, st, B, pt.p[3] + sh.final_off, pt.s[3], 2 * sh.final_len, chal, 8, 0));
-  CK(challenger_step(s, V, st, B, pt.p[3] + sh.final_off + 2 * sh.final_len, pt.s[3], 1, v->pow_resp.p, 1, 1));
+  CK(challenger_step(s, V, st, B, pt.p[3] + L.final_off, pt.s[3], 2 * L.final_len, chal, 8, 0));
+  CK(challenger_step(s, V, st, B, pt.p[3] + L.pow_off, pt.s[3], 1, v->pow_resp.p, 1, 1));
   if (P.num_queries) CK(challenger_step(s, V, st, B, chal, 0, 0, v->qchal.p, P.num_queries, P.num_queries));
   // PLONK identity at zeta
-  if (sh.has_lookup) CK(lookup_table_polys(s, B, v->lookups, v->bg.p, 8, nch, v->lut_eval.p));
+  if (has_lookup) CK(lookup_table_polys(s, B, v->lookups, v->bg.p, 8, nch, v->lut_eval.p));
   if (sh.max_j) {
-    const u32 total = B * (sh.num_constants + sh.oracle_w[1]) * sh.T;
-    hipLaunchKernelGGL(verifier_line_kernel, dim3((total + 255) / 256), dim3(256), 0, s, sh, pt, B, d_status, v->lc.p, v->lw.p);
+    const u32 total = B * (sh.num_constants + P.oracle_w[1]) * sh.T;
+    hipLaunchKernelGGL(verifier_line_kernel, dim3((total + 255) / 256), dim3(256), 0, s, sh, v->ol, pt, B, d_status, v->lc.p, v->lw.p);
     CK(hipGetLastError());
-    CK(gate_constraints_points_batch(s, B, v->gates, v->lc.p, (u64)sh.num_constants * sh.T, v->lw.p, (u64)sh.oracle_w[1] * sh.T, sh.T,
+    CK(gate_constraints_points_batch(s, B, v->gates, v->lc.p, (u64)sh.num_constants * sh.T, v->lw.p, (u64)P.oracle_w[1] * sh.T, sh.T,
                                      sh.max_j, v->pih.p, v->gate_vals.p));
   }
-  hipLaunchKernelGGL(verifier_identity_kernel, dim3((B + 63) / 64), dim3(64), 0, s, sh, pt, B, v->bg.p, v->alphas.p, v->zeta.p,
-                     v->lut_eval.p, v->gate_vals.p, v->interp.p, d_status);
-  hipLaunchKernelGGL(verifier_pow_kernel, dim3((B + 63) / 64), dim3(64), 0, s, sh, pt, B, v->pow_resp.p, v->fri_alpha.p, d_status, v->red.p);
+  hipLaunchKernelGGL(verifier_identity_kernel, dim3((B + 63) / 64), dim3(64), 0, s, sh, v->ol, (LookupGeometry)v->lookups, pt, B, v->bg.p, v->alphas.p,
+                     v->zeta.p, v->lut_eval.p, v->gate_vals.p, v->interp.p, d_status);
+  hipLaunchKernelGGL(verifier_pow_kernel, dim3((B + 63) / 64), dim3(64), 0, s, sh, v->ol, pt, B, v->pow_resp.p, v->fri_alpha.p, d_status, v->red.p);
   CK(hipGetLastError());
   if (P.num_queries) {
-    const u32 n_tasks = B * P.num_queries * sh.n_paths;
+    const u32 n_tasks = B * P.num_queries * L.n_paths;
     if (V == MP2G_POSEIDON2)
-      hipLaunchKernelGGL((verifier_paths_kernel<MP2G_POSEIDON2>), dim3((n_tasks + 255) / 256), dim3(256), 0, s, sh, pt, B, v->cap0.p, v->qchal.p, d_status, d_qstat);
+      hipLaunchKernelGGL((verifier_paths_kernel<MP2G_POSEIDON2>), dim3((n_tasks + 255) / 256), dim3(256), 0, s, L, sh, pt, B, v->cap0.p, v->qchal.p, d_status, d_qstat);
     else
-      hipLaunchKernelGGL((verifier_paths_kernel<MP2G_POSEIDON>), dim3((n_tasks + 255) / 256), dim3(256), 0, s, sh, pt, B, v->cap0.p, v->qchal.p, d_status, d_qstat);
-    hipLaunchKernelGGL(verifier_fold_kernel, dim3((B * P.num_queries + 63) / 64), dim3(64), 0, s, sh, v->fs, pt, B, v->qchal.p, v->zeta.p,
+      hipLaunchKernelGGL((verifier_paths_kernel<MP2G_POSEIDON>), dim3((n_tasks + 255) / 256), dim3(256), 0, s, L, sh, pt, B, v->cap0.p, v->qchal.p, d_status, d_qstat);
+    hipLaunchKernelGGL(verifier_fold_kernel, dim3((B * P.num_queries + 63) / 64), dim3(64), 0, s, sh, v->fs, L, pt, B, v->qchal.p, v->zeta.p,
                        v->fri_alpha.p, v->fri_betas.p, v->red.p, d_status, d_qstat);
     hipLaunchKernelGGL(verifier_status_kernel, dim3((B + 63) / 64), dim3(64), 0, s, B, d_qstat, d_status);
     CK(hipGetLastError());
@@ -521,13 +521,10 @@ namespace mp2g {
 int verifier_verify_gathered(mp2g_verifier* v, const u64* const* d_srcs, uint32_t count, uint32_t* status) {
   NEED(v && d_srcs && status, "verifier / sources / status");
   NEED(count >= 1 && count <= v->capacity, "1 <= count <= the verifier's capacity");
-  if (!v->staging.p) CK(v->staging.alloc((size_t)v->capacity * v->proof_words * sizeof(u64)));
+  if (!v->staging.p) CK(v->staging.alloc((size_t)v->capacity * v->parts.words * sizeof(u64)));
   for (uint32_t i = 0; i < count; i++)
-    CK(hipMemcpyAsync(v->staging.p + (size_t)i * v->proof_words, d_srcs[i], v->proof_words * sizeof(u64), hipMemcpyDeviceToDevice, v->ctx->stream));
-  Parts pt = v->layout;
-  size_t off = 0;
-  for (int k = 0; k < 4; k++) { pt.p[k] = v->staging.p + off; pt.s[k] = v->proof_words; off += pt.n[k]; }
-  return verify_parts(v, pt, count, status);
+    CK(hipMemcpyAsync(v->staging.p + (size_t)i * v->parts.words, d_srcs[i], v->parts.words * sizeof(u64), hipMemcpyDeviceToDevice, v->ctx->stream));
+  return verify_parts(v, contiguous_parts(v, v->staging.p), count, status);
 }
 }  // namespace mp2g
 
@@ -539,8 +536,7 @@ uint32_t mp2g_gate_table_line_points(const mp2g_gate* gates, uint32_t n_gates, u
   for (uint32_t i = 0; i < n_gates; i++) {
     const mp2g_gate& g = gates[i];
     if (g.kind > MP2G_GATE_UNINTERLEAVE_TO_U32 || g.group_end <= g.group_start) return 0;
-    const uint32_t d = gate_degree(g) + (g.group_end - g.group_start - 1) + (num_selectors > 1 ? 1 : 0);
-    if (d > deg) deg = d;
+    deg = std::max(deg, gate_filtered_degree(g, num_selectors));
   }
   return deg + 1;
 }
@@ -555,7 +551,7 @@ int mp2g_verifier_create(mp2g_ctx* c, const mp2g_fri_params* params, const uint6
   NEED(P.n_oracles == 4 && P.zs_oracle == 2, "plonky2's four oracles (constants_sigmas, wires, zs_partial_products, quotient)");
   NEED(P.zs_count >= 1 && P.zs_count <= 2, "1 or 2 challenge rounds");
   NEED(P.log_n + P.rate_bits <= 31, "log_n + rate_bits <= 31");
-  NEED(P.n_oracles + P.n_layers <= V_MAX_PATHS, "n_oracles + n_layers");
+  NEED(P.n_oracles + P.n_layers <= MP2G_MAX_PATHS, "n_oracles + n_layers");
   NEED(degree >= 2 && num_routed >= degree && num_routed % degree == 0 && num_routed <= 256, "num_routed / degree");
   NEED(P.oracle_w[0] > num_routed && P.oracle_w[1] >= num_routed, "oracle widths against num_routed");
   NEED(P.oracle_w[2] == P.zs_count * (num_routed / degree + P.num_lookup_polys), "oracle_w[2] = rounds * (num_routed / degree + num_lookup_polys)");
@@ -571,76 +567,35 @@ int mp2g_verifier_create(mp2g_ctx* c, const mp2g_fri_params* params, const uint6
   v->ctx = c; v->P = P; v->capacity = capacity;
   v->pi_given = n_public_inputs == MP2G_PI_HASH_GIVEN;
   v->n_pi = v->pi_given ? 4 : n_public_inputs;
-  GateTable& t = v->gates;
-  t.n_gates = n_gates; t.num_selectors = num_selectors; t.num_lookup_selectors = n_luts ? 4 + n_luts : 0;
-  for (uint32_t i = 0; i < n_gates; i++) t.g[i] = gates[i];
   VShape& sh = v->sh;
+  const char* msg = gate_table_make(gates, n_gates, num_selectors, n_luts ? 4 + n_luts : 0, num_constants, P.oracle_w[1], v->gates, &sh.max_j);
+  if (msg) return fail("invalid gate table: %s", msg);
   if (n_gates) {
-    const char* msg = gate_table_check(t, num_constants, P.oracle_w[1]);
-    if (msg) return fail("invalid gate table: %s", msg);
     sh.T = mp2g_gate_table_line_points(gates, n_gates, num_selectors);
     NEED(sh.T >= 1 && sh.T <= V_MAX_LINE_POINTS, "the filtered constraints need more than 32 line points");
-    for (uint32_t i = 0; i < n_gates; i++) sh.max_j = std::max(sh.max_j, gate_num_constraints(gates[i]));
   }
-  sh.log_n = P.log_n; sh.lg = P.log_n + P.rate_bits; sh.cap_h = P.cap_height; sh.capw = 4u << P.cap_height;
-  sh.n_oracles = P.n_oracles; sh.n_layers = P.n_layers; sh.num_queries = P.num_queries; sh.pow_bits = P.pow_bits;
-  for (int i = 0; i < 8; i++) { sh.oracle_w[i] = P.oracle_w[i]; sh.arity_bits[i] = P.arity_bits[i]; }
-  sh.zs_oracle = P.zs_oracle; sh.nc = P.zs_count; sh.nlp = P.num_lookup_polys;
-  sh.n_open = (u32)mp2g_fri_n_openings(&P);
+  sh.log_n = P.log_n; sh.n_oracles = P.n_oracles; sh.n_layers = P.n_layers; sh.num_queries = P.num_queries; sh.pow_bits = P.pow_bits;
+  for (int i = 0; i < 8; i++) sh.arity_bits[i] = P.arity_bits[i];
+  sh.nc = P.zs_count; sh.nlp = P.num_lookup_polys;
   sh.num_routed = num_routed; sh.degree = degree; sh.num_constants = num_constants; sh.num_selectors = num_selectors;
-  NEED(num_selectors + t.num_lookup_selectors <= num_constants, "the constants must hold the selectors and the lookup selectors");
-  // query layout (mp2g_fri_proof_words): per oracle leaf + siblings, per layer evals + siblings
-  u32 off = 0, shift = 0, clg = sh.lg;
-  for (u32 o = 0; o < P.n_oracles; o++) {
-    sh.leaf_off[o] = off; sh.leaf_len[o] = P.oracle_w[o]; sh.n_sib[o] = sh.lg - P.cap_height; sh.x_shift[o] = 0;
-    off += P.oracle_w[o] + 4 * (sh.lg - P.cap_height);
-  }
-  u32 fdeg = P.log_n;
-  for (u32 li = 0; li < P.n_layers; li++) {
-    const u32 ab = P.arity_bits[li], p = P.n_oracles + li;
-    clg -= ab; shift += ab; fdeg -= ab;
-    sh.leaf_off[p] = off; sh.leaf_len[p] = 2u << ab; sh.n_sib[p] = clg - P.cap_height; sh.x_shift[p] = shift;
-    off += (2u << ab) + 4 * (clg - P.cap_height);
-  }
-  sh.n_paths = P.n_oracles + P.n_layers;
-  sh.q_words = off; sh.q_off = P.n_layers * sh.capw;
-  sh.final_len = 1u << fdeg; sh.final_off = sh.q_off + P.num_queries * sh.q_words;
-  if ((size_t)sh.final_off + 2 * sh.final_len + 1 != mp2g_fri_proof_words(&P)) return fail("verifier: FRI proof layout mismatch");
-  FriShape& fs = v->fs;
-  fs.log_n = P.log_n; fs.rate_bits = P.rate_bits; fs.cap_h = P.cap_height; fs.n_oracles = P.n_oracles;
-  fs.zs_oracle = P.zs_oracle; fs.zs_count = P.zs_count; fs.lookup_count = P.zs_count * P.num_lookup_polys;
-  for (u32 o = 0; o < P.n_oracles; o++) { fs.o[o].w = P.oracle_w[o]; fs.n_polys += P.oracle_w[o]; }
-  v->layout.n[0] = v->n_pi; v->layout.n[1] = (P.n_oracles - 1) * sh.capw; v->layout.n[2] = 2 * sh.n_open;
-  v->layout.n[3] = (u32)mp2g_fri_proof_words(&P);
-  v->proof_words = (size_t)v->layout.n[0] + v->layout.n[1] + v->layout.n[2] + v->layout.n[3];
+  NEED(num_selectors + v->gates.num_lookup_selectors <= num_constants, "the constants must hold the selectors and the lookup selectors");
+  v->fl = fri_proof_layout(P);
+  NEED(v->fl.proof_words <= 0xFFFFFFFFull, "the FRI proof must be shorter than 2^32 words");
+  v->ol = opening_layout(P, num_constants);
+  v->fs = fri_shape(P);
+  v->parts = proof_parts(P, v->n_pi);
   v->wpp = 19 + 2 * P.n_layers + P.num_queries;
   hipStream_t s = c->stream;
   if (n_luts) {
     LookupDev& L = v->lookups;
-    L.n_luts = n_luts;
-    L.num_lu_slots = num_routed / 2; L.num_lut_slots = num_routed / 3; L.lu_degree = degree - 1;
+    lookup_geometry(num_routed, degree, L);
     NEED(L.num_lut_slots >= 1, "lookup slot geometry");
-    L.num_sldc = (L.num_lu_slots + L.lu_degree - 1) / L.lu_degree;
-    L.lut_degree = (L.num_lut_slots + L.num_sldc - 1) / L.num_sldc;
     NEED(P.num_lookup_polys == L.num_sldc + 1, "params.num_lookup_polys must be ceil((num_routed/2) / (degree-1)) + 1");
     NEED(P.oracle_w[1] >= 3 * L.num_lut_slots && P.oracle_w[1] >= 2 * L.num_lu_slots, "wires against the lookup slots");
-    size_t total = 0;
-    for (uint32_t r = 0; r < n_luts; r++) {
+    for (uint32_t r = 0; r < n_luts; r++)
       NEED(luts[r].table && luts[r].table_len >= 1 && luts[r].table_len <= 65536, "lookup table");
-      total += (size_t)luts[r].table_len * 2;
-    }
-    CK(v->lut_tables.alloc(total * sizeof(uint16_t)));
+    { int rc = lookup_upload(s, luts, n_luts, v->lut_tables, L); if (rc) return rc; }
     CK(v->lut_eval.alloc((size_t)capacity * P.zs_count * MP2G_MAX_LUTS * sizeof(u64)));
-    size_t o = 0;
-    for (uint32_t r = 0; r < n_luts; r++) {
-      const mp2g_lookup& u = luts[r];
-      L.last_lu_row[r] = u.last_lu_row; L.last_lut_row[r] = u.last_lut_row; L.first_lut_row[r] = u.first_lut_row; L.table_len[r] = u.table_len;
-      L.table[r] = (const uint16_t*)v->lut_tables.p + o;
-      CK(hipMemcpyAsync((uint16_t*)v->lut_tables.p + o, u.table, (size_t)u.table_len * 2 * sizeof(uint16_t), hipMemcpyHostToDevice, s));
-      o += (size_t)u.table_len * 2;
-    }
-    sh.has_lookup = 1; sh.n_luts = n_luts; sh.num_lut_slots = L.num_lut_slots; sh.num_lu_slots = L.num_lu_slots;
-    sh.num_sldc = L.num_sldc; sh.lu_degree = L.lu_degree; sh.lut_degree = L.lut_degree;
   } else {
     CK(v->lut_eval.alloc(8));
   }
@@ -648,8 +603,8 @@ int mp2g_verifier_create(mp2g_ctx* c, const mp2g_fri_params* params, const uint6
   if (sh.T) interpolation_rows(sh.T, rows.data());
   CK(v->interp.alloc(rows.size() * sizeof(u64)));
   CK(hipMemcpyAsync(v->interp.p, rows.data(), rows.size() * sizeof(u64), hipMemcpyHostToDevice, s));
-  CK(v->cap0.alloc(sh.capw * sizeof(u64)));
-  CK(hipMemcpyAsync(v->cap0.p, constants_sigmas_cap, sh.capw * sizeof(u64), hipMemcpyHostToDevice, s));
+  CK(v->cap0.alloc(v->fl.capw * sizeof(u64)));
+  CK(hipMemcpyAsync(v->cap0.p, constants_sigmas_cap, v->fl.capw * sizeof(u64), hipMemcpyHostToDevice, s));
   CK(v->digest.alloc(4 * sizeof(u64)));
   CK(hipMemcpyAsync(v->digest.p, circuit_digest, 4 * sizeof(u64), hipMemcpyHostToDevice, s));
   CK(hipStreamSynchronize(s));  // the caller's memory may go away
@@ -680,15 +635,16 @@ int mp2g_verifier_create(mp2g_ctx* c, const mp2g_fri_params* params, const uint6
 
 size_t mp2g_verifier_proof_words(const mp2g_verifier* v, uint32_t part_words[4]) {
   if (!v) return 0;
-  if (part_words) for (int k = 0; k < 4; k++) part_words[k] = v->layout.n[k];
-  return v->proof_words;
+  if (part_words) for (int k = 0; k < 4; k++) part_words[k] = v->parts.n[k];
+  return v->parts.words;
 }
 
 int mp2g_verifier_verify_dev(mp2g_verifier* v, const uint64_t* const d_parts[4], const uint64_t strides[4], uint32_t count, uint32_t* status) {
   NEED(v && d_parts && strides && status, "verifier / parts / strides / status");
   NEED(count >= 1 && count <= v->capacity, "1 <= count <= the verifier's capacity");
-  Parts pt = v->layout;
+  Parts pt{};
   for (int k = 0; k < 4; k++) {
+    pt.n[k] = v->parts.n[k];
     NEED(d_parts[k] || !pt.n[k], "a part is missing");
     NEED(count == 1 || strides[k] >= pt.n[k], "a stride is shorter than its part");
     pt.p[k] = d_parts[k] ? d_parts[k] : v->chal.p;
@@ -700,12 +656,9 @@ int mp2g_verifier_verify_dev(mp2g_verifier* v, const uint64_t* const d_parts[4],
 int mp2g_verifier_verify(mp2g_verifier* v, const uint64_t* words, uint32_t count, uint32_t* status) {
   NEED(v && words && status, "verifier / words / status");
   NEED(count >= 1 && count <= v->capacity, "1 <= count <= the verifier's capacity");
-  if (!v->staging.p) CK(v->staging.alloc((size_t)v->capacity * v->proof_words * sizeof(u64)));
-  CK(hipMemcpyAsync(v->staging.p, words, (size_t)count * v->proof_words * sizeof(u64), hipMemcpyHostToDevice, v->ctx->stream));
-  Parts pt = v->layout;
-  size_t off = 0;
-  for (int k = 0; k < 4; k++) { pt.p[k] = v->staging.p + off; pt.s[k] = v->proof_words; off += pt.n[k]; }
-  return verify_parts(v, pt, count, status);
+  if (!v->staging.p) CK(v->staging.alloc((size_t)v->capacity * v->parts.words * sizeof(u64)));
+  CK(hipMemcpyAsync(v->staging.p, words, (size_t)count * v->parts.words * sizeof(u64), hipMemcpyHostToDevice, v->ctx->stream));
+  return verify_parts(v, contiguous_parts(v, v->staging.p), count, status);
 }
 
 int mp2g_verifier_challenges(mp2g_verifier* v, uint64_t* out, size_t* words_per_proof) {
@@ -716,7 +669,7 @@ int mp2g_verifier_challenges(mp2g_verifier* v, uint64_t* out, size_t* words_per_
   const u32 B = v->last_count;
   hipStream_t s = v->ctx->stream;
   if (!v->chal_out.p) CK(v->chal_out.alloc((size_t)v->capacity * v->wpp * sizeof(u64)));
-  hipLaunchKernelGGL(verifier_challenges_kernel, dim3((B + 63) / 64), dim3(64), 0, s, v->sh, B, v->bg.p, v->alphas.p, v->zeta.p, v->fri_alpha.p,
+  hipLaunchKernelGGL(verifier_challenges_kernel, dim3((B + 63) / 64), dim3(64), 0, s, v->sh, v->fl.lg, v->lookups.n_luts != 0, B, v->bg.p, v->alphas.p, v->zeta.p, v->fri_alpha.p,
                      v->fri_betas.p, v->pow_resp.p, v->qchal.p, v->chal_out.p, v->wpp);
   CK(hipGetLastError());
   CK(hipMemcpyAsync(out, v->chal_out.p, (size_t)B * v->wpp * sizeof(u64), hipMemcpyDeviceToHost, s));

@@ -7,10 +7,10 @@
 // query_round_proofs[{initial_trees_proof{evals_proofs[(Vec<F>, MerkleProof)]}, steps[{evals,
 // merkle_proof}]}], final_poly, pow_witness}}, public_inputs.
 #include "ctx.h"
+#include "layout.h"
 #include <cstring>
 
 using namespace mp2g;
-#define NEED(c, msg) do { if (!(c)) return fail("invalid argument: %s", msg); } while (0)
 
 namespace {
 struct Writer {
@@ -44,84 +44,54 @@ struct Reader {
     if (v != want) ok = false;
   }
 };
-struct Layout {
-  uint32_t lg, depth, n_layers;
-  size_t capw, cap_n, final_len, q_words;
-};
-Layout layout(const mp2g_fri_params* p) {
-  Layout l;
-  l.lg = p->log_n + p->rate_bits;
-  l.depth = l.lg - p->cap_height;
-  l.n_layers = p->n_layers;
-  l.cap_n = (size_t)1 << p->cap_height;
-  l.capw = 4 * l.cap_n;
-  uint32_t deg = p->log_n;
-  for (uint32_t i = 0; i < p->n_layers; i++) deg -= p->arity_bits[i];
-  l.final_len = (size_t)1 << deg;
-  l.q_words = (mp2g_fri_proof_words(p) - p->n_layers * l.capw - 2 * l.final_len - 1) / (p->num_queries ? p->num_queries : 1);
-  return l;
-}
-// walks the structure once; T is Writer (serialize) or Reader (deserialize)
+// walks the structure once; T is Writer (serialize) or Reader (deserialize). The words come from where layout.h puts them; the
+// order they are visited in is serde's
 template <class T, class U64P>
 void walk(T& io, const mp2g_fri_params* p, uint32_t num_constants, U64P caps, U64P openings, U64P fri, U64P pis, uint32_t n_pis,
           void (*vec_len)(T&, uint64_t)) {
-  Layout l = layout(p);
+  const FriProofLayout F = fri_proof_layout(*p);
+  const OpeningLayout O = opening_layout(*p, num_constants);
+  const size_t cap_n = F.capw / 4;
   for (uint32_t o = 1; o < p->n_oracles; o++) {  // wires, zs_partial_products, quotient caps
-    vec_len(io, l.cap_n);
-    io.u64s(caps + o * l.capw, l.capw);
+    vec_len(io, cap_n);
+    io.u64s(caps + o * F.capw, F.capw);
   }
-  // OpeningSet
-  size_t off = 0;
-  auto ext_vec = [&](size_t count) { vec_len(io, count); io.u64s(openings + 2 * off, 2 * count); off += count; };
-  size_t n_zeta = 0;
-  for (uint32_t o = 0; o < p->n_oracles; o++) n_zeta += p->oracle_w[o];
-  // FRI batch order in `openings`: consts+sigmas | wires | zs + partial products | quotient | lookup | zs_next | lookup_next
-  // serde order: constants, plonk_sigmas, wires, plonk_zs, plonk_zs_next, partial_products, quotient_polys, lookup_zs, lookup_zs_next
-  const size_t L = (size_t)p->zs_count * p->num_lookup_polys;
-  size_t o0 = 0, o1 = p->oracle_w[0], o2 = o1 + (p->n_oracles > 1 ? p->oracle_w[1] : 0);
-  size_t o3 = o2 + (p->n_oracles > 2 ? p->oracle_w[2] - L : 0);
-  size_t o_lu = o3 + (p->n_oracles > 3 ? p->oracle_w[3] : 0);
-  (void)o0;
-  off = 0; ext_vec(num_constants);
-  ext_vec(p->oracle_w[0] - num_constants);
-  off = o1; ext_vec(p->n_oracles > 1 ? p->oracle_w[1] : 0);
-  off = o2; ext_vec(p->zs_count);
-  off = n_zeta; ext_vec(p->zs_count);
-  off = o2 + p->zs_count; ext_vec((p->n_oracles > 2 ? p->oracle_w[2] - L : 0) - p->zs_count);
-  off = o3; ext_vec(p->n_oracles > 3 ? p->oracle_w[3] : 0);
-  off = o_lu; ext_vec(L);                  // lookup_zs
-  off = n_zeta + p->zs_count; ext_vec(L);  // lookup_zs_next
+  // OpeningSet: constants, plonk_sigmas, wires, plonk_zs, plonk_zs_next, partial_products, quotient_polys, lookup_zs, lookup_zs_next
+  // (the Z polynomials lead oracle 2: shape_check)
+  auto ext_vec = [&](size_t off, size_t count) { vec_len(io, count); io.u64s(openings + 2 * off, 2 * count); };
+  ext_vec(O.constants, num_constants);
+  ext_vec(O.sigmas, O.oracle[0].len - num_constants);
+  ext_vec(O.oracle[1].off, O.oracle[1].len);
+  ext_vec(O.oracle[2].off, p->zs_count);
+  ext_vec(O.zs_next, p->zs_count);
+  ext_vec(O.oracle[2].off + p->zs_count, O.oracle[2].len - p->zs_count);
+  ext_vec(O.oracle[3].off, O.oracle[3].len);
+  ext_vec(O.lookup, O.n_lookup);
+  ext_vec(O.lookup_next, O.n_lookup);
   // FriProof
-  vec_len(io, l.n_layers);
-  for (uint32_t i = 0; i < l.n_layers; i++) { vec_len(io, l.cap_n); io.u64s(fri + i * l.capw, l.capw); }
+  vec_len(io, p->n_layers);
+  for (uint32_t i = 0; i < p->n_layers; i++) { vec_len(io, cap_n); io.u64s(fri + i * F.capw, F.capw); }
   vec_len(io, p->num_queries);
-  U64P q = fri + l.n_layers * l.capw;
   for (uint32_t r = 0; r < p->num_queries; r++) {
-    U64P o = q + r * l.q_words;
+    U64P q = fri + F.q_off + r * F.q_words;
+    auto path = [&](uint32_t k, size_t leaf_items) {  // (leaf, MerkleProof{siblings})
+      U64P leaf = q + F.leaf_off[k];
+      vec_len(io, leaf_items); io.u64s(leaf, F.leaf_len[k]);
+      vec_len(io, F.n_sib[k]); io.u64s(leaf + F.leaf_len[k], 4 * F.n_sib[k]);
+    };
     vec_len(io, p->n_oracles);
-    for (uint32_t oi = 0; oi < p->n_oracles; oi++) {
-      vec_len(io, p->oracle_w[oi]); io.u64s(o, p->oracle_w[oi]); o += p->oracle_w[oi];
-      vec_len(io, l.depth); io.u64s(o, 4 * l.depth); o += 4 * l.depth;
-    }
-    vec_len(io, l.n_layers);
-    uint32_t clg = l.lg;
-    for (uint32_t i = 0; i < l.n_layers; i++) {
-      size_t a = (size_t)1 << p->arity_bits[i];
-      clg -= p->arity_bits[i];
-      vec_len(io, a); io.u64s(o, 2 * a); o += 2 * a;
-      uint32_t d = clg - p->cap_height;
-      vec_len(io, d); io.u64s(o, 4 * d); o += 4 * d;
-    }
+    for (uint32_t k = 0; k < p->n_oracles; k++) path(k, F.leaf_len[k]);  // an oracle's row: Vec<F>
+    vec_len(io, p->n_layers);
+    for (uint32_t k = p->n_oracles; k < F.n_paths; k++) path(k, F.leaf_len[k] / 2);  // a layer's evaluations: extension elements
   }
-  U64P fin = q + (size_t)p->num_queries * l.q_words;
-  vec_len(io, l.final_len); io.u64s(fin, 2 * l.final_len);
-  io.u64s(fin + 2 * l.final_len, 1);  // pow_witness
+  vec_len(io, F.final_len); io.u64s(fri + F.final_off, 2 * F.final_len);
+  io.u64s(fri + F.pow_off, 1);  // pow_witness
   vec_len(io, n_pis); io.u64s(pis, n_pis);
 }
 void wlen(Writer& w, uint64_t n) { w.len(n); }
 void rlen(Reader& r, uint64_t n) { r.expect_len(n); }
 int shape_check(const mp2g_fri_params* p, uint32_t num_constants) {
-  int rc = params_check(p);  // cap_height / arity / layer bounds: the layout below subtracts them unchecked
+  int rc = params_check(p);  // cap_height / arity / layer bounds: layout.h subtracts them unchecked
   if (rc) return rc;
   NEED(num_constants <= p->oracle_w[0], "num_constants <= oracle_w[0]");
   NEED(p->zs_oracle == 2 || p->zs_count == 0, "wire format expects the Z polynomials in oracle 2");

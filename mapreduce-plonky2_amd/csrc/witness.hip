@@ -23,7 +23,6 @@
 #include <vector>
 
 using namespace mp2g;
-#define NEED(c, msg) do { if (!(c)) return fail("invalid argument: %s", msg); } while (0)
 
 namespace {
 // operand count after the opcode (t = the operands, left = how many words the tape still holds after the opcode); ~0u = malformed.
@@ -520,7 +519,6 @@ int mp2g_witness_program_set_probe(mp2g_witness_program* P, const uint32_t* prob
   P->probe.assign(probe_sids, probe_sids + n_probe);
   return 0;
 }
-#define CKH(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fail("%s: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
 // the program's read-only data on the context's device, uploaded once
 static int witness_dev_data(mp2g_witness_program* P, mp2g_ctx* c, WitnessDev** out) {
   std::lock_guard<std::mutex> g(P->dev_mu);
@@ -562,15 +560,15 @@ int mp2g_witness_program_run_dev(mp2g_witness_program* P, mp2g_ctx* c, const uin
   if (rc) return rc;
   const size_t vals_words = (size_t)batch * P->n_slots, wire_words = (size_t)batch * NUM_WIRES << P->log_n;
   if (c->wit_vals.bytes < vals_words * 8 || c->wit_rows.bytes < wire_words * 8) {
-    CKH(hipStreamSynchronize(c->stream));  // a kernel queued earlier may still use the old buffers
-    if (c->wit_vals.bytes < vals_words * 8) CKH(c->wit_vals.alloc(vals_words * 8));
-    if (c->wit_rows.bytes < wire_words * 8) CKH(c->wit_rows.alloc(wire_words * 8));
+    CK(hipStreamSynchronize(c->stream));  // a kernel queued earlier may still use the old buffers
+    if (c->wit_vals.bytes < vals_words * 8) CK(c->wit_vals.alloc(vals_words * 8));
+    if (c->wit_rows.bytes < wire_words * 8) CK(c->wit_rows.alloc(wire_words * 8));
   }
-  CKH(hipMemsetAsync(c->wit_vals.p, 0, vals_words * 8, c->stream));
-  CKH(hipMemsetAsync(c->wit_rows.p, 0, wire_words * 8, c->stream));
+  CK(hipMemsetAsync(c->wit_vals.p, 0, vals_words * 8, c->stream));
+  CK(hipMemsetAsync(c->wit_rows.p, 0, wire_words * 8, c->stream));
   // the executor fills a row-major staging matrix (one contiguous run of words per gate row); the prover's polynomial-major
   // [batch][135][n] is made from it by the tiled transpose (every word of d_wires is written)
-  CKH(witness_exec_launch(c->stream, *d, P->gf5, (u32)P->level_off.size() - 1, P->n_slots, P->log_n, (u32)P->input_sids.size(), (u32)(P->consts.size() / 2),
+  CK(witness_exec_launch(c->stream, *d, P->gf5, (u32)P->level_off.size() - 1, P->n_slots, P->log_n, (u32)P->input_sids.size(), (u32)(P->consts.size() / 2),
                           (u32)P->probe.size(), (const u64*)d_inputs, batch, c->wit_vals.p, c->wit_rows.p, (u64*)d_probe_out));
   {
     int rc2 = mp2g_wires_from_rows_dev(c, c->wit_rows.p, d_wires, P->log_n, NUM_WIRES, batch);

@@ -16,7 +16,7 @@ children's proofs; recursion.py builds the real verifier circuit for small trees
 """
 import numpy as np
 
-from . import (BatchedProver, CircuitSet, Gate, PI_HASH_GIVEN, POSEIDON2, PolynomialBatch, Verifier, circuit_digest, deserialize_proof_with_vk,
+from . import (BatchedProver, CircuitSet, PI_HASH_GIVEN, POSEIDON2, PolynomialBatch, Verifier, circuit_digest, deserialize_proof_with_vk,
                standard_recursion_params)
 from . import circuits as C
 
@@ -47,8 +47,7 @@ class CircuitProver:
         pr.set_preprocessed(self.d_pre)
         pr.enable_permutation(NUM_ROUTED, 8)
         pr.enable_quotient()
-        pr.set_gates([Gate(g.kind, g.p0, g.p1, g.p2, g.selector_index, g.group_start, g.group_end) for g in ckt.gates],
-                     ckt.num_selectors)
+        pr.set_gates(ckt.gates, ckt.num_selectors)
         if getattr(ckt, "luts", None):
             pr.set_lookups(ckt.luts)
         if witness_check:

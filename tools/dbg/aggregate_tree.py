@@ -23,7 +23,7 @@ def prover(k, B):
         pr = mp2.BatchedProver(cx, fps[k], B)
         pr.set_preprocessed(cx.to_device(ckt.pre))
         pr.enable_permutation(80, 8); pr.enable_quotient()
-        pr.set_gates([mp2.Gate(g.kind, g.p0, g.p1, g.p2, g.selector_index, g.group_start, g.group_end) for g in ckt.gates], ckt.num_selectors)
+        pr.set_gates(ckt.gates, ckt.num_selectors)
         provers[(k, B)] = (pr, cx.to_device(np.stack([ckt.wires] * B)), cx.alloc(B * 4 * 8))
     return provers[(k, B)]
 def prove(k, pis):

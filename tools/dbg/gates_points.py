@@ -17,7 +17,6 @@ ckt = C.build(5, [(C.NOOP, 0, 0, 0), kind], 21)
 npts = 20000
 consts = O.rand_field((ckt.num_constants, npts), 1)
 wires = O.rand_field((C.NUM_WIRES, npts), 2)
-gates = [mp2.Gate(g.kind, g.p0, g.p1, g.p2, g.selector_index, g.group_start, g.group_end) for g in ckt.gates]
-got = mp2.eval_gate_constraints(ctx, gates, ckt.num_selectors, consts, wires, ckt.pi_hash)
+got = mp2.eval_gate_constraints(ctx, ckt.gates, ckt.num_selectors, consts, wires, ckt.pi_hash)
 want = C.eval_on_points(ckt, consts, wires)
 print("match", np.array_equal(got, want))

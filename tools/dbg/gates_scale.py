@@ -17,7 +17,6 @@ k, B = int(sys.argv[1]), int(sys.argv[2])
 kinds = [kk for kk in C.ALL_KINDS if not sys.argv[3:] or kk[0] == 0 or str(kk[0]) in sys.argv[3:]]
 t = time.time(); ckt = C.build(k, kinds, 5); print("build", k, round(time.time() - t, 2), flush=True)
 fp = mp2.standard_recursion_params(k, (ckt.num_constants + 80, 135, 20, 16))
-gates = [mp2.Gate(g.kind, g.p0, g.p1, g.p2, g.selector_index, g.group_start, g.group_end) for g in ckt.gates]
 d_w = ctx.to_device(np.stack([ckt.wires] * B)); d_cd = ctx.to_device(O.rand_field(4, 1)); d_ph = ctx.to_device(np.stack([ckt.pi_hash] * B))
 order = (True, False) if os.environ.get("GATES_FIRST") else (False, True)
 if os.environ.get("STD_TEST_PARAMS"):
@@ -28,7 +27,7 @@ pr = mp2.BatchedProver(ctx, fp, B)
 pr.set_preprocessed(ctx.to_device(ckt.pre))
 pr.enable_permutation(80, 8); pr.enable_quotient()
 for with_gates in order:
-    pr.set_gates(gates if with_gates else [], ckt.num_selectors)
+    pr.set_gates(ckt.gates if with_gates else [], ckt.num_selectors)
     for it in range(2):
         t = time.time(); pr.prove([d_w, None, None], d_cd, d_ph); ctx.sync(); print("gates" if with_gates else "perm", round(time.time() - t, 4), flush=True)
 pr.free()

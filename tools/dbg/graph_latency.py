@@ -14,7 +14,7 @@ fp = mp2.standard_recursion_params(k, (ckt.num_constants + 80, 135, 20, 16))
 pr = mp2.BatchedProver(ctx, fp, B)
 pr.set_preprocessed(ctx.to_device(ckt.pre))
 pr.enable_permutation(80, 8); pr.enable_quotient()
-pr.set_gates([mp2.Gate(g.kind, g.p0, g.p1, g.p2, g.selector_index, g.group_start, g.group_end) for g in ckt.gates], ckt.num_selectors)
+pr.set_gates(ckt.gates, ckt.num_selectors)
 d_w = ctx.to_device(np.stack([ckt.wires] * B)); d_cd = ctx.to_device(O.rand_field(4, 1)); d_ph = ctx.to_device(np.stack([ckt.pi_hash] * B))
 def run(n):
     ts = []
