@@ -25,36 +25,6 @@
 using namespace mp2g;
 
 namespace {
-// operand count after the opcode (t = the operands, left = how many words the tape still holds after the opcode); ~0u = malformed.
-// Variable-length instructions read their counts from their first operands: those are checked to be there before they are read.
-u32 op_len(u64 op, const u64* t, size_t left = ~(size_t)0) {
-  switch (op) {
-    case OP_ARITH: return 8;
-    case OP_ARITH_EXT: return 12;
-    case OP_P2: case OP_POSEIDON: return 1 + 12 + 1 + 12;
-    case OP_BASE_SUM: return 2 + BASE_SUM_LIMBS;
-    case OP_RA: return 3 + 16 + 1;
-    case OP_REDUCING: return 5 + RED_COEFFS + 2;
-    case OP_REDUCING_EXT: return 5 + 2 * RED_EXT_COEFFS + 2;
-    case OP_COSET: return left >= 2 && t[1] <= 5 ? 3 + (2u << t[1]) + 4 : ~0u;
-    case OP_WIRE: return 3;
-    case OP_HINT_DIV_EXT: return 6;
-    case OP_HINT_LO63: case OP_HINT_HI: return 2;
-    case OP_HINT_SPLIT: return 4;  // source slot, bit position, low slot, high slot (split_low_high's LowHighGenerator)
-    case OP_PAR: return left >= 1 && t[0] <= 4096 ? 1 + (u32)t[0] : ~0u;  // section count, then the sections' lengths in words; the sections follow
-    case OP_U32_ARITH: case OP_U32_SUB: return 8;
-    case OP_U32_ADD_MANY: return left >= 4 && t[3] >= 1 && t[3] <= 16 ? 4 + (u32)t[3] + 3 : ~0u;
-    case OP_U32_RANGE_CHECK: return 4;
-    case OP_COMPARISON: return 6;
-    case OP_BASE_SPLIT: return left >= 3 && t[2] >= 1 && t[2] <= 63 ? 4 + (u32)t[2] : ~0u;
-    case OP_MUL_EXT: return 9;
-    case OP_EXP: return left >= 2 && t[1] >= 1 && t[1] <= 66 ? 3 + (u32)t[1] + 1 : ~0u;
-    case OP_QUINTIC_SQRT: return 5 + 5 + 1;
-    case OP_QUINTIC_QUOTIENT: return 5 + 5 + 5;
-    default: return ~0u;
-  }
-}
-
 // Poseidon2 linear layers on canonical values (poseidon.cuh keeps weak forms for the device; the witness wants the
 // intermediate states, canonical, as the gate's wires)
 // circ(2 M4, M4, M4) with M4 = [[5,7,1,3],[4,6,1,1],[1,3,5,7],[1,1,4,6]]: M4 by its addition chain (t0 = x0 + x1, t1 = x2 + x3,
@@ -116,11 +86,12 @@ void exec(const mp2g_witness_program& P, const u64* t, const u64* end, u64* vals
 #define W(col, row) wires[(u64)(col) * cs + (u64)(row) * rs]
   while (t < end) {
     const u64 op = *t++;
+    const u32 oplen = op_shape(op, t, (size_t)(end - t)).len;  // validated at create
     switch (op) {
       case OP_PAR: {
         const u32 ns = (u32)t[0];
         const u64* len = t + 1;
-        const u64* body = t + 1 + ns;
+        const u64* body = t + oplen;
         u64 total = 0;
         for (u32 i = 0; i < ns; i++) total += len[i];
         if (inner <= 1 || ns <= 1) {
@@ -147,28 +118,7 @@ void exec(const mp2g_witness_program& P, const u64* t, const u64* end, u64* vals
           worker();
           for (auto& th : pool) th.join();
         }
-        t = body + total;
-        break;
-      }
-      case OP_WIRE: W(t[1], t[0]) = vals[t[2]]; t += 3; break;
-      case OP_ARITH: {
-        const u64 row = t[0], i = t[1], c0 = t[2], c1 = t[3];
-        const u64 m0 = vals[t[4]], m1 = vals[t[5]], ad = vals[t[6]];
-        const u64 o = gl_add(gl_mul(gl_mul(m0, m1), c0), gl_mul(ad, c1));
-        W(4 * i, row) = m0; W(4 * i + 1, row) = m1; W(4 * i + 2, row) = ad; W(4 * i + 3, row) = o;
-        vals[t[7]] = o;
-        t += 8;
-        break;
-      }
-      case OP_ARITH_EXT: {
-        const u64 row = t[0], i = t[1], c0 = t[2], c1 = t[3];
-        const gl2 m0 = gl2_make(vals[t[4]], vals[t[5]]), m1 = gl2_make(vals[t[6]], vals[t[7]]), ad = gl2_make(vals[t[8]], vals[t[9]]);
-        const gl2 o = gl2_add(gl2_scale(gl2_mul(m0, m1), c0), gl2_scale(ad, c1));
-        const u64 b = 8 * i;
-        W(b, row) = m0.a; W(b + 1, row) = m0.b; W(b + 2, row) = m1.a; W(b + 3, row) = m1.b;
-        W(b + 4, row) = ad.a; W(b + 5, row) = ad.b; W(b + 6, row) = o.a; W(b + 7, row) = o.b;
-        vals[t[10]] = o.a; vals[t[11]] = o.b;
-        t += 12;
+        t += total;  // the sections; the header goes with the other instructions' operands below
         break;
       }
       case OP_P2: {  // Poseidon2Gate: inputs 0..11, outputs 12..23, swap 24, deltas 25..28, S-box inputs 29.., 65.., 87..
@@ -203,7 +153,6 @@ void exec(const mp2g_witness_program& P, const u64* t, const u64* end, u64* vals
           p2_external(s);
         }
         for (int i = 0; i < 12; i++) { W(12 + i, row) = s[i]; vals[t[14 + i]] = s[i]; }
-        t += 26;
         break;
       }
       case OP_POSEIDON: {  // PoseidonGate: the wire layout of the Poseidon2 gate, the original permutation (30 rounds, 4 + 22 + 4)
@@ -231,98 +180,15 @@ void exec(const mp2g_witness_program& P, const u64* t, const u64* end, u64* vals
           poseidon_mds_host(s);
         }
         for (int i = 0; i < 12; i++) { W(12 + i, row) = s[i]; vals[t[14 + i]] = s[i]; }
-        t += 26;
         break;
       }
-      case OP_BASE_SUM: {
-        const u64 row = t[0], x = vals[t[1]];
-        W(0, row) = x;
-        for (u32 i = 0; i < BASE_SUM_LIMBS; i++) { const u64 b = (x >> i) & 1; W(1 + i, row) = b; vals[t[2 + i]] = b; }
-        t += 2 + BASE_SUM_LIMBS;
+      default: {  // every other opcode has one body, shared with the device executor (witness_ops.h, witness_gf5.h)
+        const auto put = [&](u64 col, u64 row, u64 v) { W(col, row) = v; };
+        if (!exec_core_op(op, t, vals, put, &P.dom[0][0], &P.bw[0][0]) && !exec_gate_op(op, t, vals, put) && !exec_gf5_op(op, t, vals)) return;  // refused at create
         break;
       }
-      case OP_RA: {
-        const u64 row = t[0], c = t[1], idx = vals[t[2]];
-        const u32 vs = 1u << RA_BITS, base = (2 + vs) * (u32)c, routed = (2 + vs) * RA_COPIES + 2;
-        W(base, row) = idx;
-        for (u32 i = 0; i < vs; i++) W(base + 2 + i, row) = vals[t[3 + i]];
-        for (u32 i = 0; i < RA_BITS; i++) W(routed + c * RA_BITS + i, row) = (idx >> i) & 1;
-        const u64 o = vals[t[3 + (idx & (vs - 1))]];
-        W(base + 1, row) = o;
-        vals[t[19]] = o;
-        t += 20;
-        break;
-      }
-      case OP_REDUCING: case OP_REDUCING_EXT: {
-        const bool ext = op == OP_REDUCING_EXT;
-        const u32 nc = ext ? RED_EXT_COEFFS : RED_COEFFS, start_accs = 6 + (ext ? 2 * nc : nc);
-        const u64 row = t[0];
-        const gl2 alpha = gl2_make(vals[t[1]], vals[t[2]]);
-        gl2 acc = gl2_make(vals[t[3]], vals[t[4]]);
-        W(2, row) = alpha.a; W(3, row) = alpha.b; W(4, row) = acc.a; W(5, row) = acc.b;
-        for (u32 i = 0; i < nc; i++) {
-          gl2 cf;
-          if (ext) { cf = gl2_make(vals[t[5 + 2 * i]], vals[t[6 + 2 * i]]); W(6 + 2 * i, row) = cf.a; W(7 + 2 * i, row) = cf.b; }
-          else { cf = gl2_make(vals[t[5 + i]], 0); W(6 + i, row) = cf.a; }
-          acc = gl2_add(gl2_mul(acc, alpha), cf);
-          if (i < nc - 1) { W(start_accs + 2 * i, row) = acc.a; W(start_accs + 2 * i + 1, row) = acc.b; }
-        }
-        W(0, row) = acc.a; W(1, row) = acc.b;
-        const u32 o = 5 + (ext ? 2 * nc : nc);
-        vals[t[o]] = acc.a; vals[t[o + 1]] = acc.b;
-        t += o + 2;
-        break;
-      }
-      case OP_COSET: {
-        const u64 row = t[0];
-        const u32 bits = (u32)t[1], npts = 1u << bits;
-        // CosetInterpolationGate::with_max_degree(bits, 8)
-        const u32 nint0 = (npts - 2) / 7, deg = (npts - 2) / (nint0 + 1) + 2, nint = (npts - 2) / (deg - 1);
-        const u32 w_pt = 1 + 2 * npts, w_val = w_pt + 2, w_int = w_val + 2, w_sh = w_int + 4 * nint;
-        const u64 shift = vals[t[2]];
-        W(0, row) = shift;
-        const u64* v = t + 3;
-        for (u32 i = 0; i < 2 * npts; i++) W(1 + i, row) = vals[v[i]];
-        const gl2 pt = gl2_make(vals[v[2 * npts]], vals[v[2 * npts + 1]]);
-        W(w_pt, row) = pt.a; W(w_pt + 1, row) = pt.b;
-        const gl2 sh = gl2_scale(pt, gl_inv(shift));
-        W(w_sh, row) = sh.a; W(w_sh + 1, row) = sh.b;
-        gl2 ev = gl2_make(0, 0), pr = gl2_make(1, 0);
-        u32 start = 0, endi = deg;
-        for (u32 c = 0; c <= nint; c++) {
-          for (u32 i = start; i < endi; i++) {
-            const gl2 val = gl2_scale(gl2_make(vals[v[2 * i]], vals[v[2 * i + 1]]), P.bw[bits][i]);
-            const gl2 term = gl2_make(gl_sub(sh.a, P.dom[bits][i]), sh.b);
-            const gl2 nev = gl2_add(gl2_mul(ev, term), gl2_mul(val, pr));
-            pr = gl2_mul(pr, term);
-            ev = nev;
-          }
-          if (c == nint) break;
-          W(w_int + 2 * c, row) = ev.a; W(w_int + 2 * c + 1, row) = ev.b;
-          W(w_int + 2 * (nint + c), row) = pr.a; W(w_int + 2 * (nint + c) + 1, row) = pr.b;
-          start = 1 + (deg - 1) * (c + 1);
-          endi = start + deg - 1 < npts ? start + deg - 1 : npts;
-        }
-        W(w_val, row) = ev.a; W(w_val + 1, row) = ev.b;
-        vals[v[2 * npts + 2]] = ev.a; vals[v[2 * npts + 3]] = ev.b;
-        t += 3 + 2 * npts + 4;
-        break;
-      }
-      case OP_HINT_DIV_EXT: {
-        const gl2 num = gl2_make(vals[t[0]], vals[t[1]]), den = gl2_make(vals[t[2]], vals[t[3]]);
-        const gl2 q = gl2_mul(num, gl2_inv(den));
-        vals[t[4]] = q.a; vals[t[5]] = q.b;
-        t += 6;
-        break;
-      }
-      case OP_HINT_LO63: vals[t[1]] = vals[t[0]] & (((u64)1 << 63) - 1); t += 2; break;
-      case OP_HINT_HI: vals[t[1]] = vals[t[0]] >> 63; t += 2; break;
-      case OP_HINT_SPLIT: vals[t[2]] = vals[t[0]] & (((u64)1 << t[1]) - 1); vals[t[3]] = vals[t[0]] >> t[1]; t += 4; break;
-      default:  // the leaf-circuit gates (witness_ops.h) and the GF(p^5) hints (witness_gf5.h): shared with the device executor
-        if (!exec_gate_op(op, t, vals, [&](u64 col, u64 row, u64 v) { W(col, row) = v; }) && !exec_gf5_op(op, t, vals)) return;  // validated at create
-        t += op_len(op, t);
-        break;
     }
+    t += oplen;
   }
 #undef W
 }
@@ -366,10 +232,10 @@ static int witness_program_create(const uint64_t* tape, size_t tape_len, uint32_
     const u64 op = *t++;
     if ((op < OP_ARITH || op >= OP_END) && !op_is_gf5(op)) return bad("unknown opcode");
     if (op_is_gf5(op)) P->gf5 = true;
-    if (op == OP_COSET && (t + 2 > end || t[1] < 2 || t[1] > 5)) return bad("CosetInterpolation bits");
-    if (op == OP_PAR && (t + 1 > end || par_end)) return bad("parallel region header / nesting");
-    const u32 len = op_len(op, t, (size_t)(end - t));
-    if (len == ~0u || t + len > end) return bad("truncated instruction");
+    if (op == OP_PAR && par_end) return bad("parallel regions do not nest");
+    const OpShape shape = op_shape(op, t, (size_t)(end - t));
+    const u32 len = shape.len;
+    if (len == ~0u || len > (size_t)(end - t)) return bad("malformed or truncated instruction");
     if (op == OP_PAR) {
       const u64* body = t + len;
       const u64* b = body;
@@ -383,32 +249,29 @@ static int witness_program_create(const uint64_t* tape, size_t tape_len, uint32_
       t += len;
       continue;
     }
-    // operand classes: rows < n; everything else that is not a constant or a small index is a slot
-    u32 first_slot = 0;
+    // what is not shape (witness_ops.h op_shape): rows < n, columns, copy and operation indices within the gate, canonical constants
     switch (op) {
-      case OP_ARITH: case OP_ARITH_EXT: if (t[0] >= n || t[1] >= (op == OP_ARITH ? 20u : 10u) || t[2] >= GL_P || t[3] >= GL_P) return bad("arithmetic operands"); first_slot = 4; break;
-      case OP_P2: case OP_POSEIDON: case OP_BASE_SUM: case OP_REDUCING: case OP_REDUCING_EXT: if (t[0] >= n) return bad("row"); first_slot = 1; break;
-      case OP_RA: if (t[0] >= n || t[1] >= RA_COPIES) return bad("random access operands"); first_slot = 2; break;
-      case OP_COSET: if (t[0] >= n) return bad("row"); first_slot = 2; break;
-      case OP_WIRE: if (t[0] >= n || t[1] >= NUM_WIRES) return bad("wire"); first_slot = 2; break;
-      case OP_HINT_SPLIT: if (t[0] >= n_slots || t[1] < 1 || t[1] > 63) return bad("split hint"); first_slot = 2; break;
-      case OP_U32_ARITH: if (t[0] >= n || t[2] < 1 || t[2] > 3 || t[1] >= t[2]) return bad("U32Arithmetic operands"); first_slot = 3; break;
-      case OP_U32_SUB: if (t[0] >= n || t[2] < 1 || t[2] > 6 || t[1] >= t[2]) return bad("U32Subtraction operands"); first_slot = 3; break;
-      case OP_U32_ADD_MANY: if (t[0] >= n || t[2] < 1 || t[1] >= t[2] || (t[3] + 3 + 18) * t[2] > NUM_WIRES) return bad("U32AddMany operands"); first_slot = 4; break;
-      case OP_U32_RANGE_CHECK: if (t[0] >= n || t[2] < 1 || t[2] > 7 || t[1] >= t[2]) return bad("U32RangeCheck operands"); first_slot = 3; break;
+      case OP_ARITH: case OP_ARITH_EXT: if (t[0] >= n || t[1] >= (op == OP_ARITH ? 20u : 10u) || t[2] >= GL_P || t[3] >= GL_P) return bad("arithmetic operands"); break;
+      case OP_P2: case OP_POSEIDON: case OP_BASE_SUM: case OP_REDUCING: case OP_REDUCING_EXT: case OP_COSET: case OP_EXP: if (t[0] >= n) return bad("row"); break;
+      case OP_RA: if (t[0] >= n || t[1] >= RA_COPIES) return bad("random access operands"); break;
+      case OP_WIRE: if (t[0] >= n || t[1] >= NUM_WIRES) return bad("wire"); break;
+      case OP_HINT_SPLIT: if (t[0] >= n_slots || t[1] < 1 || t[1] > 63) return bad("split hint"); break;
+      case OP_U32_ARITH: if (t[0] >= n || t[2] < 1 || t[2] > 3 || t[1] >= t[2]) return bad("U32Arithmetic operands"); break;
+      case OP_U32_SUB: if (t[0] >= n || t[2] < 1 || t[2] > 6 || t[1] >= t[2]) return bad("U32Subtraction operands"); break;
+      // t[2] is bounded before it is multiplied: the product wraps in 64 bits otherwise (t[3] <= 16 by op_shape)
+      case OP_U32_ADD_MANY: if (t[0] >= n || t[2] < 1 || t[2] > NUM_WIRES || t[1] >= t[2] || (t[3] + 3 + 18) * t[2] > NUM_WIRES) return bad("U32AddMany operands"); break;
+      case OP_U32_RANGE_CHECK: if (t[0] >= n || t[2] < 1 || t[2] > 7 || t[1] >= t[2]) return bad("U32RangeCheck operands"); break;
       case OP_COMPARISON: {
         if (t[0] >= n || t[1] < 1 || t[1] > 63 || t[2] < 1 || t[2] > 16) return bad("Comparison operands");
         const u64 cb = (t[1] + t[2] - 1) / t[2];
         if (4 + 5 * t[2] + cb + 1 > NUM_WIRES) return bad("Comparison operands");
-        first_slot = 3;
         break;
       }
-      case OP_BASE_SPLIT: if (t[0] >= n || t[1] < 1 || t[1] > 2 || t[1] * t[2] > 63) return bad("BaseSplit operands"); first_slot = 3; break;
-      case OP_MUL_EXT: if (t[0] >= n || t[1] >= 13 || t[2] >= GL_P) return bad("MulExtension operands"); first_slot = 3; break;
-      case OP_EXP: if (t[0] >= n) return bad("row"); first_slot = 2; break;
-      default: first_slot = 0; break;
+      case OP_BASE_SPLIT: if (t[0] >= n || t[1] < 1 || t[1] > 2 || t[1] * t[2] > 63) return bad("BaseSplit operands"); break;
+      case OP_MUL_EXT: if (t[0] >= n || t[1] >= 13 || t[2] >= GL_P) return bad("MulExtension operands"); break;
+      default: break;
     }
-    for (u32 i = first_slot; i < len; i++) if (t[i] >= n_slots) return bad("slot out of range");
+    for (u32 i = shape.first_slot; i < len; i++) if (t[i] >= n_slots) return bad("slot out of range");
     t += len;
   }
   for (; par_end && next_boundary < boundaries.size(); next_boundary++)
@@ -437,38 +300,13 @@ static int witness_program_create(const uint64_t* tape, size_t tape_len, uint32_
     for (const u64* q = base; q < end;) {
       const u64 op = *q;
       const u64* a = q + 1;
-      const u32 len = op_len(op, a);
-      if (op == OP_PAR) { q = a + len; continue; }  // the sections follow as ordinary instructions
-      u32 r0 = 0, nr = 0, w0 = 0, nw = 0;
-      switch (op) {
-        case OP_ARITH: r0 = 4; nr = 3; w0 = 7; nw = 1; break;
-        case OP_ARITH_EXT: r0 = 4; nr = 6; w0 = 10; nw = 2; break;
-        case OP_P2: case OP_POSEIDON: r0 = 1; nr = 13; w0 = 14; nw = 12; break;
-        case OP_BASE_SUM: r0 = 1; nr = 1; w0 = 2; nw = BASE_SUM_LIMBS; break;
-        case OP_RA: r0 = 2; nr = 17; w0 = 19; nw = 1; break;
-        case OP_REDUCING: r0 = 1; nr = 4 + RED_COEFFS; w0 = 5 + RED_COEFFS; nw = 2; break;
-        case OP_REDUCING_EXT: r0 = 1; nr = 4 + 2 * RED_EXT_COEFFS; w0 = 5 + 2 * RED_EXT_COEFFS; nw = 2; break;
-        case OP_COSET: r0 = 2; nr = 3 + (2u << a[1]); w0 = 5 + (2u << a[1]); nw = 2; break;
-        case OP_WIRE: r0 = 2; nr = 1; break;
-        case OP_HINT_DIV_EXT: r0 = 0; nr = 4; w0 = 4; nw = 2; break;
-        case OP_HINT_LO63: case OP_HINT_HI: r0 = 0; nr = 1; w0 = 1; nw = 1; break;
-        case OP_HINT_SPLIT: r0 = 0; nr = 1; w0 = 2; nw = 2; break;
-        case OP_U32_ARITH: case OP_U32_SUB: r0 = 3; nr = 3; w0 = 6; nw = 2; break;
-        case OP_U32_ADD_MANY: r0 = 4; nr = (u32)a[3] + 1; w0 = 5 + (u32)a[3]; nw = 2; break;
-        case OP_U32_RANGE_CHECK: r0 = 3; nr = 1; break;
-        case OP_COMPARISON: r0 = 3; nr = 2; w0 = 5; nw = 1; break;
-        case OP_BASE_SPLIT: r0 = 3; nr = 1; w0 = 4; nw = (u32)a[2]; break;
-        case OP_MUL_EXT: r0 = 3; nr = 4; w0 = 7; nw = 2; break;
-        case OP_EXP: r0 = 2; nr = 1 + (u32)a[1]; w0 = 3 + (u32)a[1]; nw = 1; break;
-        case OP_QUINTIC_SQRT: r0 = 0; nr = 5; w0 = 5; nw = 6; break;
-        case OP_QUINTIC_QUOTIENT: r0 = 0; nr = 10; w0 = 10; nw = 5; break;
-        default: break;
-      }
+      const OpShape sh = op_shape(op, a, (size_t)(end - a));
+      if (op == OP_PAR) { q = a + sh.len; continue; }  // the sections follow as ordinary instructions
       u32 l = 0;
-      for (u32 i = 0; i < nr; i++) { const u32 sl = (u32)a[r0 + i]; if (lvl[sl] > l) l = lvl[sl]; was_read[sl] = 1; }
+      for (u32 i = 0; i < sh.nr; i++) { const u32 sl = (u32)a[sh.r0 + i]; if (lvl[sl] > l) l = lvl[sl]; was_read[sl] = 1; }
       l += 1;
-      for (u32 i = 0; i < nw; i++) {
-        const u32 sl = (u32)a[w0 + i];
+      for (u32 i = 0; i < sh.nw; i++) {
+        const u32 sl = (u32)a[sh.w0 + i];
         // a slot written twice, or written after an earlier instruction read it (the host replay saw 0 there): the level
         // schedule would reorder the accesses, so the device replay refuses the program
         if (written[sl] || was_read[sl]) P->ssa = false;
@@ -478,7 +316,7 @@ static int witness_program_create(const uint64_t* tape, size_t tape_len, uint32_
       if ((size_t)(q - base) > 0xFFFFFFFFu) return bad("tape too long");
       ins.push_back({(u32)(q - base), l, (u32)op});
       if (l > max_lvl) max_lvl = l;
-      q = a + len;
+      q = a + sh.len;
     }
     std::stable_sort(ins.begin(), ins.end(), [](const Ins& x, const Ins& y) { return x.lvl != y.lvl ? x.lvl < y.lvl : x.op < y.op; });
     P->sched.resize(ins.size());

@@ -1,14 +1,178 @@
-// The generators of the leaf-circuit gates as witness-tape instructions (include/mp2g.h MP2G_OP_U32_ARITH .. MP2G_OP_EXP): ONE
-// definition for the host replay (witness.hip) and the device replay (witness_dev.hip). Restates the generators registered at
+// What a witness-tape instruction IS (include/mp2g.h enum mp2g_witness_op, enum mp2g_witness_op_gf5), defined ONCE for the host
+// (witness.hip: validation, level schedule, replay) and the device replay (witness_dev.hip): op_shape gives an instruction's length
+// and operand roles, exec_core_op replays the recursion circuits' opcodes (MP2G_OP_ARITH .. MP2G_OP_HINT_SPLIT), exec_gate_op the
+// leaf-circuit gates (MP2G_OP_U32_ARITH .. MP2G_OP_EXP; the GF(p^5) hints are witness_gf5.h). The gate generators restate
 // mp2-common/src/serialization/circuit_data_serialization.rs:186-231 -- [dep] plonky2-u32 gates/{arithmetic_u32, subtraction_u32,
 // add_many_u32, range_check_u32, comparison}.rs, plonky2 gates/{base_sum, multiplication_extension, exponentiation}.rs -- with the
 // wire layouts of the gate evaluators (gates.hip / oracle/gates_body.inc). t = the operands after the opcode, vals = the proof's
-// slot table, put(col, row, value) writes a wire.
+// slot table, put(col, row, value) writes a wire. recursion.py's _OPS is the same table for the Python builder
+// (tests/test_witness_shape_host.py holds the two together).
 #pragma once
 #include "gl.cuh"
 #include "witness.h"
 
 namespace mp2g {
+// len = operands after the opcode (~0u: malformed); the operands [first_slot, len) are slots, the ones before it rows, indices and
+// constants; the instruction reads the slots t[r0 .. r0 + nr) and writes t[w0 .. w0 + nw). OP_PAR has a length only (section count,
+// then the sections' lengths in words; the sections follow as ordinary instructions).
+struct OpShape { u32 len, first_slot, r0, nr, w0, nw; };
+// left = how many words the tape holds after the opcode. The counts of the variable-length instructions are read here and nowhere
+// else, after they are known to be there; the rest of the instruction may still run past the tape (len > left).
+GLHD OpShape op_shape(u64 op, const u64* t, size_t left) {
+  const OpShape malformed = {~0u, 0, 0, 0, 0, 0};
+  switch (op) {
+    case OP_ARITH: return {8, 4, 4, 3, 7, 1};
+    case OP_ARITH_EXT: return {12, 4, 4, 6, 10, 2};
+    case OP_P2: case OP_POSEIDON: return {26, 1, 1, 13, 14, 12};
+    case OP_BASE_SUM: return {2 + BASE_SUM_LIMBS, 1, 1, 1, 2, BASE_SUM_LIMBS};
+    case OP_RA: return {20, 2, 2, 17, 19, 1};
+    case OP_REDUCING: return {5 + RED_COEFFS + 2, 1, 1, 4 + RED_COEFFS, 5 + RED_COEFFS, 2};
+    case OP_REDUCING_EXT: return {5 + 2 * RED_EXT_COEFFS + 2, 1, 1, 4 + 2 * RED_EXT_COEFFS, 5 + 2 * RED_EXT_COEFFS, 2};
+    case OP_COSET: {  // row, bits, shift, 2^bits values, point, result
+      if (left < 2 || t[1] < 2 || t[1] > 5) return malformed;
+      const u32 nv = 2u << t[1];
+      return {3 + nv + 4, 2, 2, 3 + nv, 5 + nv, 2};
+    }
+    case OP_WIRE: return {3, 2, 2, 1, 0, 0};
+    case OP_HINT_DIV_EXT: return {6, 0, 0, 4, 4, 2};
+    case OP_HINT_LO63: case OP_HINT_HI: return {2, 0, 0, 1, 1, 1};
+    case OP_HINT_SPLIT: return {4, 2, 0, 1, 2, 2};  // source slot, bit position, low slot, high slot (split_low_high's LowHighGenerator)
+    case OP_PAR: return left >= 1 && t[0] <= 4096 ? OpShape{1 + (u32)t[0], 0, 0, 0, 0, 0} : malformed;
+    case OP_U32_ARITH: case OP_U32_SUB: return {8, 3, 3, 3, 6, 2};
+    case OP_U32_ADD_MANY: {  // row, operation, operations, addends, the addends, carry in, result, carry out
+      if (left < 4 || t[3] < 1 || t[3] > 16) return malformed;
+      const u32 na = (u32)t[3];
+      return {4 + na + 3, 4, 4, na + 1, 5 + na, 2};
+    }
+    case OP_U32_RANGE_CHECK: return {4, 3, 3, 1, 0, 0};
+    case OP_COMPARISON: return {6, 3, 3, 2, 5, 1};
+    case OP_BASE_SPLIT: return left >= 3 && t[2] >= 1 && t[2] <= 63 ? OpShape{4 + (u32)t[2], 3, 3, 1, 4, (u32)t[2]} : malformed;
+    case OP_MUL_EXT: return {9, 3, 3, 4, 7, 2};
+    case OP_EXP: return left >= 2 && t[1] >= 1 && t[1] <= 66 ? OpShape{3 + (u32)t[1] + 1, 2, 2, 1 + (u32)t[1], 3 + (u32)t[1], 1} : malformed;
+    case OP_QUINTIC_SQRT: return {11, 0, 0, 5, 5, 6};
+    case OP_QUINTIC_QUOTIENT: return {15, 0, 0, 10, 10, 5};
+    default: return malformed;
+  }
+}
+
+// The recursion circuits' opcodes. dom_tab / bw_tab = [6][32] words: the two-adic subgroup of 2^bits points and its barycentric
+// weights in row `bits` (CosetInterpolation). MP2G_OP_P2 and MP2G_OP_POSEIDON are NOT here: their host and device replays are
+// different algorithms, not copies -- the host (witness.hip) runs canonical values through 128-bit linear layers, the device
+// (witness_dev.hip) weak representatives, and for short levels the 16-lane cooperative permutation.
+template <class Put>
+GLHD bool exec_core_op(u64 op, const u64* t, u64* vals, Put put, const u64* dom_tab, const u64* bw_tab) {
+  switch (op) {
+    case OP_WIRE: put(t[1], t[0], vals[t[2]]); return true;
+    case OP_ARITH: {
+      const u64 row = t[0], i = t[1], c0 = t[2], c1 = t[3];
+      const u64 m0 = vals[t[4]], m1 = vals[t[5]], ad = vals[t[6]];
+      const u64 o = gl_add(gl_mul(gl_mul(m0, m1), c0), gl_mul(ad, c1));
+      put(4 * i, row, m0); put(4 * i + 1, row, m1); put(4 * i + 2, row, ad); put(4 * i + 3, row, o);
+      vals[t[7]] = o;
+      return true;
+    }
+    case OP_ARITH_EXT: {
+      const u64 row = t[0], i = t[1], c0 = t[2], c1 = t[3];
+      const gl2 m0 = gl2_make(vals[t[4]], vals[t[5]]), m1 = gl2_make(vals[t[6]], vals[t[7]]), ad = gl2_make(vals[t[8]], vals[t[9]]);
+      const gl2 o = gl2_add(gl2_scale(gl2_mul(m0, m1), c0), gl2_scale(ad, c1));
+      const u64 b = 8 * i;
+      put(b, row, m0.a); put(b + 1, row, m0.b); put(b + 2, row, m1.a); put(b + 3, row, m1.b);
+      put(b + 4, row, ad.a); put(b + 5, row, ad.b); put(b + 6, row, o.a); put(b + 7, row, o.b);
+      vals[t[10]] = o.a; vals[t[11]] = o.b;
+      return true;
+    }
+    case OP_BASE_SUM: {
+      const u64 row = t[0], x = vals[t[1]];
+      put(0, row, x);
+#pragma unroll 1
+      for (u32 i = 0; i < BASE_SUM_LIMBS; i++) { const u64 b = (x >> i) & 1; put(1 + i, row, b); vals[t[2 + i]] = b; }
+      return true;
+    }
+    case OP_RA: {
+      const u64 row = t[0], c = t[1], idx = vals[t[2]];
+      const u32 vs = 1u << RA_BITS, base = (2 + vs) * (u32)c, routed = (2 + vs) * RA_COPIES + 2;
+      put(base, row, idx);
+#pragma unroll 1
+      for (u32 i = 0; i < vs; i++) put(base + 2 + i, row, vals[t[3 + i]]);
+      for (u32 i = 0; i < RA_BITS; i++) put(routed + c * RA_BITS + i, row, (idx >> i) & 1);
+      const u64 o = vals[t[3 + (idx & (vs - 1))]];
+      put(base + 1, row, o);
+      vals[t[19]] = o;
+      return true;
+    }
+    case OP_REDUCING: case OP_REDUCING_EXT: {
+      const bool ext = op == OP_REDUCING_EXT;
+      const u32 nc = ext ? RED_EXT_COEFFS : RED_COEFFS, start_accs = 6 + (ext ? 2 * nc : nc);
+      const u64 row = t[0];
+      const gl2 alpha = gl2_make(vals[t[1]], vals[t[2]]);
+      gl2 acc = gl2_make(vals[t[3]], vals[t[4]]);
+      put(2, row, alpha.a); put(3, row, alpha.b); put(4, row, acc.a); put(5, row, acc.b);
+#pragma unroll 1
+      for (u32 i = 0; i < nc; i++) {
+        gl2 cf;
+        if (ext) { cf = gl2_make(vals[t[5 + 2 * i]], vals[t[6 + 2 * i]]); put(6 + 2 * i, row, cf.a); put(7 + 2 * i, row, cf.b); }
+        else { cf = gl2_make(vals[t[5 + i]], 0); put(6 + i, row, cf.a); }
+        acc = gl2_add(gl2_mul(acc, alpha), cf);
+        if (i < nc - 1) { put(start_accs + 2 * i, row, acc.a); put(start_accs + 2 * i + 1, row, acc.b); }
+      }
+      put(0, row, acc.a); put(1, row, acc.b);
+      const u32 o = 5 + (ext ? 2 * nc : nc);
+      vals[t[o]] = acc.a; vals[t[o + 1]] = acc.b;
+      return true;
+    }
+    case OP_COSET: {
+      const u64 row = t[0];
+      const u32 bits = (u32)t[1], npts = 1u << bits;
+      const u64* dom = dom_tab + 32 * bits;
+      const u64* bw = bw_tab + 32 * bits;
+      // CosetInterpolationGate::with_max_degree(bits, 8)
+      const u32 nint0 = (npts - 2) / 7, deg = (npts - 2) / (nint0 + 1) + 2, nint = (npts - 2) / (deg - 1);
+      const u32 w_pt = 1 + 2 * npts, w_val = w_pt + 2, w_int = w_val + 2, w_sh = w_int + 4 * nint;
+      const u64 shift = vals[t[2]];
+      put(0, row, shift);
+      const u64* v = t + 3;
+#pragma unroll 1
+      for (u32 i = 0; i < 2 * npts; i++) put(1 + i, row, vals[v[i]]);
+      const gl2 pt = gl2_make(vals[v[2 * npts]], vals[v[2 * npts + 1]]);
+      put(w_pt, row, pt.a); put(w_pt + 1, row, pt.b);
+      const gl2 sh = gl2_scale(pt, gl_inv(shift));
+      put(w_sh, row, sh.a); put(w_sh + 1, row, sh.b);
+      gl2 ev = gl2_make(0, 0), pr = gl2_make(1, 0);
+      u32 start = 0, endi = deg;
+#pragma unroll 1
+      for (u32 c = 0; c <= nint; c++) {
+#pragma unroll 1
+        for (u32 i = start; i < endi; i++) {
+          const gl2 val = gl2_scale(gl2_make(vals[v[2 * i]], vals[v[2 * i + 1]]), bw[i]);
+          const gl2 term = gl2_make(gl_sub(sh.a, dom[i]), sh.b);
+          const gl2 nev = gl2_add(gl2_mul(ev, term), gl2_mul(val, pr));
+          pr = gl2_mul(pr, term);
+          ev = nev;
+        }
+        if (c == nint) break;
+        put(w_int + 2 * c, row, ev.a); put(w_int + 2 * c + 1, row, ev.b);
+        put(w_int + 2 * (nint + c), row, pr.a); put(w_int + 2 * (nint + c) + 1, row, pr.b);
+        start = 1 + (deg - 1) * (c + 1);
+        endi = start + deg - 1 < npts ? start + deg - 1 : npts;
+      }
+      put(w_val, row, ev.a); put(w_val + 1, row, ev.b);
+      vals[v[2 * npts + 2]] = ev.a; vals[v[2 * npts + 3]] = ev.b;
+      return true;
+    }
+    case OP_HINT_DIV_EXT: {
+      const gl2 num = gl2_make(vals[t[0]], vals[t[1]]), den = gl2_make(vals[t[2]], vals[t[3]]);
+      const gl2 q = gl2_mul(num, gl2_inv(den));
+      vals[t[4]] = q.a; vals[t[5]] = q.b;
+      return true;
+    }
+    case OP_HINT_LO63: vals[t[1]] = vals[t[0]] & (((u64)1 << 63) - 1); return true;
+    case OP_HINT_HI: vals[t[1]] = vals[t[0]] >> 63; return true;
+    case OP_HINT_SPLIT: vals[t[2]] = vals[t[0]] & (((u64)1 << t[1]) - 1); vals[t[3]] = vals[t[0]] >> t[1]; return true;
+    default: return false;
+  }
+}
+
+// The leaf-circuit gates.
 template <class Put>
 GLHD bool exec_gate_op(u64 op, const u64* t, u64* vals, Put put) {
   switch (op) {

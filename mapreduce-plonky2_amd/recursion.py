@@ -102,92 +102,75 @@ class Row:
         self.wires = [None] * NUM_WIRES
 
 
+def _all_cols(t):
+    return [(t[0], c) for c in range(NUM_WIRES)]
+
+
+def _block(per, limbs):
+    """operation t[1] of t[2] on a row: `per` wires of its own, then its `limbs` range-check limbs after all operations' own wires"""
+    return lambda t: [(t[0], per * t[1] + k) for k in range(per)] + [(t[0], per * t[2] + limbs * t[1] + j) for j in range(limbs)]
+
+
+# What an instruction IS, for the builder (no native library here): csrc/witness_ops.h op_shape is the same table for the executors,
+# and tests/test_witness_shape_host.py holds the two together. Per opcode: (count, shape, cells). shape = (len, r0, nr, w0, nw):
+# len operands follow the opcode, the instruction reads the slots t[r0:r0 + nr] and writes t[w0:w0 + nw]; for a variable-length
+# instruction shape is a function of its count operand t[count]. cells(t) = the (row, column) wire cells it writes (None: OP_PAR,
+# which only brackets the sections that follow it).
+_OPS = {
+    OP_ARITH: (None, (8, 4, 3, 7, 1), lambda t: [(t[0], 4 * t[1] + k) for k in range(4)]),
+    OP_ARITH_EXT: (None, (12, 4, 6, 10, 2), lambda t: [(t[0], 8 * t[1] + k) for k in range(8)]),
+    OP_P2: (None, (26, 1, 13, 14, 12), _all_cols),
+    OP_POSEIDON: (None, (26, 1, 13, 14, 12), _all_cols),
+    OP_BASE_SUM: (None, (2 + 63, 1, 1, 2, 63), lambda t: [(t[0], c) for c in range(64)]),
+    OP_RA: (None, (20, 2, 17, 19, 1), lambda t: [(t[0], 18 * t[1] + k) for k in range(18)] + [(t[0], 18 * 4 + 2 + 4 * t[1] + k) for k in range(4)]),
+    OP_REDUCING: (None, (5 + 43 + 2, 1, 4 + 43, 5 + 43, 2), _all_cols),
+    OP_REDUCING_EXT: (None, (5 + 64 + 2, 1, 4 + 64, 5 + 64, 2), _all_cols),
+    OP_COSET: (1, lambda bits: (3 + (2 << bits) + 4, 2, 3 + (2 << bits), 5 + (2 << bits), 2), _all_cols),
+    OP_WIRE: (None, (3, 2, 1, 0, 0), lambda t: [(t[0], t[1])]),
+    OP_HINT_DIV_EXT: (None, (6, 0, 4, 4, 2), lambda t: []),
+    OP_HINT_LO63: (None, (2, 0, 1, 1, 1), lambda t: []),
+    OP_HINT_HI: (None, (2, 0, 1, 1, 1), lambda t: []),
+    OP_HINT_SPLIT: (None, (4, 0, 1, 2, 2), lambda t: []),
+    OP_PAR: (0, lambda ns: (1 + ns, 0, 0, 0, 0), None),
+    OP_U32_ARITH: (None, (8, 3, 3, 6, 2), _block(6, 32)),
+    OP_U32_SUB: (None, (8, 3, 3, 6, 2), _block(5, 16)),
+    OP_U32_ADD_MANY: (3, lambda na: (4 + na + 3, 4, na + 1, 5 + na, 2), lambda t: _block(t[3] + 3, 18)(t)),
+    OP_U32_RANGE_CHECK: (None, (4, 3, 1, 0, 0), lambda t: [(t[0], t[1])] + [(t[0], t[2] + 16 * t[1] + j) for j in range(16)]),
+    OP_COMPARISON: (None, (6, 3, 2, 5, 1), _all_cols),
+    OP_BASE_SPLIT: (2, lambda nl: (4 + nl, 3, 1, 4, nl), lambda t: [(t[0], c) for c in range(1 + t[2])]),
+    OP_MUL_EXT: (None, (9, 3, 4, 7, 2), lambda t: [(t[0], 6 * t[1] + k) for k in range(6)]),
+    OP_EXP: (1, lambda nb: (3 + nb + 1, 2, 1 + nb, 3 + nb, 1), lambda t: [(t[0], c) for c in range(2 * t[1] + 2)]),
+    gf5.OP_QUINTIC_SQRT: (None, (11, 0, 5, 5, 6), lambda t: []),
+    gf5.OP_QUINTIC_QUOTIENT: (None, (15, 0, 10, 10, 5), lambda t: []),
+}
+
+
+def _op_shape(tape, pos):
+    """(len, r0, nr, w0, nw) of the instruction at tape[pos]"""
+    op = int(tape[pos])
+    if op not in _OPS:
+        raise ValueError(f"opcode {op}")
+    count, shape, _ = _OPS[op]
+    return shape if count is None else shape(int(tape[pos + 1 + count]))
+
+
 def tape_instructions(tape):
-    """(position, opcode) of every instruction of a recorded witness program (the lengths csrc/witness.hip's op_len gives)"""
-    fixed = {OP_ARITH: 8, OP_ARITH_EXT: 12, OP_P2: 26, OP_POSEIDON: 26, OP_BASE_SUM: 2 + 63, OP_RA: 20, OP_REDUCING: 5 + 43 + 2, OP_REDUCING_EXT: 5 + 64 + 2,
-             OP_WIRE: 3, OP_HINT_DIV_EXT: 6, OP_HINT_LO63: 2, OP_HINT_HI: 2, OP_HINT_SPLIT: 4, OP_U32_ARITH: 8, OP_U32_SUB: 8, OP_U32_RANGE_CHECK: 4,
-             OP_COMPARISON: 6, OP_MUL_EXT: 9, gf5.OP_QUINTIC_SQRT: 11, gf5.OP_QUINTIC_QUOTIENT: 15}
+    """(position, opcode) of every instruction of a recorded witness program"""
     t, n = 0, len(tape)
     while t < n:
-        op = int(tape[t])
-        yield t, op
-        if op == OP_COSET:
-            t += 1 + 3 + (2 << int(tape[t + 2])) + 4
-        elif op == OP_PAR:
-            t += 1 + 1 + int(tape[t + 1])
-        elif op == OP_U32_ADD_MANY:
-            t += 1 + 4 + int(tape[t + 4]) + 3
-        elif op == OP_BASE_SPLIT:
-            t += 1 + 4 + int(tape[t + 3])
-        elif op == OP_EXP:
-            t += 1 + 3 + int(tape[t + 2]) + 1
-        else:
-            t += 1 + fixed[op]
+        yield t, int(tape[t])
+        t += 1 + _op_shape(tape, t)[0]
 
 
 def instruction_slots(tape, pos):
     """(slots read, slots written, (row, col) wire cells written, next position) of the instruction at tape[pos] -- the operand roles
-    of csrc/witness.hip's executor"""
-    op = int(tape[pos])
-    need = {OP_ARITH: 8, OP_ARITH_EXT: 12, OP_P2: 26, OP_POSEIDON: 26, OP_BASE_SUM: 65, OP_RA: 20, OP_REDUCING: 50, OP_REDUCING_EXT: 71, OP_WIRE: 3,
-            OP_HINT_DIV_EXT: 6, OP_HINT_LO63: 2, OP_HINT_HI: 2, OP_HINT_SPLIT: 4}.get(op)
-    if need is None and op == OP_COSET:
-        need = 3 + (2 << int(tape[pos + 2])) + 4
-    t = tape[pos + 1:pos + 1 + (need or 0)]
-    if op == OP_ARITH:
-        return t[4:7], [t[7]], [(t[0], 4 * t[1] + k) for k in range(4)], pos + 9
-    if op == OP_ARITH_EXT:
-        return t[4:10], t[10:12], [(t[0], 8 * t[1] + k) for k in range(8)], pos + 13
-    if op in (OP_P2, OP_POSEIDON):
-        return t[1:14], t[14:26], [(t[0], c) for c in range(135)], pos + 27
-    if op == OP_BASE_SUM:
-        return [t[1]], t[2:2 + 63], [(t[0], c) for c in range(64)], pos + 1 + 2 + 63
-    if op == OP_RA:
-        base = (2 + 16) * t[1]
-        return t[2:19], [t[19]], [(t[0], base + k) for k in range(18)] + [(t[0], (2 + 16) * 4 + 2 + 4 * t[1] + k) for k in range(4)], pos + 21
-    if op == OP_REDUCING:
-        return t[1:5 + 43], t[5 + 43:5 + 43 + 2], [(t[0], c) for c in range(135)], pos + 1 + 5 + 43 + 2
-    if op == OP_REDUCING_EXT:
-        return t[1:5 + 64], t[5 + 64:5 + 64 + 2], [(t[0], c) for c in range(135)], pos + 1 + 5 + 64 + 2
-    if op == OP_COSET:
-        npts = 1 << t[1]
-        return t[2:3 + 2 * npts + 2], t[3 + 2 * npts + 2:3 + 2 * npts + 4], [(t[0], c) for c in range(135)], pos + 1 + 3 + 2 * npts + 4
-    if op == OP_WIRE:
-        return [t[2]], [], [(t[0], t[1])], pos + 4
-    if op == OP_HINT_DIV_EXT:
-        return t[0:4], t[4:6], [], pos + 7
-    if op in (OP_HINT_LO63, OP_HINT_HI):
-        return [t[0]], [t[1]], [], pos + 3
-    if op == OP_HINT_SPLIT:
-        return [t[0]], t[2:4], [], pos + 5
-    if op == gf5.OP_QUINTIC_SQRT:
-        t = tape[pos + 1:pos + 12]
-        return t[0:5], t[5:11], [], pos + 12
-    if op == gf5.OP_QUINTIC_QUOTIENT:
-        t = tape[pos + 1:pos + 16]
-        return t[0:10], t[10:15], [], pos + 16
-    t = tape[pos + 1:]
-    if op in (OP_U32_ARITH, OP_U32_SUB):
-        per, limbs = (6, 32) if op == OP_U32_ARITH else (5, 16)
-        row, i, ops = t[0], t[1], t[2]
-        return t[3:6], t[6:8], [(row, per * i + k) for k in range(per)] + [(row, per * ops + limbs * i + j) for j in range(limbs)], pos + 9
-    if op == OP_U32_ADD_MANY:
-        row, i, ops, na = t[0], t[1], t[2], t[3]
-        per = na + 3
-        return t[4:5 + na], t[5 + na:7 + na], [(row, per * i + k) for k in range(per)] + [(row, per * ops + 18 * i + j) for j in range(18)], pos + 1 + 4 + na + 3
-    if op == OP_U32_RANGE_CHECK:
-        row, i, k = t[0], t[1], t[2]
-        return [t[3]], [], [(row, i)] + [(row, k + 16 * i + j) for j in range(16)], pos + 5
-    if op == OP_COMPARISON:
-        return t[3:5], [t[5]], [(t[0], c) for c in range(135)], pos + 7
-    if op == OP_BASE_SPLIT:
-        return [t[3]], t[4:4 + t[2]], [(t[0], c) for c in range(1 + t[2])], pos + 1 + 4 + t[2]
-    if op == OP_MUL_EXT:
-        return t[3:7], t[7:9], [(t[0], 6 * t[1] + k) for k in range(6)], pos + 10
-    if op == OP_EXP:
-        nb = t[1]
-        return t[2:3 + nb], [t[3 + nb]], [(t[0], c) for c in range(2 * nb + 2)], pos + 1 + 3 + nb + 1
-    raise ValueError(f"opcode {op}")
+    of the executors (csrc/witness_ops.h)"""
+    ln, r0, nr, w0, nw = _op_shape(tape, pos)
+    cells = _OPS[int(tape[pos])][2]
+    if cells is None:
+        raise ValueError(f"opcode {int(tape[pos])} has no operand roles")
+    t = tape[pos + 1:pos + 1 + ln]
+    return t[r0:r0 + nr], t[w0:w0 + nw], cells(t), pos + 1 + ln
 
 
 def check_sections_independent(tape, start, lengths):

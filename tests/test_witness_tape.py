@@ -110,6 +110,9 @@ def test_tape_validation_of_the_leaf_gate_opcodes():
     assert create([R.OP_U32_ADD_MANY, 2, 4, 5, 17, 0, 1, 2, 3, 10, 11]) is not None  # 17 addends
     assert create([R.OP_U32_ADD_MANY, 2, 0, 6, 3, 0, 1, 2, 3, 10, 11]) is not None   # (3 + 3 + 18) x 6 wires > 135
     assert create([R.OP_U32_ADD_MANY, 2, 0, 5, 3, 0, 1]) is not None                 # the addend count runs past the tape
+    inv37 = pow(37, -1, 1 << 64)                                                     # (16 + 3 + 18) x inv37 wires = 1 modulo 2^64:
+    assert create([R.OP_U32_ADD_MANY, 2, 1 << 40, inv37, 16] + list(range(17)) + [10, 11]) is not None  # the bound must not wrap
+    assert create([R.OP_U32_ADD_MANY, 2, 0, 136, 1, 0, 1, 10, 11]) is not None       # more operations than a row has wires
     assert create([R.OP_U32_RANGE_CHECK, 0, 6, 7, 1]) is None and create([R.OP_U32_RANGE_CHECK, 0, 7, 7, 1]) is not None
     assert create([R.OP_COMPARISON, 0, 32, 16, 0, 1, 10]) is None
     assert create([R.OP_COMPARISON, 0, 64, 16, 0, 1, 10]) is not None and create([R.OP_COMPARISON, 0, 32, 17, 0, 1, 10]) is not None
@@ -140,8 +143,8 @@ def test_public_header_and_python_agree_on_the_opcodes():
 def test_random_tapes_are_refused_or_replayed_without_harm():
     """the tape indexes host memory (slot table, wire matrix): whatever words a caller hands to mp2g_witness_program_create, the library
     either refuses the tape or replays it inside its buffers. 400 random tapes -- well-formed instructions with operands drawn around
-    their limits (rows, columns, counts, slots one past the end), some truncated -- each created and, if accepted, replayed on the
-    host for two random input vectors into a guarded wire buffer"""
+    their limits (rows, columns, counts, slots one past the end; a count or index now and then 2^40, 2^63 or 2^64 - 1), some truncated --
+    each created and, if accepted, replayed on the host for two random input vectors into a guarded wire buffer"""
     mp2 = importlib.import_module("mapreduce-plonky2_amd")
     lib = mp2.load()
     rng = np.random.default_rng(0xC0FFEE07)
@@ -154,37 +157,43 @@ def test_random_tapes_are_refused_or_replayed_without_harm():
     def row():
         return int(rng.integers(0, n + (1 if rng.random() < 0.05 else 0)))
 
+    def cnt(lo, hi):
+        """a count or index operand: around its limits and, now and then, huge (a bound that multiplies or shifts by it must not wrap)"""
+        if rng.random() < 0.03:
+            return [1 << 40, 1 << 63, (1 << 64) - 1][int(rng.integers(0, 3))]
+        return int(rng.integers(lo, hi))
+
     def instr():
         op = int(rng.integers(1, 25))
         sl = lambda k: [slot() for _ in range(k)]
-        if op == R.OP_ARITH: return [op, row(), int(rng.integers(0, 21)), int(rng.integers(0, P, dtype=np.uint64)), int(rng.integers(0, P, dtype=np.uint64))] + sl(4)
-        if op == R.OP_ARITH_EXT: return [op, row(), int(rng.integers(0, 11)), 1, 2] + sl(8)
+        if op == R.OP_ARITH: return [op, row(), cnt(0, 21), int(rng.integers(0, P, dtype=np.uint64)), int(rng.integers(0, P, dtype=np.uint64))] + sl(4)
+        if op == R.OP_ARITH_EXT: return [op, row(), cnt(0, 11), 1, 2] + sl(8)
         if op in (R.OP_P2, R.OP_POSEIDON): return [op, row()] + sl(25)
         if op == R.OP_BASE_SUM: return [op, row()] + sl(64)
-        if op == R.OP_RA: return [op, row(), int(rng.integers(0, 5))] + sl(18)
+        if op == R.OP_RA: return [op, row(), cnt(0, 5)] + sl(18)
         if op == R.OP_REDUCING: return [op, row()] + sl(4 + 43 + 2)
         if op == R.OP_REDUCING_EXT: return [op, row()] + sl(4 + 64 + 2)
         if op == R.OP_COSET:
-            bits = int(rng.integers(1, 7))
+            bits = cnt(1, 7)
             return [op, row(), bits] + sl(1 + (2 << min(bits, 5)) + 4)
-        if op == R.OP_WIRE: return [op, row(), int(rng.integers(0, 137))] + sl(1)
+        if op == R.OP_WIRE: return [op, row(), cnt(0, 137)] + sl(1)
         if op == R.OP_HINT_DIV_EXT: return [op] + sl(6)
         if op in (R.OP_HINT_LO63, R.OP_HINT_HI): return [op] + sl(2)
-        if op == R.OP_HINT_SPLIT: return [op, slot(), int(rng.integers(0, 66))] + sl(2)
-        if op == R.OP_PAR: return [op, 1, 4, R.OP_HINT_HI, slot(), slot()][:int(rng.integers(3, 7))]
-        if op == R.OP_U32_ARITH: return [op, row(), int(rng.integers(0, 4)), int(rng.integers(0, 5))] + sl(5)
-        if op == R.OP_U32_SUB: return [op, row(), int(rng.integers(0, 7)), int(rng.integers(0, 8))] + sl(5)
+        if op == R.OP_HINT_SPLIT: return [op, slot(), cnt(0, 66)] + sl(2)
+        if op == R.OP_PAR: return [op, cnt(1, 2), 4, R.OP_HINT_HI, slot(), slot()][:int(rng.integers(3, 7))]
+        if op == R.OP_U32_ARITH: return [op, row(), cnt(0, 4), cnt(0, 5)] + sl(5)
+        if op == R.OP_U32_SUB: return [op, row(), cnt(0, 7), cnt(0, 8)] + sl(5)
         if op == R.OP_U32_ADD_MANY:
-            na = int(rng.integers(0, 19))
-            return [op, row(), int(rng.integers(0, 6)), int(rng.integers(0, 7)), na] + sl(min(na, 17) + 3)
-        if op == R.OP_U32_RANGE_CHECK: return [op, row(), int(rng.integers(0, 8)), int(rng.integers(0, 9))] + sl(1)
-        if op == R.OP_COMPARISON: return [op, row(), int(rng.integers(0, 66)), int(rng.integers(0, 19))] + sl(3)
+            na = cnt(0, 19)
+            return [op, row(), cnt(0, 6), cnt(0, 7), na] + sl(min(na, 17) + 3)
+        if op == R.OP_U32_RANGE_CHECK: return [op, row(), cnt(0, 8), cnt(0, 9)] + sl(1)
+        if op == R.OP_COMPARISON: return [op, row(), cnt(0, 66), cnt(0, 19)] + sl(3)
         if op == R.OP_BASE_SPLIT:
-            nl = int(rng.integers(0, 66))
-            return [op, row(), int(rng.integers(0, 4)), nl] + sl(1 + min(nl, 64))
-        if op == R.OP_MUL_EXT: return [op, row(), int(rng.integers(0, 15)), int(rng.integers(0, P, dtype=np.uint64))] + sl(6)
+            nl = cnt(0, 66)
+            return [op, row(), cnt(0, 4), nl] + sl(1 + min(nl, 64))
+        if op == R.OP_MUL_EXT: return [op, row(), cnt(0, 15), int(rng.integers(0, P, dtype=np.uint64))] + sl(6)
         if op == R.OP_EXP:
-            nb = int(rng.integers(0, 69))
+            nb = cnt(0, 69)
             return [op, row(), nb] + sl(1 + min(nb, 67) + 1)
         return [op, 0, 0]  # MP2G_OP_END and beyond: no such opcode
 

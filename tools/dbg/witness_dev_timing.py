@@ -1,4 +1,5 @@
-"""time mp2g_witness_program_run_dev against the host replay for the reduce circuit's base and wrap programs"""
+"""time mp2g_witness_program_run_dev against the host replay for the reduce circuit's base and wrap programs; the device replay is
+timed five times per batch size (all five printed). MP2G_LIB chooses the library: to compare two builds run it for each in turn"""
 import importlib, os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -21,11 +22,13 @@ for B in (1, 8, 32, 128):
     inp = np.tile(row, (B, 1))
     d_in, d_w, d_pr = ctx.to_device(inp), ctx.alloc(B * 135 * n * 8), ctx.alloc(B * prog.probe.size * 8)
     prog.run_dev(ctx, d_in, B, d_w, d_pr); ctx.sync()
-    ctx.timer_start()
-    prog.run_dev(ctx, d_in, B, d_w, d_pr)
-    ms = ctx.timer_stop()
+    ms = []
+    for _ in range(5):
+        ctx.timer_start()
+        prog.run_dev(ctx, d_in, B, d_w, d_pr)
+        ms.append(ctx.timer_stop())
     t0 = time.perf_counter()
-    prog.run(inp, threads=0)
+    prog.run(inp, threads=16)
     host = (time.perf_counter() - t0) * 1e3
-    print(f"B={B}: device {ms:.2f} ms, host ({os.cpu_count()} threads) {host:.1f} ms")
+    print(f"B={B}: device {' '.join(f'{x:.2f}' for x in ms)} ms, host (16 threads) {host:.1f} ms")
     d_in.free(); d_w.free(); d_pr.free()
