@@ -421,9 +421,19 @@ typedef struct {
  * of the preprocessed oracle are then: selectors, the 4 + n_luts lookup selectors (gates/selectors.rs
  * selectors_lookup, selector_ends_lookups), gate constants. Needs mp2g_prover_set_gates (with the LookupGate /
  * LookupTableGate entries), params.num_lookup_polys = ceil((num_routed/2) / (degree-1)) + 1 and
- * oracle_w[2] = zs_count * (num_routed/degree + num_lookup_polys). The multiplicity wires are part of the witness
- * (prove()'s set_lookup_wires fills them on the host). n_luts = 0 removes the argument. */
+ * oracle_w[2] = zs_count * (num_routed/degree + num_lookup_polys). The multiplicity wires are part of the witness:
+ * mp2g_prover_lookup_wires_dev fills them on the device, as do the witness tape's replays for a program that has the
+ * tables (mp2g_witness_program_set_lookups). n_luts = 0 removes the argument. */
 int mp2g_prover_set_lookups(mp2g_prover* pr, const mp2g_lookup* luts, uint32_t n_luts);
+/* prove()'s set_lookup_wires ([dep] plonk/prover.rs) for a batch, in place, stream ordered on the prover's context; needs
+ * mp2g_prover_set_lookups. For hosts that keep plonky2's generators and use only the prover. Per table t: lookup j < n_lookups[t]
+ * sits at row last_lu_row + j / 40, wires 2 (j % 40), + 1 and is READ; every later slot of the table's LookupGate rows is
+ * padding and receives the table's first pair; entry e of the table goes to row first_lut_row - e / 26, wires 3 (e % 26) .. + 2 =
+ * input, output, multiplicity = the number of LookupGate slots of the table (padding included) that hold the entry's pair; the
+ * LookupTableGate slots past the table's end get zeros. No other wire is touched. A slot whose pair is in no entry is not
+ * counted and nothing fails here: that proof fails the lookup argument (witness-check flag 4). Refused: n_lookups[t] above
+ * the table's 40 x rows slots; a table that holds an input twice (set_lookups itself accepts such a table). */
+int mp2g_prover_lookup_wires_dev(mp2g_prover* pr, const uint32_t* n_lookups /* [n_luts] */, uint64_t* d_wires /* [batch][wires_w][n] */, uint32_t batch);
 
 /* The filtered constraints C_j = sum_gates filter_g c_{g,j} at npts arbitrary points (host pointers):
  * consts [num_constants][npts], wires [wires_w][npts], out [max_j][npts] with max_j the largest
@@ -508,8 +518,9 @@ uint32_t mp2g_gate_table_line_points(const mp2g_gate* gates, uint32_t n_gates, u
  * (3) Two instructions must not write the same wire with different values (they may run in either order on the device).
  * (4) MP2G_OP_PAR brackets sections that neither read each other's written slots nor write the same slots or wires.
  *
- * OPCODES come in two blocks: the base set [1, MP2G_OP_END) of enum mp2g_witness_op and the GF(p^5) set [32, MP2G_OP_GF5_END)
- * of enum mp2g_witness_op_gf5; every other value (0, MP2G_OP_END .. 31, MP2G_OP_GF5_END and above) is refused.
+ * OPCODES come in three blocks: the base set [1, MP2G_OP_END) of enum mp2g_witness_op, the GF(p^5) set [32, MP2G_OP_GF5_END)
+ * of enum mp2g_witness_op_gf5 and the lookup set [40, MP2G_OP_LUT_END) of enum mp2g_witness_op_lut; every other value (0,
+ * MP2G_OP_END .. 31, MP2G_OP_GF5_END .. 39, MP2G_OP_LUT_END and above) is refused.
  *
  * What mp2g_witness_program_create VALIDATES (a tape that fails is refused with a message, nothing is run): every opcode
  * is known, no instruction is truncated, every row < 2^log_n, every column < 135, gate-operation indices and counts are in
@@ -615,6 +626,16 @@ enum mp2g_witness_op_gf5 {
   MP2G_OP_QUINTIC_QUOTIENT = 33,
   MP2G_OP_GF5_END = 34 /* one past the last opcode of the GF(p^5) set */
 };
+/* Lookups into the circuit's tables (CircuitBuilder::add_lookup_from_index). A program that holds the opcode needs its tables
+ * (mp2g_witness_program_set_lookups) before it runs. */
+enum mp2g_witness_op_lut {
+  /* LookupGate (40 slots a row) / LookupGenerator: out = the table's output for the input; 0 when the table has no such input
+   * (the pair is then in no table entry: that proof fails the lookup argument in prove(), witness-check flag 4, nothing fails in
+   * the replay).   operands: row (one of the table's LookupGate rows), i (< 40), lut (table index), s_inp, d_out.
+   * wires 2i, 2i+1 = input, output. */
+  MP2G_OP_LOOKUP = 40,
+  MP2G_OP_LUT_END = 41 /* one past the last opcode of the lookup set */
+};
 /* create: the tape is copied. input_sids [n_inputs]: the slots the caller provides per proof, in the order of the proof's input
  * words (a framework circuit: the circuit-set digest, then per verified child its verifier data, public inputs, caps, openings, FRI
  * proof words and set-membership path, then the circuit's own inputs -- recursion.py universal_inputs); const_slots [n_consts][2]:
@@ -623,6 +644,16 @@ typedef struct mp2g_witness_program mp2g_witness_program;
 int mp2g_witness_program_create(const uint64_t* tape, size_t tape_len, uint32_t n_slots, uint32_t log_n, const uint32_t* input_sids,
                                 uint32_t n_inputs, const uint64_t* const_slots, uint32_t n_consts, mp2g_witness_program** out);
 uint32_t mp2g_witness_program_num_inputs(const mp2g_witness_program* p);
+/* The circuit's lookup tables, for a tape with MP2G_OP_LOOKUP (tables and rows as mp2g_prover_set_lookups takes them; copied; call
+ * before the first device run, which uploads them with the program's other data). After the tape, every replay (run, run_rows,
+ * run_dev) then also does prove()'s set_lookup_wires -- the padding of the LookupGate rows, the LookupTableGate rows, the
+ * multiplicities: see mp2g_prover_lookup_wires_dev -- so the wire matrix is complete. run_dev uses that kernel, the host replays a
+ * plain C++ twin of it (bit-identical, no GPU). n_lookups of a table = the number of its MP2G_OP_LOOKUP instructions.
+ * Refused: an instruction that names a table >= n_luts or a row outside that table's LookupGate rows; a table's instructions not
+ * taking the slots 0 .. n_t - 1 of its rows (slot = 40 (row - last_lu_row) + i) exactly once; LookupTableGate rows that are not
+ * ceil(table_len / 26); tables that share rows; a table that holds an input twice. A program with the opcode and no tables is
+ * refused at run. */
+int mp2g_witness_program_set_lookups(mp2g_witness_program* p, const mp2g_lookup* luts, uint32_t n_luts);
 /* The same replay ON THE DEVICE, for a batch of proofs of one circuit, stream ordered on ctx's stream and without a host copy of
  * anything: one block per proof walks the program's dependency levels (csrc/witness_dev.hip). d_inputs [batch][n_inputs] and
  * d_wires [batch][135][2^log_n] (zero-filled here, then written: what mp2g_prover_prove_dev takes as d_values[0]) are device

@@ -517,6 +517,12 @@ class BatchedProver:
         includes the gate constraint terms -- prove() of a circuit built from the supported gates."""
         _ck(load().mp2g_prover_set_gates(self.h, gate_array(gates), len(gates), num_selectors))
 
+    def lookup_wires_dev(self, n_lookups, d_wires, batch):
+        """prove()'s set_lookup_wires on the device, in place on d_wires [batch][wires_w][n] (needs set_lookups): n_lookups[t] =
+        the looked-up slots of table t; the padding, the table rows and the multiplicities are written"""
+        nl = np.ascontiguousarray(n_lookups, dtype=np.uint32)
+        _ck(load().mp2g_prover_lookup_wires_dev(self.h, nl.ctypes.data_as(ctypes.c_void_p), d_wires.ptr, int(batch)))
+
     def set_lookups(self, luts):
         """Lookup tables of the circuit (CommonCircuitData::luts + ProverOnlyCircuitData::lookup_rows): prove() then
         draws the lookup challenges, computes the RE / Sum / LDC polynomials into the Z oracle and adds the lookup
@@ -668,8 +674,16 @@ class WitnessProgram:
         self.h = ctypes.c_void_p()
         _ck(load().mp2g_witness_program_create(_p(tape), ctypes.c_size_t(tape.size), int(ckt.n_slots), int(ckt.log_n), _p(ins), int(ins.size),
                                                _p(cs), int(cs.shape[0]), ctypes.byref(self.h)))
+        if getattr(ckt, "luts", None):
+            self.set_lookups(ckt.luts)
         _ck(load().mp2g_witness_program_set_probe(self.h, _p(self.probe), int(self.probe.size)))
         self.n_levels = int(load().mp2g_witness_program_num_levels(self.h))
+
+    def set_lookups(self, luts):
+        """the circuit's lookup tables (the dicts a built circuit keeps in ckt.luts): a tape with MP2G_OP_LOOKUP needs them, and
+        every replay then also fills the padding, the table rows and the multiplicities (prove()'s set_lookup_wires)"""
+        arr, keep = lookup_array(luts)
+        _ck(load().mp2g_witness_program_set_lookups(self.h, arr, len(luts)))
 
     def run_dev(self, ctx, d_inputs, batch, d_wires, d_probe):
         """the same replay on the device, stream ordered on ctx's stream: d_inputs [batch][n_inputs] -> d_wires [batch][135][n] (the

@@ -9,6 +9,7 @@
 #include "zperm.h"
 #include "gates.h"
 #include "lookup.h"
+#include "lookup_wires.h"
 #include <cstring>
 #include <new>
 #include <vector>
@@ -46,6 +47,8 @@ struct mp2g_prover {
   // lookup argument (mp2g_prover_set_lookups): tables on the device, per-proof table polynomials
   LookupDev lookups{};
   DevBuf lut_tables, lut_eval;
+  DevBuf lut_index;            // input -> entry of every table (lookup_wires.h), for mp2g_prover_lookup_wires_dev
+  bool lut_inputs_unique = false;
   // PublicInputGate row whose first four wires the prover fills from d_pi_hash (mp2g_prover_bind_public_inputs)
   int64_t pi_row = -1;
   // witness check (mp2g_prover_enable_witness_check): bit 0 copy constraints, bit 1 gate constraints
@@ -640,12 +643,38 @@ int mp2g_prover_set_lookups(mp2g_prover* pr, const mp2g_lookup* luts, uint32_t n
   pr->gates.num_lookup_selectors = 0;
   { int rc = lookup_upload(pr->ctx->stream, luts, n_luts, pr->lut_tables, L); if (rc) return rc; }
   CK(pr->lut_eval.alloc((size_t)pr->Bcap * P.zs_count * MP2G_MAX_LUTS * sizeof(u64)));
+  {
+    // the index set_lookup_wires on the device looks pairs up in (mp2g_prover_lookup_wires_dev), built here once
+    std::vector<u32> index;
+    pr->lut_inputs_unique = lut_build_index(luts, n_luts, index);
+    CK(pr->lut_index.alloc(index.size() * sizeof(u32)));
+    CK(hipMemcpy(pr->lut_index.p, index.data(), index.size() * sizeof(u32), hipMemcpyHostToDevice));
+  }
   pr->lookups = L;
   pr->gates.num_lookup_selectors = n_sel;
   // the gate constants move behind the lookup selectors: re-validate the table against the constant count
   const char* msg = gate_table_check(pr->gates, num_constants, P.oracle_w[1]);
   if (msg) { pr->lookups = LookupDev{}; pr->gates.num_lookup_selectors = 0; return fail("invalid gate table with lookups: %s", msg); }
   pr->drop_graph();
+  return 0;
+}
+int mp2g_prover_lookup_wires_dev(mp2g_prover* pr, const uint32_t* n_lookups, uint64_t* d_wires, uint32_t batch) {
+  NEED(pr && n_lookups && d_wires && batch >= 1, "prover / n_lookups / wires / batch");
+  const LookupDev& D = pr->lookups;
+  NEED(D.n_luts, "call mp2g_prover_set_lookups first");
+  NEED(pr->lut_inputs_unique, "a lookup table holds an input twice: its multiplicities are not defined");
+  LutIndex L{};
+  L.n_luts = D.n_luts; L.lu_slots = D.num_lu_slots; L.lut_slots = D.num_lut_slots;
+  for (uint32_t t = 0; t < D.n_luts; t++) {
+    NEED((uint64_t)n_lookups[t] <= (uint64_t)(D.last_lut_row[t] - D.last_lu_row[t]) * D.num_lu_slots, "n_lookups exceeds the table's LookupGate slots");
+    L.last_lu_row[t] = D.last_lu_row[t]; L.last_lut_row[t] = D.last_lut_row[t]; L.first_lut_row[t] = D.first_lut_row[t];
+    L.table_len[t] = D.table_len[t]; L.n_lookups[t] = n_lookups[t];
+    L.table[t] = D.table[t];
+    L.index[t] = (const u32*)pr->lut_index.p + (size_t)t * LUT_INPUTS;
+  }
+  // set_lookups checked the rows against 2^log_n and the slot columns against oracle_w[1]
+  const u64 n = (u64)1 << pr->P.log_n;
+  CK(lookup_wires_launch(pr->ctx->stream, L, (u64*)d_wires, batch, (u64)pr->P.oracle_w[1] * n, n, 1));
   return 0;
 }
 int mp2g_prover_bind_public_inputs(mp2g_prover* pr, int64_t row) {

@@ -4,6 +4,7 @@
 #include <mutex>
 #include <vector>
 #include "ctx.h"
+#include "lookup_wires.h"
 
 namespace mp2g {
 // the opcodes are the PUBLIC ones (include/mp2g.h enum mp2g_witness_op: operand layouts and rules are documented there)
@@ -16,17 +17,25 @@ enum { OP_ARITH = MP2G_OP_ARITH, OP_ARITH_EXT = MP2G_OP_ARITH_EXT, OP_P2 = MP2G_
 // the second block (include/mp2g.h enum mp2g_witness_op_gf5): GF(p^5) hints, witness_gf5.h
 enum { OP_QUINTIC_SQRT = MP2G_OP_QUINTIC_SQRT, OP_QUINTIC_QUOTIENT = MP2G_OP_QUINTIC_QUOTIENT, OP_GF5_END = MP2G_OP_GF5_END };
 GLHD bool op_is_gf5(u64 op) { return op >= OP_QUINTIC_SQRT && op < OP_GF5_END; }
+// the third block (include/mp2g.h enum mp2g_witness_op_lut): lookups into the circuit's tables (mp2g_witness_program_set_lookups)
+enum { OP_LOOKUP = MP2G_OP_LOOKUP, OP_LUT_END = MP2G_OP_LUT_END };
+GLHD bool op_is_lut(u64 op) { return op >= OP_LOOKUP && op < OP_LUT_END; }
 const u32 BASE_SUM_LIMBS = 63, RA_BITS = 4, RA_COPIES = 4, RED_COEFFS = 43, RED_EXT_COEFFS = 32, NUM_WIRES = 135;
 
 // the program's read-only data on one device (uploaded at the first device run there)
 struct WitnessDev {
   int device = -1;
   DevBuf tape, sched, level_off, level_p2, input_sids, consts, domtab, probe;
+  // the program's lookup tables (n_luts = 0: none): tables and input index on the device, the description by value for the
+  // lookup-wires pass and in device memory (lut_desc) for the executor's MP2G_OP_LOOKUP
+  DevBuf lut_tables, lut_index, lut_desc;
+  LutIndex lut{};
 };
 // device executor (witness_dev.hip): one block per proof walks the level schedule; gf5 = the program holds GF(p^5) opcodes (a tape
 // without them runs the kernel instance that has no code for them)
 hipError_t witness_exec_launch(hipStream_t s, const WitnessDev& d, bool gf5, u32 n_levels, u32 n_slots, u32 log_n, u32 n_inputs, u32 n_consts,
                                u32 n_probe, const u64* d_inputs, u32 batch, u64* d_vals, u64* d_wires, u64* d_probe_out);
+const u32 WIT_LU_SLOTS = 40, WIT_LUT_SLOTS = 26;  // LookupGate / LookupTableGate num_slots with 80 routed wires
 }  // namespace mp2g
 
 struct mp2g_witness_program {
@@ -41,6 +50,12 @@ struct mp2g_witness_program {
   std::vector<u32> level_p2;  // per level: first schedule index and count of its Poseidon2 rows (one opcode = one contiguous run)
   bool ssa = true;
   bool gf5 = false;        // the tape holds GF(p^5) opcodes (include/mp2g.h enum mp2g_witness_op_gf5)
+  // lookup tables (mp2g_witness_program_set_lookups): the copied tables, their input index, and the description the host replay
+  // and its lookup-wires pass read (host pointers into the two vectors)
+  bool has_lookup = false;  // the tape holds MP2G_OP_LOOKUP
+  std::vector<mp2g::u16> lut_tables;
+  std::vector<u32> lut_index;
+  mp2g::LutIndex lut{};
   std::vector<u32> probe;  // slots returned next to the wires by the device run (mp2g_witness_program_set_probe)
   std::mutex dev_mu;
   std::vector<mp2g::WitnessDev*> dev;  // per device

@@ -184,7 +184,8 @@ void exec(const mp2g_witness_program& P, const u64* t, const u64* end, u64* vals
       }
       default: {  // every other opcode has one body, shared with the device executor (witness_ops.h, witness_gf5.h)
         const auto put = [&](u64 col, u64 row, u64 v) { W(col, row) = v; };
-        if (!exec_core_op(op, t, vals, put, &P.dom[0][0], &P.bw[0][0]) && !exec_gate_op(op, t, vals, put) && !exec_gf5_op(op, t, vals)) return;  // refused at create
+        if (!exec_core_op(op, t, vals, put, &P.dom[0][0], &P.bw[0][0]) && !exec_gate_op(op, t, vals, put) && !exec_gf5_op(op, t, vals) &&
+            !exec_lut_op(op, t, vals, put, P.lut)) return;  // refused at create (MP2G_OP_LOOKUP without tables: at run)
         break;
       }
     }
@@ -199,6 +200,8 @@ void run_one(const mp2g_witness_program& P, const u64* inputs, u64* vals, u64* w
   for (size_t i = 0; i < P.consts.size(); i += 2) vals[P.consts[i]] = P.consts[i + 1];
   for (size_t i = 0; i < P.input_sids.size(); i++) vals[P.input_sids[i]] = inputs[i];
   exec(P, P.tape.data(), P.tape.data() + P.tape.size(), vals, wires, inner, rows ? 1 : n, rows ? NUM_WIRES : 1);
+  // prove()'s set_lookup_wires: padding, table rows and multiplicities (the twin of the kernel the device replay runs)
+  if (P.lut.n_luts) lookup_wires_host(P.lut, wires, rows ? 1 : n, rows ? NUM_WIRES : 1);
 }
 }  // namespace
 
@@ -230,8 +233,9 @@ static int witness_program_create(const uint64_t* tape, size_t tape_len, uint32_
       if (t >= par_end) { par_end = nullptr; boundaries.clear(); next_boundary = 0; }
     }
     const u64 op = *t++;
-    if ((op < OP_ARITH || op >= OP_END) && !op_is_gf5(op)) return bad("unknown opcode");
+    if ((op < OP_ARITH || op >= OP_END) && !op_is_gf5(op) && !op_is_lut(op)) return bad("unknown opcode");
     if (op_is_gf5(op)) P->gf5 = true;
+    if (op_is_lut(op)) P->has_lookup = true;
     if (op == OP_PAR && par_end) return bad("parallel regions do not nest");
     const OpShape shape = op_shape(op, t, (size_t)(end - t));
     const u32 len = shape.len;
@@ -268,6 +272,8 @@ static int witness_program_create(const uint64_t* tape, size_t tape_len, uint32_
         break;
       }
       case OP_BASE_SPLIT: if (t[0] >= n || t[1] < 1 || t[1] > 2 || t[1] * t[2] > 63) return bad("BaseSplit operands"); break;
+      // the table's own rows are known at mp2g_witness_program_set_lookups, which checks the row against them
+      case OP_LOOKUP: if (t[0] >= n || t[1] >= WIT_LU_SLOTS || t[2] >= MP2G_MAX_LUTS) return bad("Lookup operands"); break;
       case OP_MUL_EXT: if (t[0] >= n || t[1] >= 13 || t[2] >= GL_P) return bad("MulExtension operands"); break;
       default: break;
     }
@@ -357,6 +363,70 @@ int mp2g_witness_program_set_probe(mp2g_witness_program* P, const uint32_t* prob
   P->probe.assign(probe_sids, probe_sids + n_probe);
   return 0;
 }
+static int witness_program_set_lookups(mp2g_witness_program* P, const mp2g_lookup* luts, uint32_t n_luts) {
+  NEED(P && (luts || !n_luts) && n_luts <= MP2G_MAX_LUTS, "program / tables (at most MP2G_MAX_LUTS)");
+  std::lock_guard<std::mutex> g(P->dev_mu);
+  NEED(P->dev.empty(), "set the lookup tables before the first device run");
+  const u64 n = (u64)1 << P->log_n;
+  LutIndex L{};
+  L.n_luts = n_luts; L.lu_slots = WIT_LU_SLOTS; L.lut_slots = WIT_LUT_SLOTS;
+  size_t words = 0;
+  for (uint32_t t = 0; t < n_luts; t++) {
+    const mp2g_lookup& u = luts[t];
+    NEED(u.table && u.table_len >= 1 && u.table_len <= LUT_INPUTS, "table (1 .. 65536 entries)");
+    NEED(u.last_lu_row < u.last_lut_row && u.last_lut_row <= u.first_lut_row && (u64)u.first_lut_row + 1 < n, "lookup rows");
+    NEED((u64)u.first_lut_row - u.last_lut_row + 1 == ((u64)u.table_len + WIT_LUT_SLOTS - 1) / WIT_LUT_SLOTS,
+         "the LookupTableGate rows must be ceil(table_len / 26)");
+    for (uint32_t o = 0; o < t; o++)
+      NEED(u.last_lu_row > luts[o].first_lut_row || u.first_lut_row < luts[o].last_lu_row, "two tables share rows");
+    L.last_lu_row[t] = u.last_lu_row; L.last_lut_row[t] = u.last_lut_row; L.first_lut_row[t] = u.first_lut_row; L.table_len[t] = u.table_len;
+    words += (size_t)u.table_len * 2;
+  }
+  std::vector<u32> index;
+  NEED(lut_build_index(luts, n_luts, index), "a lookup table holds an input twice");
+  // the instructions of a table take the slots 0 .. n_t - 1 of its LookupGate rows, each once
+  std::vector<std::vector<uint8_t>> used(n_luts);
+  for (uint32_t t = 0; t < n_luts; t++) used[t].assign((size_t)(luts[t].last_lut_row - luts[t].last_lu_row) * WIT_LU_SLOTS, 0);
+  const u64* end = P->tape.data() + P->tape.size();
+  for (const u64* q = P->tape.data(); q < end;) {
+    const u64 op = *q;
+    const u64* a = q + 1;
+    q = a + op_shape(op, a, (size_t)(end - a)).len;  // validated at create; a parallel region's sections follow its header
+    if (op != OP_LOOKUP) continue;
+    NEED(a[2] < n_luts, "an MP2G_OP_LOOKUP names a table that was not given");
+    const mp2g_lookup& u = luts[a[2]];
+    NEED(a[0] >= u.last_lu_row && a[0] < u.last_lut_row, "an MP2G_OP_LOOKUP row outside its table's LookupGate rows");
+    uint8_t& slot = used[a[2]][(size_t)(a[0] - u.last_lu_row) * WIT_LU_SLOTS + a[1]];
+    NEED(!slot, "two MP2G_OP_LOOKUP instructions use one slot");
+    slot = 1;
+  }
+  for (uint32_t t = 0; t < n_luts; t++) {
+    size_t cnt = 0;
+    while (cnt < used[t].size() && used[t][cnt]) cnt++;
+    for (size_t j = cnt; j < used[t].size(); j++) NEED(!used[t][j], "the MP2G_OP_LOOKUP instructions of a table leave a slot free before a used one");
+    L.n_lookups[t] = (u32)cnt;
+  }
+  P->lut_tables.resize(words);
+  P->lut_index.swap(index);
+  size_t off = 0;
+  for (uint32_t t = 0; t < n_luts; t++) {
+    memcpy(P->lut_tables.data() + off, luts[t].table, (size_t)luts[t].table_len * 2 * sizeof(u16));
+    L.table[t] = P->lut_tables.data() + off;
+    L.index[t] = P->lut_index.data() + (size_t)t * LUT_INPUTS;
+    off += (size_t)luts[t].table_len * 2;
+  }
+  P->lut = L;
+  return 0;
+}
+int mp2g_witness_program_set_lookups(mp2g_witness_program* P, const mp2g_lookup* luts, uint32_t n_luts) {
+  try {
+    return witness_program_set_lookups(P, luts, n_luts);
+  } catch (const std::bad_alloc&) {
+    return fail("out of memory while copying the lookup tables");
+  } catch (...) {
+    return fail("mp2g_witness_program_set_lookups failed");
+  }
+}
 // the program's read-only data on the context's device, uploaded once
 static int witness_dev_data(mp2g_witness_program* P, mp2g_ctx* c, WitnessDev** out) {
   std::lock_guard<std::mutex> g(P->dev_mu);
@@ -383,6 +453,16 @@ static int witness_dev_data(mp2g_witness_program* P, mp2g_ctx* c, WitnessDev** o
     memcpy(tab.data() + 6 * 32, P->bw, sizeof(P->bw));
     e = up(d->domtab, tab.data(), tab.size() * 8);
   }
+  if (e == hipSuccess && P->lut.n_luts) {
+    e = up(d->lut_tables, P->lut_tables.data(), P->lut_tables.size() * sizeof(u16));
+    if (e == hipSuccess) e = up(d->lut_index, P->lut_index.data(), P->lut_index.size() * sizeof(u32));
+    d->lut = P->lut;
+    for (u32 t = 0; t < P->lut.n_luts && e == hipSuccess; t++) {
+      d->lut.table[t] = (const u16*)d->lut_tables.p + (P->lut.table[t] - P->lut_tables.data());
+      d->lut.index[t] = (const u32*)d->lut_index.p + (size_t)t * LUT_INPUTS;
+    }
+    if (e == hipSuccess) e = up(d->lut_desc, &d->lut, sizeof(LutIndex));
+  }
   if (e != hipSuccess) { delete d; return fail("witness program upload: %s", hipGetErrorString(e)); }
   P->dev.push_back(d);
   *out = d;
@@ -393,6 +473,7 @@ int mp2g_witness_program_run_dev(mp2g_witness_program* P, mp2g_ctx* c, const uin
   NEED(P && c && d_inputs && d_wires && batch >= 1, "program / ctx / inputs / wires");
   NEED(P->probe.empty() || d_probe_out, "probe output");
   if (!P->ssa) return fail("the witness program writes a slot twice, or writes a slot an earlier instruction read: it cannot be level-scheduled for the device");
+  NEED(!P->has_lookup || P->lut.n_luts, "the program holds MP2G_OP_LOOKUP: call mp2g_witness_program_set_lookups first");
   WitnessDev* d = nullptr;
   int rc = witness_dev_data(P, c, &d);
   if (rc) return rc;
@@ -408,6 +489,8 @@ int mp2g_witness_program_run_dev(mp2g_witness_program* P, mp2g_ctx* c, const uin
   // [batch][135][n] is made from it by the tiled transpose (every word of d_wires is written)
   CK(witness_exec_launch(c->stream, *d, P->gf5, (u32)P->level_off.size() - 1, P->n_slots, P->log_n, (u32)P->input_sids.size(), (u32)(P->consts.size() / 2),
                           (u32)P->probe.size(), (const u64*)d_inputs, batch, c->wit_vals.p, c->wit_rows.p, (u64*)d_probe_out));
+  // prove()'s set_lookup_wires on the staging matrix, where a LookupGate row is contiguous (lookup_wires.hip)
+  CK(lookup_wires_launch(c->stream, d->lut, c->wit_rows.p, batch, (u64)NUM_WIRES << P->log_n, 1, NUM_WIRES));
   {
     int rc2 = mp2g_wires_from_rows_dev(c, c->wit_rows.p, d_wires, P->log_n, NUM_WIRES, batch);
     if (rc2) return rc2;
@@ -418,6 +501,7 @@ static int witness_run(const mp2g_witness_program* P, const uint64_t* inputs, ui
                        const uint32_t* probe_sids, uint32_t n_probe, uint64_t* probe_out, bool rows) {
   NEED(P && inputs && wires && batch >= 1, "program / inputs / wires");
   NEED(!n_probe || (probe_sids && probe_out), "probe");
+  NEED(!P->has_lookup || P->lut.n_luts, "the program holds MP2G_OP_LOOKUP: call mp2g_witness_program_set_lookups first");
   for (uint32_t i = 0; i < n_probe; i++) NEED(probe_sids[i] < P->n_slots, "probe slot");
   const size_t n_in = P->input_sids.size();
   for (size_t i = 0; i < (size_t)batch * n_in; i++) NEED(inputs[i] < GL_P, "inputs must be canonical field elements");

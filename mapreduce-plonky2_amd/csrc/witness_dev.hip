@@ -153,8 +153,8 @@ GLD void exec_poseidon(const u64* t, u64* vals, u64* wires, u64 n) {
   for (int i = 0; i < 12; i++) { const u64 o = gl_canon(s[i]); W(12 + i, row) = o; vals[t[14 + i]] = o; }
 }
 
-template <bool GF5>
-GLD void exec_one(const u64* t, u64* vals, u64* wires, u64 n, const u64* domtab) {
+template <bool GF5, bool LUT>
+GLD void exec_one(const u64* t, u64* vals, u64* wires, u64 n, const u64* domtab, const LutIndex* lut) {
   const u64 op = *t++;
   switch (op) {
     case OP_P2: exec_p2(t, vals, wires, n); break;
@@ -166,6 +166,9 @@ GLD void exec_one(const u64* t, u64* vals, u64* wires, u64 n, const u64* domtab)
       if constexpr (GF5) {
         if (exec_gf5_op(op, t, vals)) break;
       }
+      if constexpr (LUT) {
+        if (exec_lut_op(op, t, vals, put, *lut)) break;
+      }
       exec_gate_op(op, t, vals, put);
       break;
     }
@@ -175,14 +178,15 @@ GLD void exec_one(const u64* t, u64* vals, u64* wires, u64 n, const u64* domtab)
 
 constexpr int WIT_LANES = 512;
 // GF5: the program holds GF(p^5) opcodes. Only that instance carries their code (the field's square root and inverse are long
-// out-of-line bodies); a tape without them runs the instance that is the kernel as it was before they existed.
-template <bool GF5>
+// out-of-line bodies); a tape without them runs the instance that is the kernel as it was before they existed. LUT: the same for
+// MP2G_OP_LOOKUP, whose tables `lut` describes (device memory).
+template <bool GF5, bool LUT>
 __global__ void __launch_bounds__(WIT_LANES) witness_exec_kernel(const u64* __restrict__ tape, const u32* __restrict__ sched,
                                                                 const u32* __restrict__ level_off, const u32* __restrict__ level_p2, u32 n_levels, u32 n_slots, u32 log_n,
                                                                 const u32* __restrict__ input_sids, u32 n_inputs, const u64* __restrict__ consts,
                                                                 u32 n_consts, const u64* __restrict__ domtab, const u32* __restrict__ probe,
                                                                 u32 n_probe, const u64* __restrict__ inputs, u64* vals_all, u64* wires_all,
-                                                                u64* probe_out) {
+                                                                u64* probe_out, const LutIndex* __restrict__ lut) {
   const u32 b = blockIdx.x, tid = threadIdx.x;
   const u64 n = (u64)1 << log_n;
   u64* vals = vals_all + (u64)b * n_slots;
@@ -200,10 +204,10 @@ __global__ void __launch_bounds__(WIT_LANES) witness_exec_kernel(const u64* __re
       const u32 rest = (hi - lo) - p2_n;
       for (u32 i = tid; i < rest; i += WIT_LANES) {
         const u32 j = lo + i;
-        exec_one<GF5>(tape + sched[j < p2_lo ? j : j + p2_n], vals, wires, n, domtab);
+        exec_one<GF5, LUT>(tape + sched[j < p2_lo ? j : j + p2_n], vals, wires, n, domtab, lut);
       }
     } else {
-      for (u32 i = lo + tid; i < hi; i += WIT_LANES) exec_one<GF5>(tape + sched[i], vals, wires, n, domtab);
+      for (u32 i = lo + tid; i < hi; i += WIT_LANES) exec_one<GF5, LUT>(tape + sched[i], vals, wires, n, domtab, lut);
     }
     __syncthreads();  // the level's slot writes (global memory, this block's) are visible to the next level's reads
   }
@@ -213,9 +217,12 @@ __global__ void __launch_bounds__(WIT_LANES) witness_exec_kernel(const u64* __re
 
 hipError_t witness_exec_launch(hipStream_t s, const WitnessDev& d, bool gf5, u32 n_levels, u32 n_slots, u32 log_n, u32 n_inputs,
                                u32 n_consts, u32 n_probe, const u64* d_inputs, u32 batch, u64* d_vals, u64* d_wires, u64* d_probe_out) {
-  hipLaunchKernelGGL(gf5 ? witness_exec_kernel<true> : witness_exec_kernel<false>, dim3(batch), dim3(WIT_LANES), 0, s, d.tape.p, (const u32*)d.sched.p, (const u32*)d.level_off.p,
+  const bool lut = d.lut.n_luts != 0;
+  const auto kernel = lut ? (gf5 ? witness_exec_kernel<true, true> : witness_exec_kernel<false, true>)
+                          : (gf5 ? witness_exec_kernel<true, false> : witness_exec_kernel<false, false>);
+  hipLaunchKernelGGL(kernel, dim3(batch), dim3(WIT_LANES), 0, s, d.tape.p, (const u32*)d.sched.p, (const u32*)d.level_off.p,
                      (const u32*)d.level_p2.p, n_levels, n_slots, log_n, (const u32*)d.input_sids.p, n_inputs, d.consts.p, n_consts, d.domtab.p,
-                     (const u32*)d.probe.p, n_probe, d_inputs, d_vals, d_wires, d_probe_out);
+                     (const u32*)d.probe.p, n_probe, d_inputs, d_vals, d_wires, d_probe_out, lut ? (const LutIndex*)d.lut_desc.p : nullptr);
   return hipGetLastError();
 }
 }  // namespace mp2g

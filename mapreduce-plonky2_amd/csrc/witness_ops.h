@@ -1,4 +1,4 @@
-// What a witness-tape instruction IS (include/mp2g.h enum mp2g_witness_op, enum mp2g_witness_op_gf5), defined ONCE for the host
+// What a witness-tape instruction IS (include/mp2g.h enum mp2g_witness_op, enum mp2g_witness_op_gf5, enum mp2g_witness_op_lut), defined ONCE for the host
 // (witness.hip: validation, level schedule, replay) and the device replay (witness_dev.hip): op_shape gives an instruction's length
 // and operand roles, exec_core_op replays the recursion circuits' opcodes (MP2G_OP_ARITH .. MP2G_OP_HINT_SPLIT), exec_gate_op the
 // leaf-circuit gates (MP2G_OP_U32_ARITH .. MP2G_OP_EXP; the GF(p^5) hints are witness_gf5.h). The gate generators restate
@@ -51,6 +51,7 @@ GLHD OpShape op_shape(u64 op, const u64* t, size_t left) {
     case OP_EXP: return left >= 2 && t[1] >= 1 && t[1] <= 66 ? OpShape{3 + (u32)t[1] + 1, 2, 2, 1 + (u32)t[1], 3 + (u32)t[1], 1} : malformed;
     case OP_QUINTIC_SQRT: return {11, 0, 0, 5, 5, 6};
     case OP_QUINTIC_QUOTIENT: return {15, 0, 0, 10, 10, 5};
+    case OP_LOOKUP: return {5, 3, 3, 1, 4, 1};  // row, slot of the LookupGate row, table, input, output
     default: return malformed;
   }
 }
@@ -170,6 +171,20 @@ GLHD bool exec_core_op(u64 op, const u64* t, u64* vals, Put put, const u64* dom_
     case OP_HINT_SPLIT: vals[t[2]] = vals[t[0]] & (((u64)1 << t[1]) - 1); vals[t[3]] = vals[t[0]] >> t[1]; return true;
     default: return false;
   }
+}
+
+// The lookup block. L = the program's tables (lookup_wires.h; create and set_lookups checked the row, the slot and the table).
+// LookupGate / LookupGenerator: wires 2i, 2i+1 = the looked-up input and the table's output for it. An input the table does not
+// hold gives 0: the pair is then in no table entry and the proof fails the lookup argument.
+template <class Put>
+GLHD bool exec_lut_op(u64 op, const u64* t, u64* vals, Put put, const LutIndex& L) {
+  if (op != OP_LOOKUP) return false;
+  const u64 row = t[0], i = t[1], lut = t[2], x = vals[t[3]];
+  const u32 e = x < LUT_INPUTS ? L.index[lut][x] : LUT_ABSENT;
+  const u64 out = e != LUT_ABSENT ? L.table[lut][2 * e + 1] : 0;
+  put(2 * i, row, x); put(2 * i + 1, row, out);
+  vals[t[4]] = out;
+  return true;
 }
 
 // The leaf-circuit gates.

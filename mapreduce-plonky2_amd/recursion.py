@@ -23,6 +23,7 @@ import numpy as np
 from . import Gate, MULT_GEN
 from . import circuits as C
 from . import gf5
+from . import lut
 
 P = C.P
 W7 = 7  # quadratic extension X^2 = 7
@@ -79,6 +80,7 @@ class T:
  # the leaf circuits' user-logic gates (round 6; include/mp2g.h enum mp2g_witness_op documents every operand layout)
  OP_U32_ARITH, OP_U32_SUB, OP_U32_ADD_MANY, OP_U32_RANGE_CHECK, OP_COMPARISON, OP_BASE_SPLIT, OP_MUL_EXT, OP_EXP) = range(1, 24)
 # The GF(p^5) hints are the header's second block (enum mp2g_witness_op_gf5, 32..33): gf5.OP_QUINTIC_SQRT, gf5.OP_QUINTIC_QUOTIENT.
+# The lookup is its third (enum mp2g_witness_op_lut, 40): lut.OP_LOOKUP.
 
 
 class E:
@@ -142,6 +144,7 @@ _OPS = {
     OP_EXP: (1, lambda nb: (3 + nb + 1, 2, 1 + nb, 3 + nb, 1), lambda t: [(t[0], c) for c in range(2 * t[1] + 2)]),
     gf5.OP_QUINTIC_SQRT: (None, (11, 0, 5, 5, 6), lambda t: []),
     gf5.OP_QUINTIC_QUOTIENT: (None, (15, 0, 10, 10, 5), lambda t: []),
+    lut.OP_LOOKUP: (None, (5, 3, 1, 4, 1), lambda t: [(t[0], 2 * t[1]), (t[0], 2 * t[1] + 1)]),
 }
 
 
@@ -259,6 +262,8 @@ class Builder:
         self.input_sids = []    # slots the caller fills, in add_virtual order
         self.input_vals = []
         self.const_slots = []   # (sid, value)
+        self.luts = []          # lookup tables: [(input, output)] each
+        self.lookups = []       # per table: (input target, output target, tape position of its OP_LOOKUP)
 
     # ---- cells and copy constraints ------------------------------------------------------------------------------
     def _find(self, c):
@@ -941,6 +946,62 @@ class Builder:
         self.tape += [OP_COSET, row, bits, shift.sid] + [x for v in values for x in (v.a.sid, v.b.sid)] + [point.a.sid, point.b.sid, out.a.sid, out.b.sid]
         return out
 
+    # ---- lookup tables ([dep] plonky2 plonk/circuit_builder.rs add_lookup_table_from_pairs, add_lookup_from_index) -----------------
+    def add_lookup_table(self, pairs):
+        """a table of (input, output) u16 pairs, each input once. Returns its index."""
+        assert len(self.luts) < lut.MAX_LUTS, "at most MP2G_MAX_LUTS lookup tables"
+        self.luts.append(lut.table(pairs))
+        self.lookups.append([])
+        return len(self.luts) - 1
+
+    def add_lookup_table_from_fn(self, fn, inputs):
+        return self.add_lookup_table([(x, fn(x)) for x in inputs])
+
+    def add_lookup_from_index(self, x, index):
+        """the table's output for x (0, and a proof that fails the lookup argument, when the table has no input x). The LookupGate
+        rows of a table are laid out at build() (add_all_lookups): the instruction is recorded here, where the witness replay needs
+        the value, and gets its row and slot there."""
+        out = T(lut.output(self.luts[index], x.v), None, self._sid())
+        assert dict(self.luts[index]).get(x.v) is not None or not self.strict, f"lookup: {x.v} is not in table {index}"
+        self.lookups[index].append((x, out, len(self.tape)))
+        self.tape += [lut.OP_LOOKUP, 0, 0, index, x.sid, out.sid]
+        return out
+
+    def _add_all_lookups(self):
+        """CircuitBuilder::add_all_lookups: per table the LookupGate rows holding its lookups (the last one padded with the table's
+        first pair), the LookupTableGate rows with the table running DOWN from the last of them (multiplicities as prove()'s
+        set_lookup_wires counts them), and one Noop -- the layout of circuits.build(luts=...)."""
+        infos = []
+        for t, (pairs, lookups) in enumerate(zip(self.luts, self.lookups)):
+            n_lu, n_lut = lut.rows_needed(len(pairs), len(lookups))
+            first = len(self.rows)
+            for _ in range(n_lu):
+                self._new_row(C.LOOKUP, lut.NUM_LU_SLOTS)
+            for _ in range(n_lut):
+                self._new_row(C.LOOKUP_TABLE, lut.NUM_LUT_SLOTS)
+            self._new_row(C.NOOP)
+            for j, (x, out, pos) in enumerate(lookups):
+                row, i = first + j // lut.NUM_LU_SLOTS, j % lut.NUM_LU_SLOTS
+                self._put(row, 2 * i, x)
+                self._put(row, 2 * i + 1, out)
+                self.tape[pos + 1], self.tape[pos + 2] = row, i
+            info = {"table": np.array(pairs, dtype=np.uint16).reshape(-1, 2), "n_lookups": len(lookups), "last_lu_row": first,
+                    "last_lut_row": first + n_lu, "first_lut_row": first + n_lu + n_lut - 1}
+
+            class _Cells:  # wires[col][row] over the builder's rows, for lut.fill_wires
+                def __init__(s, col):
+                    s.col = col
+
+                def __getitem__(s, r):
+                    return self.rows[r].wires[s.col]
+
+                def __setitem__(s, r, v):
+                    self.rows[r].wires[s.col] = v
+
+            lut.fill_wires([_Cells(c) for c in range(NUM_ROUTED)], info)
+            infos.append(info)
+        return infos
+
     # ---- gate set ------------------------------------------------------------------------------------------------------------------
     def add_gate_rows(self, kinds, seed=0xC0FFEE06):
         """one satisfied row of every gate (kind, p0, p1, p2) of `kinds` the circuit does not contain yet. plonky2 evaluates every
@@ -1026,6 +1087,7 @@ class Builder:
     def build(self, min_log_n=6):
         """CircuitBuilder::build: the public-inputs hash bound to a PublicInputGate, rows padded with Noops to a
         power of two, selectors, sigma polynomials from the copy classes. Returns a circuits.Circuit."""
+        lut_info = self._add_all_lookups()
         pi_hash = self.hash_n_to_m_no_pad(self.public_inputs, 4, self.hasher)  # C::InnerHasher of the circuit's config
         pi_row = self._new_row(C.PUBLIC_INPUT)
         for i, t in enumerate(pi_hash):
@@ -1064,7 +1126,18 @@ class Builder:
             ids = [ks[c] * int(xs[r]) % P for r, c in cells]
             for (r, c), v in zip(cells, ids[1:] + ids[:1]):
                 sig[c][r] = v
-        consts = np.array(cols + [[row.consts[k] for row in self.rows] for k in range(2)], dtype=np.uint64)
+        lookup_sel = []
+        if lut_info:  # gates/selectors.rs selectors_lookup, selector_ends_lookups: between the selectors and the gate constants
+            lookup_sel = [[0] * n for _ in range(C.LOOKUP_SELECTORS + len(lut_info))]
+            for t, info in enumerate(lut_info):
+                for r in range(info["last_lut_row"], info["first_lut_row"] + 1):
+                    lookup_sel[0][r] = 1  # TransSre
+                for r in range(info["last_lu_row"], info["last_lut_row"]):
+                    lookup_sel[1][r] = 1  # TransLdc
+                lookup_sel[2][info["first_lut_row"] + 1] = 1  # InitSre
+                lookup_sel[3][info["last_lu_row"]] = 1        # LastLdc
+                lookup_sel[C.LOOKUP_SELECTORS + t][info["last_lut_row"]] = 1  # end of table t
+        consts = np.array(cols + lookup_sel + [[row.consts[k] for row in self.rows] for k in range(2)], dtype=np.uint64)
         ckt = C.Circuit()
         ckt.log_n, ckt.gates, ckt.num_selectors = log_n, gates, len(cols)
         ckt.pi_hash = np.array([t.v for t in pi_hash], dtype=np.uint64)
@@ -1075,7 +1148,8 @@ class Builder:
         ckt.instances = instances
         ckt.pi_row = pi_row
         ckt.gate_array = (Gate * len(gates))(*gates)
-        ckt.luts, ckt.num_lookup_selectors, ckt.num_lookup_polys = [], 0, 0
+        ckt.luts, ckt.num_lookup_selectors = lut_info, len(lookup_sel)
+        ckt.num_lookup_polys = C.NUM_LOOKUP_POLYS if lut_info else 0
         ckt.n_used_rows = n_rows - 1
         # the witness program of this circuit (see the OP_* table above) and the inputs this build was run with
         ckt.tape = np.array(self.tape, dtype=np.uint64)
@@ -1147,7 +1221,7 @@ def eval_gate_circuit(b, g, consts, wires, pih):
     (extension targets), wires = local wires, pih = public-inputs hash (base targets). Order as eval_unfiltered."""
     k = g.kind
     out = []
-    if k == C.NOOP:
+    if k in (C.NOOP, C.LOOKUP, C.LOOKUP_TABLE):  # the lookup gates have no constraints of their own: the lookup argument carries them
         return out
     if k == C.CONSTANT:
         return [b.sub_ext(consts[i], wires[i]) for i in range(g.p0)]
@@ -1454,6 +1528,81 @@ class InnerCircuit:
         self.cap = [[int(x) for x in h] for h in np.asarray(constants_sigmas_cap).reshape(-1, 4)]
         self.circuit_digest = [int(x) for x in circuit_digest]
         self.n_public_inputs = n_public_inputs
+        # CommonCircuitData::luts and the rows of each table (the dicts of ckt.luts), num_lookup_selectors
+        self.luts = list(getattr(ckt, "luts", None) or [])
+        self.num_lookup_selectors = getattr(ckt, "num_lookup_selectors", 0) if self.luts else 0
+
+
+def check_lookup_constraints_circuit(b, luts, sel, wires, zs, zs_next, deltas, lut_polys):
+    """plonk/vanishing_poly.rs check_lookup_constraints_circuit for one challenge round, in the order of csrc/verifier.hip and
+    oracle/gates_body.inc eval_lookup_constraints: sel = the lookup selectors (TransSre, TransLdc, InitSre, LastLdc, then one end
+    selector per table), zs = RE then the partial Sum / LDC polynomials at zeta, zs_next the same at g zeta, deltas = the
+    round's four challenges (A, B, alpha, delta; base targets), lut_polys[t] = get_lut_poly of table t. Returns the terms."""
+    n_lu, n_lut = lut.NUM_LU_SLOTS, lut.NUM_LUT_SLOTS
+    lu_deg = 8 - 1                 # quotient degree factor - 1 (csrc/lookup.h lookup_geometry)
+    ns = -(-n_lu // lu_deg)        # the partial Sum / LDC polynomials: NUM_LOOKUP_POLYS - 1
+    lut_deg = -(-n_lut // ns)
+    d_a, d_b, d_al, d_de = [b.to_ext(t) for t in deltas]
+    combo = lambda i, stride: b.sub_ext(d_al, b.mul_add_ext(d_a, wires[stride * i + 1], wires[stride * i]))  # alpha - (inp + A out)
+    terms = [b.mul_ext(sel[3], zs[ns]), b.mul_ext(sel[2], zs[1]), b.mul_ext(sel[2], zs[0])]
+    for t in range(len(luts)):
+        terms.append(b.mul_ext(sel[4 + t], b.sub_ext(zs[0], lut_polys[t])))
+    cur = zs_next[0]
+    for i in range(n_lut):
+        cur = b.mul_add_ext(cur, d_de, b.mul_add_ext(d_b, wires[3 * i + 1], wires[3 * i]))
+    terms.append(b.mul_ext(sel[0], b.sub_ext(zs[0], cur)))
+    lut_c = [combo(i, 3) for i in range(n_lut)]
+    lu_c = [combo(i, 2) for i in range(n_lu)]
+
+    def prod(xs):
+        acc = None
+        for x in xs:
+            acc = x if acc is None else b.mul_ext(acc, x)
+        return acc if acc is not None else b.one_ext()
+
+    for poly in range(ns):
+        t0, u0 = min(poly * lut_deg, n_lut), poly * lu_deg
+        t1, u1 = min(t0 + lut_deg, n_lut), min(u0 + lu_deg, n_lu)
+        lut_sum = b.zero_ext()
+        for i in range(t0, t1):
+            lut_sum = b.mul_add_ext(wires[3 * i + 2], prod(lut_c[j] for j in range(t0, t1) if j != i), lut_sum)
+        lu_sum = b.zero_ext()
+        for i in range(u0, u1):
+            lu_sum = b.add_ext(lu_sum, prod(lu_c[j] for j in range(u0, u1) if j != i))
+        diff = b.sub_ext(zs[1 + poly], zs_next[ns] if poly == 0 else zs[poly])
+        terms.append(b.mul_ext(sel[0], b.mul_sub_ext(prod(lut_c[t0:t1]), diff, lut_sum)))  # Sum transition
+        terms.append(b.mul_ext(sel[1], b.mul_add_ext(prod(lu_c[u0:u1]), diff, lu_sum)))     # LDC transition
+    return terms
+
+
+def _table_value(b, v, values):
+    """the table entry v as a target: 0 and the powers of two are constants, every other value is the value with its lowest set
+    bit cleared plus that bit -- one addition per distinct value, in rows all of them share. As plain constants the few hundred
+    distinct entries of the bit tables would not fit the RandomAccessGate rows' spare constant slots (Builder.constant), and the
+    ConstantGate rows they would bring take the wrap circuit out of the shape the universal verifier checks."""
+    if v not in values:
+        values[v] = b.constant(v) if v & (v - 1) == 0 else b.add(_table_value(b, v & (v - 1), values), b.constant(v & -v))
+    return values[v]
+
+
+def lut_polys_circuit(b, luts, deltas, cache, values):
+    """get_lut_poly of every table under one round's challenges: sum_i (inp_i + B out_i) delta^(padded - 1 - i) over the table
+    zero-padded to whole LookupTableGate rows, the table's entries fixed by the circuit (values: entry -> target, _table_value).
+    The input and output columns are reduced apart (ReducingGate rows) and a column several tables share -- the 14 bit tables
+    have 3 input columns -- once per round (cache: column -> its sum)."""
+    d_b, d_de = b.to_ext(deltas[1]), b.to_ext(deltas[3])
+    out = []
+    for info in luts:
+        tab = [(int(a), int(c)) for a, c in info["table"]]
+        padded = -(-len(tab) // lut.NUM_LUT_SLOTS) * lut.NUM_LUT_SLOTS
+        sums = []
+        for col in range(2):
+            key = tuple(p[col] for p in tab) + (0,) * (padded - len(tab))
+            if key not in cache:
+                cache[key] = b.reduce_base(d_de, [_table_value(b, v, values) for v in reversed(key)])
+            sums.append(cache[key])
+        out.append(b.mul_add_ext(d_b, sums[1], sums[0]))
+    return out
 
 
 def verify_proof_circuit(b, inner, caps, openings, fri, public_inputs, verifier_data=None):
@@ -1463,7 +1612,8 @@ def verify_proof_circuit(b, inner, caps, openings, fri, public_inputs, verifier_
     verifier_data = (cap targets [16][4], circuit digest targets [4]) for a universal verifier whose verifier data are
     witnesses; None = the constants of inner (verify_proof_fixed_circuit, the first wrap step)."""
     fp, ckt = inner.fp, inner.ckt
-    assert fp.num_lookup_polys == 0, "lookup tables: not in the recursive verifier yet"
+    luts, nlp = inner.luts, fp.num_lookup_polys
+    assert (nlp == C.NUM_LOOKUP_POLYS) if luts else (nlp == 0), "the circuit's lookup tables and num_lookup_polys do not agree"
     k, lg = fp.log_n, fp.log_n + fp.rate_bits
     n = 1 << k
     nc = fp.zs_count
@@ -1482,7 +1632,13 @@ def verify_proof_circuit(b, inner, caps, openings, fri, public_inputs, verifier_
     else:
         cap_t[0], digest = verifier_data
     op = [VE((int(e[0]), int(e[1]))) for e in openings]
-    o_w, o_z, o_q, o_next = ws[0], ws[0] + ws[1], ws[0] + ws[1] + ws[2], sum(ws)
+    # openings in FRI batch order (csrc/layout.h opening_layout): constants, sigmas | wires | Z, partial products | quotient chunks |
+    # lookup polynomials (the tail of oracle 2) | Z at g zeta | lookup polynomials at g zeta
+    n_lookup = nc * nlp
+    wz = ws[2] - n_lookup
+    o_w, o_z, o_q, o_next = ws[0], ws[0] + ws[1], ws[0] + ws[1] + wz, sum(ws)
+    o_lu = o_q + ws[3]
+    assert len(op) == o_next + nc + n_lookup, "number of openings"
     fri = [int(x) for x in fri]
     pos = 0
 
@@ -1520,6 +1676,8 @@ def verify_proof_circuit(b, inner, caps, openings, fri, public_inputs, verifier_
     flat = lambda cap: [t for h in cap for t in h]
     ch.observe(flat(cap_t[1]))
     betas, gammas = ch.get_n(nc), ch.get_n(nc)
+    # with lookups 2 * num_challenges more (plonk_challenges_after_cap); round c's deltas = (betas ++ gammas ++ these)[4c .. 4c + 4)
+    deltas = betas + gammas + (ch.get_n(2 * nc) if luts else [])
     ch.observe(flat(cap_t[2]))
     alphas = ch.get_n(nc)
     ch.observe(flat(cap_t[3]))
@@ -1542,7 +1700,7 @@ def verify_proof_circuit(b, inner, caps, openings, fri, public_inputs, verifier_
     consts_o, sigmas_o = op[:num_consts], op[num_consts:o_w]
     wires_o = op[o_w:o_z]
     zs_o, pps_o = op[o_z:o_z + nc], op[o_z + nc:o_q]
-    quot_o = op[o_q:o_next]
+    quot_o = op[o_q:o_lu]
     zs_next = op[o_next:o_next + nc]
     terms = [b.mul_ext(l0, b.add_const_ext(zs_o[c], P - 1)) for c in range(nc)]
     k_is = [pow(MULT_GEN, j, P) for j in range(num_routed)]
@@ -1561,6 +1719,16 @@ def verify_proof_circuit(b, inner, caps, openings, fri, public_inputs, verifier_
             prev = zs_o[c] if chn == 0 else pps_o[c * num_prods + chn - 1]
             nxt = zs_next[c] if chn == chunks - 1 else pps_o[c * num_prods + chn]
             terms.append(b.mul_sub_ext(prev, num, b.mul_ext(nxt, den)))
+    # the lookup argument: its terms sit between the partial-product and the gate terms
+    nlsel = inner.num_lookup_selectors
+    if luts:
+        values = {}
+        for c in range(nc):
+            d = deltas[4 * c:4 * c + 4]
+            terms += check_lookup_constraints_circuit(b, luts, consts_o[ckt.num_selectors:ckt.num_selectors + nlsel], wires_o,
+                                                      op[o_lu + c * nlp:o_lu + (c + 1) * nlp],
+                                                      op[o_next + nc + c * nlp:o_next + nc + (c + 1) * nlp], d,
+                                                      lut_polys_circuit(b, luts, d, {}, values))
     # gate constraints. plonky2 sums filter_g c_{g,j} into slot j and alpha-reduces the slots; the same field element is
     # sum_g filter_g (sum_j alpha^j c_{g,j}) alpha^(#permutation terms): each gate's constraints are alpha-reduced first
     # (ReducingExtensionGate rows, 32 coefficients each), the filter multiplies the reduced value once.
@@ -1568,7 +1736,7 @@ def verify_proof_circuit(b, inner, caps, openings, fri, public_inputs, verifier_
     nsel = ckt.num_selectors
     per_gate = []
     for gi, g in enumerate(gates):
-        cons = eval_gate_circuit(b, g, consts_o[nsel:], wires_o, pi_hash)
+        cons = eval_gate_circuit(b, g, consts_o[nsel + nlsel:], wires_o, pi_hash)
         if not cons:
             continue
         s_sel = consts_o[g.selector_index]
@@ -1616,12 +1784,14 @@ def verify_proof_circuit(b, inner, caps, openings, fri, public_inputs, verifier_
                 # subgroup_x = g * w^(bit-reversed index)
                 sx = b.mul_const(MULT_GEN, b.exp_from_bits_const_base(w_lg, list(reversed(bits))))
                 # fri_combine_initial: (reduce(all leaf evals) - red0) / (x - zeta), shifted, + the g*zeta batch
-                leaf_all = [t for o in range(4) for t in init[o][0]]
+                # both batches in fri_batch_poly order: the lookup polynomials leave their place in oracle 2 for the end
+                leaf_all = init[0][0] + init[1][0] + init[2][0][:wz] + init[3][0] + init[2][0][wz:]
+                leaf_next = init[2][0][:nc] + init[2][0][wz:]
                 sx_e = b.to_ext(sx)
                 num0 = b.sub_ext(b.reduce_base(fri_alpha, leaf_all), red[0])
                 q0 = b.div_ext(num0, b.sub_ext(sx_e, zeta))
-                num1 = b.sub_ext(b.reduce_base(fri_alpha, init[2][0][:nc]) if nc > 21 else
-                                 b.reduce_with_powers_ext([b.to_ext(t) for t in init[2][0][:nc]], fri_alpha), red[1])
+                num1 = b.sub_ext(b.reduce_base(fri_alpha, leaf_next) if len(leaf_next) > 21 else
+                                 b.reduce_with_powers_ext([b.to_ext(t) for t in leaf_next], fri_alpha), red[1])
                 q1 = b.div_ext(num1, b.sub_ext(sx_e, zeta_next))
                 old_eval = b.mul_add_ext(q0, alpha_pow_next, q1)
                 xbits = bits
@@ -1739,10 +1909,6 @@ class FrameworkCircuit:
         self.min_log_n, self.extra_gates = max(6, int(min_log_n)), tuple(extra_gates)
 
     def build_base(self, fw, child_proofs, child_vds, memberships, inputs, set_digest, strict=True):
-        if self.num_verifiers and fw.rec.fp.num_lookup_polys:
-            # verify_proof_circuit has no in-circuit lookup argument (check_lookup_constraints_circuit): a circuit with lookup
-            # tables can be proved by prove() but not wrapped or checked by the universal verifier (Limits)
-            raise NotImplementedError("the in-circuit verifier does not check the lookup argument: circuits with lookup tables cannot enter the framework")
         b = Builder(strict)
         set_t = [b.add_virtual(int(x)) for x in set_digest]  # CircuitSetTarget::build_target: a virtual cap of height 0
         child_pis = []
@@ -1797,7 +1963,7 @@ def wrap_proof_chain(prover, fri_params, chain, base, proof):
 
 def dummy_proof(inner):
     fp = inner.fp
-    n_open = sum(fp.oracle_w[o] for o in range(4)) + fp.zs_count
+    n_open = sum(fp.oracle_w[o] for o in range(4)) + fp.zs_count * (1 + fp.num_lookup_polys)
     return (np.zeros((4, 4 << fp.cap_height), dtype=np.uint64), np.zeros((n_open, 2), dtype=np.uint64),
             np.zeros(fp.proof_words, dtype=np.uint64), np.zeros(inner.n_public_inputs, dtype=np.uint64))
 
@@ -1919,6 +2085,7 @@ class RecursiveCircuits:
 # the container here is numpy's .npz -- plain arrays, loaded with allow_pickle=False -- not bincode of plonky2's CircuitData)
 _CKT_ARRAYS = ("pre", "tape", "input_sids", "const_slots", "pi_hash_sids", "public_input_sids", "pi_hash", "public_inputs", "input_values")
 _CKT_SCALARS = ("log_n", "num_selectors", "num_constants", "pi_row", "n_slots", "n_used_rows")
+_LUT_ROWS = ("n_lookups", "last_lu_row", "last_lut_row", "first_lut_row")  # per lookup table of a circuit, next to the table itself
 PARAMS_VERSION = 1
 
 
@@ -1931,6 +2098,11 @@ def circuit_to_arrays(ckt, prefix, out):
                                      dtype=np.uint32).reshape(-1, 7)
     out[prefix + "instances"] = np.asarray(ckt.instances, dtype=np.uint32)
     out[prefix + "domain_separator"] = np.asarray(ckt.domain_separator, dtype=np.uint64)
+    luts = getattr(ckt, "luts", None) or []
+    if luts:  # only a circuit with lookup tables has these entries: a file without one is what it was
+        out[prefix + "lut_rows"] = np.array([[t[k] for k in _LUT_ROWS] for t in luts], dtype=np.int64)
+        for i, t in enumerate(luts):
+            out[prefix + f"lut_table/{i}"] = np.ascontiguousarray(t["table"], dtype=np.uint16).reshape(-1, 2)
 
 
 def circuit_from_arrays(data, prefix):
@@ -1944,6 +2116,10 @@ def circuit_from_arrays(data, prefix):
     ckt.instances = [int(x) for x in data[prefix + "instances"]]
     ckt.domain_separator = [int(x) for x in data[prefix + "domain_separator"]]
     ckt.luts, ckt.num_lookup_selectors, ckt.num_lookup_polys = [], 0, 0
+    if prefix + "lut_rows" in getattr(data, "files", data):
+        for i, row in enumerate(data[prefix + "lut_rows"]):
+            ckt.luts.append({**{k: int(v) for k, v in zip(_LUT_ROWS, row)}, "table": np.array(data[prefix + f"lut_table/{i}"], dtype=np.uint16)})
+        ckt.num_lookup_selectors, ckt.num_lookup_polys = C.LOOKUP_SELECTORS + len(ckt.luts), C.NUM_LOOKUP_POLYS
     ckt.wires = None  # a parameter file holds circuits, not witnesses
     return ckt
 
@@ -2167,6 +2343,50 @@ def reduce_logic(b, child_pis, inputs):
     for pis in child_pis:
         acc = b.add(acc, pis[0])
     return [acc] + b.hash_n_to_m_no_pad([t for pis in child_pis for t in pis[1:5]], 4)
+
+
+# ---- a leaf with lookup tables: the byte realignment of the values-extraction column gadget ---------------------------------------
+def add_bits_lookup_tables(b):
+    """the 14 tables mp2-v1/src/values_extraction/gadgets/column_gadget.rs:53-68 registers: first_bits_n and last_bits_n of a byte
+    as big-endian integers for n = 1..7, over the inputs 0..=255 (first_bits_5: 0..=263, last_bits_3: 0..=256). Returns
+    (first-bits table indices, last-bits table indices), entry n - 1 for n bits."""
+    first = [b.add_lookup_table_from_fn(lambda v, n=n: v >> (8 - n), range(256 + (8 if n == 5 else 0))) for n in range(1, 8)]
+    last = [b.add_lookup_table_from_fn(lambda v, n=n: v & ((1 << n) - 1), range(256 + (1 if n == 3 else 0))) for n in range(1, 8)]
+    return first, last
+
+
+def column_realign_logic(b, child_pis, inputs):
+    """the byte-realignment half of extract_value_target (column_gadget.rs:166-203): inputs = 32 value bytes and a bit offset j in
+    0..7; aligned byte i = last_bits_(8-j)(byte i) 2^j + first_bits_j(byte i + 1) (0 after the last byte), chosen among its 8
+    candidates by a random access on j. Public inputs: the 32 aligned bytes packed big-endian into 8 u32 limbs
+    (column_realign_value is the off-circuit twin). 441 lookups over the 14 tables."""
+    ins = [b.add_virtual(int(x)) for x in (inputs if inputs is not None else [0] * 33)]
+    value, offset = ins[:32], ins[32]
+    first, last = add_bits_lookup_tables(b)
+    zero = b.zero()
+    aligned = []
+    for i in range(32):
+        cur = value[i]
+        candidates = [cur]
+        for j in range(7):
+            first_part = b.add_lookup_from_index(value[i + 1], first[j]) if i < 31 else zero
+            last_part = b.add_lookup_from_index(cur, last[6 - j])
+            candidates.append(b.mul_const_add(1 << (j + 1), last_part, first_part))
+        aligned.append(b.random_access(offset, candidates + [zero] * 8))
+    limbs = []
+    for k in range(8):
+        acc = aligned[4 * k]
+        for t in aligned[4 * k + 1:4 * k + 4]:
+            acc = b.mul_const_add(256, acc, t)
+        limbs.append(acc)
+    return limbs
+
+
+def column_realign_value(value_bytes, offset):
+    """column_realign_logic off the circuit: the 256-bit big-endian value shifted left by `offset` bits, truncated to 256 bits, as
+    8 big-endian u32 limbs"""
+    v = (int.from_bytes(bytes(int(x) for x in value_bytes), "big") << int(offset)) & ((1 << 256) - 1)
+    return [(v >> (32 * (7 - k))) & 0xFFFFFFFF for k in range(8)]
 
 
 # ---- batched generate_proof: the recorded witness programs instead of the Python builder --------------------------------------------
