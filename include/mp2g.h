@@ -518,13 +518,14 @@ uint32_t mp2g_gate_table_line_points(const mp2g_gate* gates, uint32_t n_gates, u
  * (3) Two instructions must not write the same wire with different values (they may run in either order on the device).
  * (4) MP2G_OP_PAR brackets sections that neither read each other's written slots nor write the same slots or wires.
  *
- * OPCODES come in three blocks: the base set [1, MP2G_OP_END) of enum mp2g_witness_op, the GF(p^5) set [32, MP2G_OP_GF5_END)
- * of enum mp2g_witness_op_gf5 and the lookup set [40, MP2G_OP_LUT_END) of enum mp2g_witness_op_lut; every other value (0,
- * MP2G_OP_END .. 31, MP2G_OP_GF5_END .. 39, MP2G_OP_LUT_END and above) is refused.
+ * OPCODES come in four blocks: the base set [1, MP2G_OP_END) of enum mp2g_witness_op, the GF(p^5) set [32, MP2G_OP_GF5_END)
+ * of enum mp2g_witness_op_gf5, the lookup set [40, MP2G_OP_LUT_END) of enum mp2g_witness_op_lut and the wide set
+ * [48, MP2G_OP_WIDE_END) of enum mp2g_witness_op_wide; every other value (0, MP2G_OP_END .. 31, MP2G_OP_GF5_END .. 39,
+ * MP2G_OP_LUT_END .. 47, MP2G_OP_WIDE_END and above) is refused.
  *
  * What mp2g_witness_program_create VALIDATES (a tape that fails is refused with a message, nothing is run): every opcode
- * is known, no instruction is truncated, every row < 2^log_n, every column < 135, gate-operation indices and counts are in
- * the ranges given below, constants are canonical, every slot operand, input slot and constant slot is < n_slots,
+ * is known, no instruction is truncated, every row < 2^log_n, every column < 135, gate-operation indices, limb counts and
+ * other counts are in the ranges given below, constants are canonical, every slot operand, input slot and constant slot is < n_slots,
  * parallel regions do not nest and their section lengths end on instruction boundaries. It does NOT check that the
  * values satisfy the circuit: that is prove()'s witness check (mp2g_prover_enable_witness_check), which fails the proof
  * the way plonky2's prove() panics on an unsatisfied witness. */
@@ -635,6 +636,38 @@ enum mp2g_witness_op_lut {
    * wires 2i, 2i+1 = input, output. */
   MP2G_OP_LOOKUP = 40,
   MP2G_OP_LUT_END = 41 /* one past the last opcode of the lookup set */
+};
+/* The wide block: the bit-interleaving gates of [dep] plonky2_crypto (u32/gates/interleave_u32.rs, uninterleave_to_b32.rs,
+ * uninterleave_to_u32.rs: what its xor / and of u32 words are built from), the multi-limb division hints (UInt256DivGenerator,
+ * mp2-common/src/u256.rs:920-952; [dep] plonky2_ecdsa BigUintDivRemGenerator) and PoseidonMdsGate's generator. Bit wires are
+ * most significant first. A multi-limb integer is a run of u32 limbs, least significant first, one slot each; a limb operand is
+ * read as the low 32 bits of its slot (a circuit's range checks catch a wider value). None of these instructions fails a replay:
+ * a value that cannot satisfy the circuit fails that proof in prove()'s witness check, as with the hints above. */
+enum mp2g_witness_op_wide {
+  /* U32InterleaveGate with `ops` operations a row / U32InterleaveGenerator: x_interleaved = sum_k b_k 4^k, b_k = bit k of the low
+   * 32 bits of x.   operands: row, i (< ops), ops (1..3), s_x, d_x_interleaved.   wires 2i, 2i+1 = x, x_interleaved; wire
+   * 2 ops + 32 i + j = b_(31-j). */
+  MP2G_OP_U32_INTERLEAVE = 48,
+  /* UninterleaveToB32Gate / UninterleaveToB32Generator: evens = sum_b bit(2b) 4^b, odds = sum_b bit(2b+1) 4^b over the 64 bits of
+   * x_interleaved, b = 0..31.   operands: row, i (< ops), ops (1..2), s_x_interleaved, d_evens, d_odds.   wires 3i, 3i+1, 3i+2 =
+   * x_interleaved, evens, odds; wire 3 ops + 64 i + j = bit (63-j). */
+  MP2G_OP_UNINTERLEAVE_TO_B32 = 49,
+  /* UninterleaveToU32Gate / UninterleaveToU32Generator: as MP2G_OP_UNINTERLEAVE_TO_B32 with weights 2^b instead of 4^b (the even
+   * bits and the odd bits as two u32 words: of the sum of two interleaved words, the xor and the and). */
+  MP2G_OP_UNINTERLEAVE_TO_U32 = 50,
+  /* UInt256DivGenerator::run_once, branch by branch. is_div != 0 and divisor != 0: (quotient, remainder) = divmod(dividend,
+   * divisor). is_div != 0 and divisor = 0: (0, dividend). is_div = 0: quotient = 1 and remainder = dividend - dividend divisor
+   * mod 2^256 (so that quotient' divisor + remainder = dividend holds for quotient' = dividend, as mul_div_u256 then checks).
+   * operands: s_dividend[8], s_divisor[8], s_is_div, d_quotient[8], d_remainder[8].   no wires. */
+  MP2G_OP_U256_DIV = 51,
+  /* BigUintDivRemGenerator: (div, rem) = divmod(a, b) over na and nb limbs; b = 0 gives (0, a truncated to nb limbs) -- this
+   * library's choice: [dep] plonky2_ecdsa's generator panics on a zero divisor. rem < b fits nb limbs, div <= a fits na.
+   * operands: na (1..32), nb (1..32), s_a[na], s_b[nb], d_div[na], d_rem[nb].   no wires. */
+  MP2G_OP_BIGUINT_DIV_REM = 52,
+  /* PoseidonMdsGate / PoseidonMdsGenerator: Poseidon's MDS layer applied to 12 extension elements, component by component.
+   * operands: row, s_in[12][2], d_out[12][2].   wires 2i, 2i+1 = input i; wires 24 + 2i, 24 + 2i + 1 = output i. */
+  MP2G_OP_POSEIDON_MDS = 53,
+  MP2G_OP_WIDE_END = 54 /* one past the last opcode of the wide set */
 };
 /* create: the tape is copied. input_sids [n_inputs]: the slots the caller provides per proof, in the order of the proof's input
  * words (a framework circuit: the circuit-set digest, then per verified child its verifier data, public inputs, caps, openings, FRI

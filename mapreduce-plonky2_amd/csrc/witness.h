@@ -20,6 +20,12 @@ GLHD bool op_is_gf5(u64 op) { return op >= OP_QUINTIC_SQRT && op < OP_GF5_END; }
 // the third block (include/mp2g.h enum mp2g_witness_op_lut): lookups into the circuit's tables (mp2g_witness_program_set_lookups)
 enum { OP_LOOKUP = MP2G_OP_LOOKUP, OP_LUT_END = MP2G_OP_LUT_END };
 GLHD bool op_is_lut(u64 op) { return op >= OP_LOOKUP && op < OP_LUT_END; }
+// the fourth block (include/mp2g.h enum mp2g_witness_op_wide): interleave gates, multi-limb division hints, PoseidonMds; witness_wide.h
+enum { OP_U32_INTERLEAVE = MP2G_OP_U32_INTERLEAVE, OP_UNINTERLEAVE_TO_B32 = MP2G_OP_UNINTERLEAVE_TO_B32,
+       OP_UNINTERLEAVE_TO_U32 = MP2G_OP_UNINTERLEAVE_TO_U32, OP_U256_DIV = MP2G_OP_U256_DIV, OP_BIGUINT_DIV_REM = MP2G_OP_BIGUINT_DIV_REM,
+       OP_POSEIDON_MDS = MP2G_OP_POSEIDON_MDS, OP_WIDE_END = MP2G_OP_WIDE_END };
+GLHD bool op_is_wide(u64 op) { return op >= OP_U32_INTERLEAVE && op < OP_WIDE_END; }
+const u32 BIGUINT_MAX_LIMBS = 32;  // MP2G_OP_BIGUINT_DIV_REM: limbs of either operand
 const u32 BASE_SUM_LIMBS = 63, RA_BITS = 4, RA_COPIES = 4, RED_COEFFS = 43, RED_EXT_COEFFS = 32, NUM_WIRES = 135;
 
 // the program's read-only data on one device (uploaded at the first device run there)
@@ -32,9 +38,12 @@ struct WitnessDev {
   LutIndex lut{};
 };
 // device executor (witness_dev.hip): one block per proof walks the level schedule; gf5 = the program holds GF(p^5) opcodes (a tape
-// without them runs the kernel instance that has no code for them)
+// without them runs the kernel instance that has no code for them). witness_exec_launch_wide (witness_dev_wide.hip): the same for a
+// program that holds wide opcodes, with the instances that carry their code.
 hipError_t witness_exec_launch(hipStream_t s, const WitnessDev& d, bool gf5, u32 n_levels, u32 n_slots, u32 log_n, u32 n_inputs, u32 n_consts,
                                u32 n_probe, const u64* d_inputs, u32 batch, u64* d_vals, u64* d_wires, u64* d_probe_out);
+hipError_t witness_exec_launch_wide(hipStream_t s, const WitnessDev& d, bool gf5, u32 n_levels, u32 n_slots, u32 log_n, u32 n_inputs, u32 n_consts,
+                                    u32 n_probe, const u64* d_inputs, u32 batch, u64* d_vals, u64* d_wires, u64* d_probe_out);
 const u32 WIT_LU_SLOTS = 40, WIT_LUT_SLOTS = 26;  // LookupGate / LookupTableGate num_slots with 80 routed wires
 }  // namespace mp2g
 
@@ -50,6 +59,7 @@ struct mp2g_witness_program {
   std::vector<u32> level_p2;  // per level: first schedule index and count of its Poseidon2 rows (one opcode = one contiguous run)
   bool ssa = true;
   bool gf5 = false;        // the tape holds GF(p^5) opcodes (include/mp2g.h enum mp2g_witness_op_gf5)
+  bool wide = false;       // the tape holds wide opcodes (include/mp2g.h enum mp2g_witness_op_wide)
   // lookup tables (mp2g_witness_program_set_lookups): the copied tables, their input index, and the description the host replay
   // and its lookup-wires pass read (host pointers into the two vectors)
   bool has_lookup = false;  // the tape holds MP2G_OP_LOOKUP

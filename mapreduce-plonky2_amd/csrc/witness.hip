@@ -15,6 +15,7 @@
 #include "witness.h"
 #include "witness_ops.h"
 #include "witness_gf5.h"
+#include "witness_wide.h"
 #include <algorithm>
 #include <atomic>
 #include <cstring>
@@ -182,10 +183,10 @@ void exec(const mp2g_witness_program& P, const u64* t, const u64* end, u64* vals
         for (int i = 0; i < 12; i++) { W(12 + i, row) = s[i]; vals[t[14 + i]] = s[i]; }
         break;
       }
-      default: {  // every other opcode has one body, shared with the device executor (witness_ops.h, witness_gf5.h)
+      default: {  // every other opcode has one body, shared with the device executor (witness_ops.h, witness_gf5.h, witness_wide.h)
         const auto put = [&](u64 col, u64 row, u64 v) { W(col, row) = v; };
         if (!exec_core_op(op, t, vals, put, &P.dom[0][0], &P.bw[0][0]) && !exec_gate_op(op, t, vals, put) && !exec_gf5_op(op, t, vals) &&
-            !exec_lut_op(op, t, vals, put, P.lut)) return;  // refused at create (MP2G_OP_LOOKUP without tables: at run)
+            !exec_lut_op(op, t, vals, put, P.lut) && !exec_wide_op(op, t, vals, put)) return;  // refused at create (MP2G_OP_LOOKUP without tables: at run)
         break;
       }
     }
@@ -233,9 +234,10 @@ static int witness_program_create(const uint64_t* tape, size_t tape_len, uint32_
       if (t >= par_end) { par_end = nullptr; boundaries.clear(); next_boundary = 0; }
     }
     const u64 op = *t++;
-    if ((op < OP_ARITH || op >= OP_END) && !op_is_gf5(op) && !op_is_lut(op)) return bad("unknown opcode");
+    if ((op < OP_ARITH || op >= OP_END) && !op_is_gf5(op) && !op_is_lut(op) && !op_is_wide(op)) return bad("unknown opcode");
     if (op_is_gf5(op)) P->gf5 = true;
     if (op_is_lut(op)) P->has_lookup = true;
+    if (op_is_wide(op)) P->wide = true;
     if (op == OP_PAR && par_end) return bad("parallel regions do not nest");
     const OpShape shape = op_shape(op, t, (size_t)(end - t));
     const u32 len = shape.len;
@@ -275,6 +277,10 @@ static int witness_program_create(const uint64_t* tape, size_t tape_len, uint32_
       // the table's own rows are known at mp2g_witness_program_set_lookups, which checks the row against them
       case OP_LOOKUP: if (t[0] >= n || t[1] >= WIT_LU_SLOTS || t[2] >= MP2G_MAX_LUTS) return bad("Lookup operands"); break;
       case OP_MUL_EXT: if (t[0] >= n || t[1] >= 13 || t[2] >= GL_P) return bad("MulExtension operands"); break;
+      // 2 ops + 32 ops = 102 and 3 ops + 64 ops = 134 wires at the most (the limb counts of MP2G_OP_BIGUINT_DIV_REM: op_shape)
+      case OP_U32_INTERLEAVE: if (t[0] >= n || t[2] < 1 || t[2] > 3 || t[1] >= t[2]) return bad("U32Interleave operands"); break;
+      case OP_UNINTERLEAVE_TO_B32: case OP_UNINTERLEAVE_TO_U32: if (t[0] >= n || t[2] < 1 || t[2] > 2 || t[1] >= t[2]) return bad("Uninterleave operands"); break;
+      case OP_POSEIDON_MDS: if (t[0] >= n) return bad("row"); break;
       default: break;
     }
     for (u32 i = shape.first_slot; i < len; i++) if (t[i] >= n_slots) return bad("slot out of range");
@@ -487,7 +493,7 @@ int mp2g_witness_program_run_dev(mp2g_witness_program* P, mp2g_ctx* c, const uin
   CK(hipMemsetAsync(c->wit_rows.p, 0, wire_words * 8, c->stream));
   // the executor fills a row-major staging matrix (one contiguous run of words per gate row); the prover's polynomial-major
   // [batch][135][n] is made from it by the tiled transpose (every word of d_wires is written)
-  CK(witness_exec_launch(c->stream, *d, P->gf5, (u32)P->level_off.size() - 1, P->n_slots, P->log_n, (u32)P->input_sids.size(), (u32)(P->consts.size() / 2),
+  CK((P->wide ? witness_exec_launch_wide : witness_exec_launch)(c->stream, *d, P->gf5, (u32)P->level_off.size() - 1, P->n_slots, P->log_n, (u32)P->input_sids.size(), (u32)(P->consts.size() / 2),
                           (u32)P->probe.size(), (const u64*)d_inputs, batch, c->wit_vals.p, c->wit_rows.p, (u64*)d_probe_out));
   // prove()'s set_lookup_wires on the staging matrix, where a LookupGate row is contiguous (lookup_wires.hip)
   CK(lookup_wires_launch(c->stream, d->lut, c->wit_rows.p, batch, (u64)NUM_WIRES << P->log_n, 1, NUM_WIRES));

@@ -9,12 +9,25 @@
 // levels. Values live in a per-proof slot table in global memory (written once each: SSA), wires go into a row-major staging
 // matrix [B][n][135] (a gate row's wires are one contiguous run) that witness.hip transposes into the prover's [B][135][n]. Arithmetic is gl.cuh / poseidon.cuh: the Poseidon2 gate's S-box inputs are the weak
 // representatives of the sponge kernels, canonicalised where they become wires.
+//
+// This file is compiled TWICE: as itself, and from witness_dev_wide.hip with MP2G_WITNESS_WIDE set, which gives the instances that
+// also carry the wide block (include/mp2g.h enum mp2g_witness_op_wide, witness_wide.h) under names of their own
+// (witness_exec_kernel_wide, witness_exec_launch_wide). The wide instances sit in an object of their own so that this one --
+// code, layout and the PC-relative addresses of its constants -- is what it was before they existed.
+#ifndef MP2G_WITNESS_WIDE
+#define MP2G_WITNESS_WIDE 0
+#endif
 #include "gl.cuh"
 #include "poseidon.cuh"
 #include "poseidon_wave.cuh"
 #include "witness.h"
 #include "witness_ops.h"
 #include "witness_gf5.h"
+#if MP2G_WITNESS_WIDE
+#include "witness_wide.h"
+#define witness_exec_kernel witness_exec_kernel_wide
+#define witness_exec_launch witness_exec_launch_wide
+#endif
 
 namespace mp2g {
 namespace {
@@ -159,8 +172,8 @@ GLD void exec_one(const u64* t, u64* vals, u64* wires, u64 n, const u64* domtab,
   switch (op) {
     case OP_P2: exec_p2(t, vals, wires, n); break;
     case OP_POSEIDON: exec_poseidon(t, vals, wires, n); break;
-    default: {  // every other opcode has one body, shared with the host executor (witness_ops.h, witness_gf5.h); anything else was
-                // refused at create
+    default: {  // every other opcode has one body, shared with the host executor (witness_ops.h, witness_gf5.h, witness_wide.h);
+                // anything else was refused at create
       const auto put = [wires](u64 col, u64 row, u64 v) { W(col, row) = v; };
       if (exec_core_op(op, t, vals, put, domtab, domtab + 6 * 32)) break;
       if constexpr (GF5) {
@@ -169,6 +182,9 @@ GLD void exec_one(const u64* t, u64* vals, u64* wires, u64 n, const u64* domtab,
       if constexpr (LUT) {
         if (exec_lut_op(op, t, vals, put, *lut)) break;
       }
+#if MP2G_WITNESS_WIDE
+      if (exec_wide_op(op, t, vals, put)) break;
+#endif
       exec_gate_op(op, t, vals, put);
       break;
     }
@@ -179,7 +195,8 @@ GLD void exec_one(const u64* t, u64* vals, u64* wires, u64 n, const u64* domtab,
 constexpr int WIT_LANES = 512;
 // GF5: the program holds GF(p^5) opcodes. Only that instance carries their code (the field's square root and inverse are long
 // out-of-line bodies); a tape without them runs the instance that is the kernel as it was before they existed. LUT: the same for
-// MP2G_OP_LOOKUP, whose tables `lut` describes (device memory).
+// MP2G_OP_LOOKUP, whose tables `lut` describes (device memory). The wide block is the third such flag, MP2G_WITNESS_WIDE of the
+// head of this file: its divisions keep multi-limb integers per lane, MP2G_OP_BIGUINT_DIV_REM in private memory.
 template <bool GF5, bool LUT>
 __global__ void __launch_bounds__(WIT_LANES) witness_exec_kernel(const u64* __restrict__ tape, const u32* __restrict__ sched,
                                                                 const u32* __restrict__ level_off, const u32* __restrict__ level_p2, u32 n_levels, u32 n_slots, u32 log_n,

@@ -1,7 +1,7 @@
-// What a witness-tape instruction IS (include/mp2g.h enum mp2g_witness_op, enum mp2g_witness_op_gf5, enum mp2g_witness_op_lut), defined ONCE for the host
+// What a witness-tape instruction IS (include/mp2g.h enum mp2g_witness_op, _gf5, _lut, _wide), defined ONCE for the host
 // (witness.hip: validation, level schedule, replay) and the device replay (witness_dev.hip): op_shape gives an instruction's length
 // and operand roles, exec_core_op replays the recursion circuits' opcodes (MP2G_OP_ARITH .. MP2G_OP_HINT_SPLIT), exec_gate_op the
-// leaf-circuit gates (MP2G_OP_U32_ARITH .. MP2G_OP_EXP; the GF(p^5) hints are witness_gf5.h). The gate generators restate
+// leaf-circuit gates (MP2G_OP_U32_ARITH .. MP2G_OP_EXP; the GF(p^5) hints are witness_gf5.h, the wide block witness_wide.h). The gate generators restate
 // mp2-common/src/serialization/circuit_data_serialization.rs:186-231 -- [dep] plonky2-u32 gates/{arithmetic_u32, subtraction_u32,
 // add_many_u32, range_check_u32, comparison}.rs, plonky2 gates/{base_sum, multiplication_extension, exponentiation}.rs -- with the
 // wire layouts of the gate evaluators (gates.hip / oracle/gates_body.inc). t = the operands after the opcode, vals = the proof's
@@ -52,6 +52,16 @@ GLHD OpShape op_shape(u64 op, const u64* t, size_t left) {
     case OP_QUINTIC_SQRT: return {11, 0, 0, 5, 5, 6};
     case OP_QUINTIC_QUOTIENT: return {15, 0, 0, 10, 10, 5};
     case OP_LOOKUP: return {5, 3, 3, 1, 4, 1};  // row, slot of the LookupGate row, table, input, output
+    // the wide block (bodies: witness_wide.h)
+    case OP_U32_INTERLEAVE: return {5, 3, 3, 1, 4, 1};  // row, operation, operations, x, x interleaved
+    case OP_UNINTERLEAVE_TO_B32: case OP_UNINTERLEAVE_TO_U32: return {6, 3, 3, 1, 4, 2};  // row, operation, operations, x interleaved, evens, odds
+    case OP_U256_DIV: return {33, 0, 0, 17, 17, 16};  // dividend[8], divisor[8], is_div, quotient[8], remainder[8]
+    case OP_BIGUINT_DIV_REM: {  // limbs of a, limbs of b, a, b, div (as many limbs as a), rem (as many as b)
+      if (left < 2 || t[0] < 1 || t[0] > BIGUINT_MAX_LIMBS || t[1] < 1 || t[1] > BIGUINT_MAX_LIMBS) return malformed;
+      const u32 nl = (u32)t[0] + (u32)t[1];
+      return {2 + 2 * nl, 2, 2, nl, 2 + nl, nl};
+    }
+    case OP_POSEIDON_MDS: return {49, 1, 1, 24, 25, 24};  // row, 12 extension inputs, 12 extension outputs
     default: return malformed;
   }
 }

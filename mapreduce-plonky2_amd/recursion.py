@@ -24,6 +24,7 @@ from . import Gate, MULT_GEN
 from . import circuits as C
 from . import gf5
 from . import lut
+from . import wideops
 
 P = C.P
 W7 = 7  # quadratic extension X^2 = 7
@@ -80,7 +81,8 @@ class T:
  # the leaf circuits' user-logic gates (round 6; include/mp2g.h enum mp2g_witness_op documents every operand layout)
  OP_U32_ARITH, OP_U32_SUB, OP_U32_ADD_MANY, OP_U32_RANGE_CHECK, OP_COMPARISON, OP_BASE_SPLIT, OP_MUL_EXT, OP_EXP) = range(1, 24)
 # The GF(p^5) hints are the header's second block (enum mp2g_witness_op_gf5, 32..33): gf5.OP_QUINTIC_SQRT, gf5.OP_QUINTIC_QUOTIENT.
-# The lookup is its third (enum mp2g_witness_op_lut, 40): lut.OP_LOOKUP.
+# The lookup is its third (enum mp2g_witness_op_lut, 40): lut.OP_LOOKUP. The wide block is its fourth (enum mp2g_witness_op_wide,
+# 48..53): wideops.OP_U32_INTERLEAVE .. wideops.OP_POSEIDON_MDS.
 
 
 class E:
@@ -116,7 +118,7 @@ def _block(per, limbs):
 # What an instruction IS, for the builder (no native library here): csrc/witness_ops.h op_shape is the same table for the executors,
 # and tests/test_witness_shape_host.py holds the two together. Per opcode: (count, shape, cells). shape = (len, r0, nr, w0, nw):
 # len operands follow the opcode, the instruction reads the slots t[r0:r0 + nr] and writes t[w0:w0 + nw]; for a variable-length
-# instruction shape is a function of its count operand t[count]. cells(t) = the (row, column) wire cells it writes (None: OP_PAR,
+# instruction shape is a function of its count operand t[count] (of its count operands, where count is a tuple). cells(t) = the (row, column) wire cells it writes (None: OP_PAR,
 # which only brackets the sections that follow it).
 _OPS = {
     OP_ARITH: (None, (8, 4, 3, 7, 1), lambda t: [(t[0], 4 * t[1] + k) for k in range(4)]),
@@ -145,6 +147,12 @@ _OPS = {
     gf5.OP_QUINTIC_SQRT: (None, (11, 0, 5, 5, 6), lambda t: []),
     gf5.OP_QUINTIC_QUOTIENT: (None, (15, 0, 10, 10, 5), lambda t: []),
     lut.OP_LOOKUP: (None, (5, 3, 1, 4, 1), lambda t: [(t[0], 2 * t[1]), (t[0], 2 * t[1] + 1)]),
+    wideops.OP_U32_INTERLEAVE: (None, (5, 3, 1, 4, 1), _block(2, 32)),
+    wideops.OP_UNINTERLEAVE_TO_B32: (None, (6, 3, 1, 4, 2), _block(3, 64)),
+    wideops.OP_UNINTERLEAVE_TO_U32: (None, (6, 3, 1, 4, 2), _block(3, 64)),
+    wideops.OP_U256_DIV: (None, (33, 0, 17, 17, 16), lambda t: []),
+    wideops.OP_BIGUINT_DIV_REM: ((0, 1), lambda na, nb: (2 + 2 * (na + nb), 2, na + nb, 2 + na + nb, na + nb), lambda t: []),
+    wideops.OP_POSEIDON_MDS: (None, (49, 1, 24, 25, 24), lambda t: [(t[0], c) for c in range(48)]),
 }
 
 
@@ -154,7 +162,9 @@ def _op_shape(tape, pos):
     if op not in _OPS:
         raise ValueError(f"opcode {op}")
     count, shape, _ = _OPS[op]
-    return shape if count is None else shape(int(tape[pos + 1 + count]))
+    if count is None:
+        return shape
+    return shape(*[int(tape[pos + 1 + c]) for c in (count if isinstance(count, tuple) else (count,))])
 
 
 def tape_instructions(tape):
@@ -828,6 +838,81 @@ class Builder:
         self.tape += [OP_EXP, row, nb, base.sid] + [bt.sid for bt in bits] + [out.sid]
         return out
 
+    # ---- the wide block (wideops.py; csrc/witness_wide.h replays these on host and device) -------------------------------------------
+    def u32_interleave(self, x, ops=3):
+        """U32InterleaveGate(ops) / U32InterleaveGenerator: bit k of the u32 x at bit 2k. Returns x_interleaved."""
+        row, i = self._slot(("u32interleave", ops), ops, lambda: self._new_row(C.U32_INTERLEAVE, ops))
+        self._put(row, 2 * i, x)
+        out = self._out(row, 2 * i + 1, wideops.interleave(x.v))
+        w = self.rows[row].wires
+        for j in range(32):  # bit wires most significant first
+            w[2 * ops + 32 * i + j] = (x.v >> (31 - j)) & 1
+        self.tape += [wideops.OP_U32_INTERLEAVE, row, i, ops, x.sid, out.sid]
+        return out
+
+    def _uninterleave(self, kind, op, fn, x, ops):
+        row, i = self._slot(("uninterleave", kind, ops), ops, lambda: self._new_row(kind, ops))
+        self._put(row, 3 * i, x)
+        ev, od = fn(x.v)
+        tev, tod = self._out(row, 3 * i + 1, ev), self._out(row, 3 * i + 2, od)
+        w = self.rows[row].wires
+        for j in range(64):
+            w[3 * ops + 64 * i + j] = (x.v >> (63 - j)) & 1
+        self.tape += [op, row, i, ops, x.sid, tev.sid, tod.sid]
+        return tev, tod
+
+    def uninterleave_to_b32(self, x, ops=2):
+        """UninterleaveToB32Gate(ops) / UninterleaveToB32Generator: the bits of even and of odd weight of a 64-bit value, each left
+        spread (bit 2b). Returns (evens, odds)."""
+        return self._uninterleave(C.UNINTERLEAVE_TO_B32, wideops.OP_UNINTERLEAVE_TO_B32, wideops.uninterleave_b32, x, ops)
+
+    def uninterleave_to_u32(self, x, ops=2):
+        """UninterleaveToU32Gate(ops) / UninterleaveToU32Generator: the same, packed into two u32 words. Returns (evens, odds)."""
+        return self._uninterleave(C.UNINTERLEAVE_TO_U32, wideops.OP_UNINTERLEAVE_TO_U32, wideops.uninterleave_u32, x, ops)
+
+    def xor_and_u32(self, a, b):
+        """[dep] plonky2_crypto's u32 logic: interleave both words, add -- bit 2k of the sum is a_k xor b_k, bit 2k + 1 is a_k and
+        b_k, and 2 * 0x5555555555555555 is below p -- and uninterleave. The interleave gates range-check a and b. Returns (xor, and)."""
+        return self.uninterleave_to_u32(self.add(self.u32_interleave(a), self.u32_interleave(b)))
+
+    def xor_u32(self, a, b):
+        return self.xor_and_u32(a, b)[0]
+
+    def and_u32(self, a, b):
+        return self.xor_and_u32(a, b)[1]
+
+    def u256_div_hint(self, a, b, is_div):
+        """UInt256DivGenerator (mp2-common/src/u256.rs:920-952) over two lists of 8 u32 limb targets, least significant first, and a
+        boolean target: (quotient limbs, remainder limbs). Witness values only -- u256.mul_div_u256 places the constraints."""
+        assert len(a) == len(b) == wideops.U256_LIMBS
+        qv, rv = wideops.u256_div(wideops.from_limbs(t.v for t in a), wideops.from_limbs(t.v for t in b), is_div.v != 0)
+        q = [self._hint(v) for v in wideops.to_limbs(qv, 8)]
+        r = [self._hint(v) for v in wideops.to_limbs(rv, 8)]
+        self.tape += [wideops.OP_U256_DIV] + [t.sid for t in a] + [t.sid for t in b] + [is_div.sid] + [t.sid for t in q] + [t.sid for t in r]
+        return q, r
+
+    def biguint_div_rem_hint(self, a, b):
+        """[dep] plonky2_ecdsa BigUintDivRemGenerator over lists of 1..32 u32 limb targets: (div limbs, as many as a has; rem limbs, as
+        many as b has). Witness values only. b = 0 gives (0, a cut to b's limbs), where the generator of plonky2_ecdsa panics."""
+        na, nb = len(a), len(b)
+        assert 1 <= na <= wideops.BIGUINT_MAX_LIMBS and 1 <= nb <= wideops.BIGUINT_MAX_LIMBS
+        dv, rv = wideops.biguint_div_rem(wideops.from_limbs(t.v for t in a), wideops.from_limbs(t.v for t in b), nb)
+        d = [self._hint(v) for v in wideops.to_limbs(dv, na)]
+        r = [self._hint(v) for v in wideops.to_limbs(rv, nb)]
+        self.tape += [wideops.OP_BIGUINT_DIV_REM, na, nb] + [t.sid for t in a] + [t.sid for t in b] + [t.sid for t in d] + [t.sid for t in r]
+        return d, r
+
+    def poseidon_mds_row(self, inputs):
+        """PoseidonMdsGate / PoseidonMdsGenerator: Poseidon's MDS layer on 12 extension targets, component by component"""
+        assert len(inputs) == 12
+        row = self._new_row(C.POSEIDON_MDS)
+        for i, e in enumerate(inputs):
+            self._put(row, 2 * i, e.a), self._put(row, 2 * i + 1, e.b)
+        o = [C.poseidon_mds([e.v[c] for e in inputs]) for c in range(2)]
+        outs = [E(self._out(row, 24 + 2 * i, o[0][i]), self._out(row, 24 + 2 * i + 1, o[1][i])) for i in range(12)]
+        self.tape += [wideops.OP_POSEIDON_MDS, row] + [t.sid for e in inputs for t in (e.a, e.b)] + [t.sid for e in outs for t in (e.a, e.b)]
+        return outs
+
     # ---- RandomAccessGate (bits 4, 4 copies, 2 extra constants) ---------------------------------------------------------------
     def random_access(self, index, values):
         assert len(values) == 1 << self.RA_BITS
@@ -1378,6 +1463,8 @@ def eval_gate_circuit(b, g, consts, wires, pih):
         return out
     if k in (C.U32_ARITHMETIC, C.U32_RANGE_CHECK, C.U32_SUBTRACTION, C.U32_ADD_MANY, C.COMPARISON):
         return eval_u32_gate_circuit(b, g, wires)
+    if k in (C.U32_INTERLEAVE, C.UNINTERLEAVE_TO_B32, C.UNINTERLEAVE_TO_U32):
+        return eval_interleave_gate_circuit(b, g, wires)
     raise NotImplementedError(f"no in-circuit evaluator for gate kind {k}")
 
 
@@ -1470,6 +1557,23 @@ def eval_u32_gate_circuit(b, g, wires):
     out += [b.mul_ext(x, b.sub_ext(one, x)) for x in bits]
     out.append(b.sub_ext(b.add_const_ext(wires[3], cs), bc))
     out.append(b.sub_ext(wires[2], bits[cb]))
+    return out
+
+
+def eval_interleave_gate_circuit(b, g, wires):
+    """[dep] plonky2_crypto's bit-interleaving gates, constraint by constraint in the order of csrc/gates.hip / oracle/gates_body.inc:
+    per operation the booleanity of its bit wires (most significant first), then the weighted sums against its routed wires"""
+    ops, one, out = g.p0, b.one_ext(), []
+    per, nbits = (2, 32) if g.kind == C.U32_INTERLEAVE else (3, 64)
+    for i in range(ops):
+        bits = [wires[per * ops + nbits * i + j] for j in range(nbits)]
+        out += [b.mul_ext(x, b.sub_ext(one, x)) for x in bits]
+        if g.kind == C.U32_INTERLEAVE:  # x = sum b_k 2^k, x_interleaved = sum b_k 4^k
+            sums = [_limb_sum(b, bits[::-1], 2), _limb_sum(b, bits[::-1], 4)]
+        else:  # bit wire j has weight 2^(63 - j): the odd j are the bits of even weight
+            base = 4 if g.kind == C.UNINTERLEAVE_TO_B32 else 2
+            sums = [_limb_sum(b, bits[::-1], 2), _limb_sum(b, bits[1::2][::-1], base), _limb_sum(b, bits[0::2][::-1], base)]
+        out += [b.sub_ext(sm, wires[per * i + q]) for q, sm in enumerate(sums)]
     return out
 
 
