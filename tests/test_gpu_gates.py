@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import circuits as C
+import field_cases as F
 import oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -37,6 +38,20 @@ def test_constraints_match_oracle_at_random_points(ctx, mp2, kinds):
     want = C.eval_on_points(ckt, consts, wires)
     assert np.array_equal(got, want)
     assert got.any()
+    # edge fills (as test_gpu_gates_extension.py uses for the extension evaluator), then wires AND constants drawn from the canonical
+    # edge lattice of tests/field_cases.py (constants outside the selector rows): uniform operands reach the carry and borrow
+    # branches of the field arithmetic with probability ~2^-32 per operation
+    edge = np.array([0, 1, P - 1], dtype=np.uint64)
+    pick = np.random.default_rng(5).integers(0, 4, size=wires.shape)
+    mixed = np.where(pick < 3, edge[np.minimum(pick, 2)], wires)
+    lattice = np.array(F.EC, dtype=np.uint64)
+    edge_consts = consts.copy()
+    edge_consts[ckt.num_selectors:] = lattice[np.random.default_rng(6).integers(0, len(lattice), size=edge_consts[ckt.num_selectors:].shape)]
+    edge_wires = lattice[np.random.default_rng(7).integers(0, len(lattice), size=wires.shape)]
+    for k, w in ((consts, np.zeros_like(wires)), (consts, np.ones_like(wires)), (consts, np.full_like(wires, P - 1)), (consts, mixed),
+                 (consts, edge_wires), (edge_consts, wires), (edge_consts, edge_wires)):
+        got = mp2.eval_gate_constraints(ctx, gpu_gates(mp2, ckt), ckt.num_selectors, k, w, ckt.pi_hash)
+        assert np.array_equal(got, C.eval_on_points(ckt, k, w))
 
 
 def test_witness_check_on_h(ctx, mp2):
