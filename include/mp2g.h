@@ -396,7 +396,9 @@ typedef struct {
   uint32_t kind, p0, p1, p2;
   uint32_t selector_index, group_start, group_end;
 } mp2g_gate;
-/* Gate::num_constraints / Gate::degree of a descriptor; 0 for an unknown kind */
+/* Gate::num_constraints / Gate::degree of a descriptor; 0 for an unknown kind and for a malformed descriptor: a parameter outside
+ * the range documented above, an operation / slot / limb / coefficient count of 0 where the gate needs one, or a wire or
+ * constraint count that does not fit 32 bits */
 uint32_t mp2g_gate_num_constraints(const mp2g_gate* g);
 uint32_t mp2g_gate_degree(const mp2g_gate* g);
 /* Give the batched prover the gate table: the quotient then carries the gate constraint terms after
@@ -485,7 +487,7 @@ int mp2g_verifier_challenges(mp2g_verifier* v, uint64_t* out, size_t* words_per_
 void mp2g_verifier_free(mp2g_verifier* v);
 /* The number T of base-field points the verifier evaluates the gate constraints at (see DESIGN.md "Verifier"): 1 + the largest
  * degree of a filtered constraint = 1 + max over gates of degree + (selector group size - 1) + (num_selectors > 1). Pure host
- * arithmetic: needs no GPU. 0 for an unknown gate kind. */
+ * arithmetic: needs no GPU. 0 for an unknown gate kind, a malformed descriptor (as for mp2g_gate_degree) or an empty selector group. */
 uint32_t mp2g_gate_table_line_points(const mp2g_gate* gates, uint32_t n_gates, uint32_t num_selectors);
 
 /* ---- witness generation: the witness tape ------------------------------------------------------------------

@@ -15,104 +15,6 @@
 
 namespace mp2g {
 
-u32 gate_num_constraints(const mp2g_gate& g) {
-  switch (g.kind) {
-    case MP2G_GATE_CONSTANT: return g.p0;
-    case MP2G_GATE_PUBLIC_INPUT: return 4;
-    case MP2G_GATE_ARITHMETIC: return g.p0;
-    case MP2G_GATE_BASE_SUM: return 1 + g.p0;
-    case MP2G_GATE_ARITHMETIC_EXT: case MP2G_GATE_MUL_EXT: return 2 * g.p0;
-    case MP2G_GATE_POSEIDON2: case MP2G_GATE_POSEIDON: return 1 + 4 + 36 + 22 + 48 + 12;
-    case MP2G_GATE_POSEIDON_MDS: return 24;
-    case MP2G_GATE_COSET_INTERPOLATION: return 4 + 4 * (((1u << g.p0) - 2) / (g.p1 - 1));
-    case MP2G_GATE_U32_ARITHMETIC: return 36 * g.p0;
-    case MP2G_GATE_U32_RANGE_CHECK: return 17 * g.p0;
-    case MP2G_GATE_U32_SUBTRACTION: return 19 * g.p0;
-    case MP2G_GATE_U32_ADD_MANY: return 21 * g.p1;
-    case MP2G_GATE_COMPARISON: return g.p1 ? 6 + 5 * g.p1 + (g.p0 + g.p1 - 1) / g.p1 : 0;
-    case MP2G_GATE_EXPONENTIATION: return g.p0 + 1;
-    case MP2G_GATE_REDUCING: case MP2G_GATE_REDUCING_EXT: return 2 * g.p0;
-    case MP2G_GATE_RANDOM_ACCESS: return (g.p0 + 2) * g.p1 + g.p2;
-    case MP2G_GATE_U32_INTERLEAVE: return 34 * g.p0;
-    case MP2G_GATE_UNINTERLEAVE_TO_B32: case MP2G_GATE_UNINTERLEAVE_TO_U32: return 67 * g.p0;
-    default: return 0;  // Noop, Lookup, LookupTable
-  }
-}
-u32 gate_degree(const mp2g_gate& g) {
-  switch (g.kind) {
-    case MP2G_GATE_CONSTANT: case MP2G_GATE_PUBLIC_INPUT: return 1;
-    case MP2G_GATE_ARITHMETIC: case MP2G_GATE_ARITHMETIC_EXT: case MP2G_GATE_MUL_EXT: return 3;
-    case MP2G_GATE_BASE_SUM: return g.p1;
-    case MP2G_GATE_POSEIDON2: case MP2G_GATE_POSEIDON: return 7;
-    case MP2G_GATE_POSEIDON_MDS: return 1;
-    case MP2G_GATE_COSET_INTERPOLATION: return g.p1;
-    case MP2G_GATE_U32_ARITHMETIC: case MP2G_GATE_U32_RANGE_CHECK: case MP2G_GATE_U32_SUBTRACTION: case MP2G_GATE_U32_ADD_MANY: return 4;
-    case MP2G_GATE_COMPARISON: return g.p1 ? 1u << ((g.p0 + g.p1 - 1) / g.p1) : 0;
-    case MP2G_GATE_EXPONENTIATION: return 4;
-    case MP2G_GATE_REDUCING: case MP2G_GATE_REDUCING_EXT: return 2;
-    case MP2G_GATE_RANDOM_ACCESS: return g.p0 + 1;
-    case MP2G_GATE_U32_INTERLEAVE: case MP2G_GATE_UNINTERLEAVE_TO_B32: case MP2G_GATE_UNINTERLEAVE_TO_U32: return 2;
-    default: return 0;
-  }
-}
-// highest wire index + 1 and gate constants a descriptor touches
-static void gate_footprint(const mp2g_gate& g, u32& wires, u32& consts) {
-  wires = 0; consts = 0;
-  switch (g.kind) {
-    case MP2G_GATE_CONSTANT: wires = g.p0; consts = g.p0; break;
-    case MP2G_GATE_PUBLIC_INPUT: wires = 4; break;
-    case MP2G_GATE_ARITHMETIC: wires = 4 * g.p0; consts = 2; break;
-    case MP2G_GATE_BASE_SUM: wires = 1 + g.p0; break;
-    case MP2G_GATE_ARITHMETIC_EXT: wires = 8 * g.p0; consts = 2; break;
-    case MP2G_GATE_MUL_EXT: wires = 6 * g.p0; consts = 1; break;
-    case MP2G_GATE_POSEIDON2: case MP2G_GATE_POSEIDON: wires = 135; break;
-    case MP2G_GATE_POSEIDON_MDS: wires = 48; break;
-    case MP2G_GATE_COSET_INTERPOLATION: wires = 1 + 2 * (1u << g.p0) + 6 + 4 * (((1u << g.p0) - 2) / (g.p1 - 1)); break;
-    case MP2G_GATE_U32_ARITHMETIC: wires = 38 * g.p0; break;
-    case MP2G_GATE_U32_RANGE_CHECK: wires = 17 * g.p0; break;
-    case MP2G_GATE_U32_SUBTRACTION: wires = 21 * g.p0; break;
-    case MP2G_GATE_U32_ADD_MANY: wires = (g.p0 + 3 + 18) * g.p1; break;
-    case MP2G_GATE_COMPARISON: wires = g.p1 ? 4 + 5 * g.p1 + (g.p0 + g.p1 - 1) / g.p1 + 1 : 0; break;
-    case MP2G_GATE_EXPONENTIATION: wires = 2 * g.p0 + 2; break;
-    case MP2G_GATE_REDUCING: wires = 6 + g.p0 + 2 * (g.p0 - 1); break;
-    case MP2G_GATE_REDUCING_EXT: wires = 6 + 2 * g.p0 + 2 * (g.p0 - 1); break;
-    case MP2G_GATE_RANDOM_ACCESS: wires = (2 + (1u << g.p0)) * g.p1 + g.p2 + g.p0 * g.p1; consts = g.p2; break;
-    case MP2G_GATE_LOOKUP: wires = 2 * g.p0; break;
-    case MP2G_GATE_LOOKUP_TABLE: wires = 3 * g.p0; break;
-    case MP2G_GATE_U32_INTERLEAVE: wires = 34 * g.p0; break;
-    case MP2G_GATE_UNINTERLEAVE_TO_B32: case MP2G_GATE_UNINTERLEAVE_TO_U32: wires = 67 * g.p0; break;
-    default: break;
-  }
-}
-const char* gate_table_check(const GateTable& t, u32 num_constants, u32 wires_w) {
-  if (t.n_gates > MP2G_MAX_GATES) return "too many gates";
-  if (t.num_selectors == 0 || t.num_selectors > num_constants) return "num_selectors must be in 1..num_constants";
-  for (u32 i = 0; i < t.n_gates; i++) {
-    const mp2g_gate& g = t.g[i];
-    if (g.kind > MP2G_GATE_UNINTERLEAVE_TO_U32) return "unknown gate kind";
-    if (g.kind >= MP2G_GATE_LOOKUP && g.p0 < 1) return "gate needs at least one slot / operation";
-    if ((g.kind == MP2G_GATE_U32_ARITHMETIC || g.kind == MP2G_GATE_U32_RANGE_CHECK || g.kind == MP2G_GATE_U32_SUBTRACTION) && g.p0 < 1)
-      return "u32 gate needs at least one operation";
-    if (g.kind == MP2G_GATE_U32_ADD_MANY && (g.p0 < 1 || g.p0 > 16 || g.p1 < 1)) return "U32AddManyGate needs 1..16 addends and an operation";
-    if (g.kind == MP2G_GATE_COMPARISON && (g.p1 < 1 || g.p0 < g.p1 || (g.p0 + g.p1 - 1) / g.p1 > 4))
-      return "ComparisonGate needs num_chunks >= 1 and chunks of at most 4 bits";
-    if (g.kind == MP2G_GATE_COSET_INTERPOLATION && (g.p0 < 2 || g.p0 > 5 || g.p1 < 2 || g.p1 > (1u << g.p0)))
-      return "CosetInterpolationGate needs 2..5 subgroup bits and 2 <= degree <= 2^bits";
-    if (g.kind == MP2G_GATE_BASE_SUM && (g.p1 < 2 || g.p0 < 1)) return "BaseSumGate needs base >= 2 and a limb";
-    if ((g.kind == MP2G_GATE_REDUCING || g.kind == MP2G_GATE_REDUCING_EXT || g.kind == MP2G_GATE_EXPONENTIATION) && g.p0 < 1)
-      return "gate needs at least one coefficient / power bit";
-    if (g.kind == MP2G_GATE_RANDOM_ACCESS && (g.p0 < 1 || g.p0 > 6 || g.p1 < 1)) return "RandomAccessGate needs 1..6 bits and a copy";
-    u32 w, c;
-    gate_footprint(g, w, c);
-    if (w > wires_w) return "gate needs more wires than the wires oracle has";
-    if (t.num_selectors + t.num_lookup_selectors + c > num_constants) return "gate needs more constants than the preprocessed oracle has";
-    if (g.selector_index >= t.num_selectors) return "selector_index out of range";
-    if (!(g.group_start <= i && i < g.group_end && g.group_end <= t.n_gates)) return "gate is not inside its selector group";
-    if (gate_num_constraints(g) > MP2G_MAX_GATE_CONSTRAINTS) return "gate has too many constraints";
-  }
-  return nullptr;
-}
-
 struct Alg { u64 a, b; };  // ExtensionAlgebra element over the evaluation field, X^2 = 7
 // x y + z over the algebra as weak representatives, for values that feed further products or the lazy accumulator. Every operand
 // may be any u64; y7 is some representative of 7 y.b, which the callers form once where y.b is the same for a whole loop. The
@@ -638,15 +540,12 @@ __device__ __forceinline__ void eval_gate(const mp2g_gate g, WireF wire, ConstF 
   }
 }
 
-// gates/gate.rs compute_filter
-template <class ConstAll>
-GLD u64 gate_filter(const GateTable& t, u32 gi, ConstAll call) {
-  const mp2g_gate& g = t.g[gi];
-  const u64 s = call(g.selector_index);
+// gates/gate.rs compute_filter; s = the gate's selector polynomial at the point
+GLD u64 gate_filter(const mp2g_gate& g, u32 gi, u32 num_selectors, u64 s) {
   u64 f = 1;
   for (u32 r = g.group_start; r < g.group_end; r++)
     if (r != gi) f = gl_mul(f, gl_sub(r, s));
-  if (t.num_selectors > 1) f = gl_mul(f, gl_sub(0xFFFFFFFFull, s));
+  if (num_selectors > 1) f = gl_mul(f, gl_sub(0xFFFFFFFFull, s));
   return f;
 }
 
@@ -655,6 +554,11 @@ GLD u64 gate_filter(const GateTable& t, u32 gi, ConstAll call) {
 // block's proof sit in LDS, and a gate's constraints accumulate un-reduced, sum_j c_j alpha^j as a 136-bit
 // integer (lo, hi, top), reduced once: per constraint and challenge one 64x64 multiply and a carry chain
 // instead of two modular multiplications. q[b][a][i] is written by the first launch and added to by the rest.
+// (This kernel and the light kernel spell out the alpha-power staging, their accessors, the filter, the accumulation and
+// the store into q, although the text is the same twice: every shared form that was compiled -- gate_filter() called here,
+// helpers for the staging and the store, a view struct, one function for the whole step -- changed these listings for the
+// worse, from padding no-ops inside the Poseidon kernel's round loop up to 300 instead of 86 registers;
+// profiles/gate_shape/README.md has the figures.)
 template <u32 KIND>
 __global__ void __launch_bounds__(256) gate_constraints_lde_kernel(mp2g_gate g, u32 gi, u32 num_selectors, u32 cst_off, u32 n_cons,
                                                                    const u64* __restrict__ C, const u64* __restrict__ W,
@@ -699,25 +603,18 @@ __global__ void __launch_bounds__(256) gate_constraints_lde_kernel(mp2g_gate g, 
   }
 }
 
-// The light gates of a table in ONE launch: Constant, PublicInput, Arithmetic, BaseSum, ArithmeticExtension and MulExtension
-// rows all live on the first 80 wire columns, evaluate a few dozen constraints each and are bound by streaming those wires and the
-// accumulator (5-6.6 cycles per VALU instruction against ~3.1 for the compute-bound gates, tools/dbg/step_pmc.sh). Fused, the
-// wires and constants of a point are fetched once (the loads of the gates overlap), the alpha powers are shared (same alpha, the
-// longest gate's table) and q is read and written once instead of once per gate. Each case pins the kind at compile time so that
-// eval_gate's switch folds to that gate's body, as in the per-kind kernels.
+// The light gates of a table (MP2G_LIGHT_GATES) in ONE launch: Constant, PublicInput, Arithmetic, BaseSum, ArithmeticExtension and
+// MulExtension rows all live on the first 80 wire columns, evaluate a few dozen constraints each and are bound by streaming those
+// wires and the accumulator (5-6.6 cycles per VALU instruction against ~3.1 for the compute-bound gates, tools/dbg/step_pmc.sh).
+// Fused, the wires and constants of a point are fetched once (the loads of the gates overlap), the alpha powers are shared (same
+// alpha, the longest gate's table) and q is read and written once instead of once per gate. Each case pins the kind at compile
+// time so that eval_gate's switch folds to that gate's body, as in the per-kind kernels.
 #define MP2G_MAX_LIGHT_GATES 12
 struct LightGates {
   u32 n;
   mp2g_gate g[MP2G_MAX_LIGHT_GATES];
   u32 gi[MP2G_MAX_LIGHT_GATES];
 };
-static bool gate_is_light(const mp2g_gate& g) {
-  switch (g.kind) {
-    case MP2G_GATE_CONSTANT: case MP2G_GATE_PUBLIC_INPUT: case MP2G_GATE_ARITHMETIC: case MP2G_GATE_BASE_SUM:
-    case MP2G_GATE_ARITHMETIC_EXT: case MP2G_GATE_MUL_EXT: return true;
-    default: return false;
-  }
-}
 __global__ void __launch_bounds__(256) gate_constraints_lde_light_kernel(LightGates lg_, u32 num_selectors, u32 cst_off, u32 max_cons,
                                                                          const u64* __restrict__ C, const u64* __restrict__ W,
                                                                          u64 w_bstride, u32 lg, const u64* __restrict__ apw_tab,
@@ -757,12 +654,7 @@ __global__ void __launch_bounds__(256) gate_constraints_lde_light_kernel(LightGa
     };
     switch (g.kind) {
 #define LIGHT_CASE(K) case K: g.kind = K; eval_gate<true>(g, wire, cst, pih, emit); break;
-      LIGHT_CASE(MP2G_GATE_CONSTANT)
-      LIGHT_CASE(MP2G_GATE_PUBLIC_INPUT)
-      LIGHT_CASE(MP2G_GATE_ARITHMETIC)
-      LIGHT_CASE(MP2G_GATE_BASE_SUM)
-      LIGHT_CASE(MP2G_GATE_ARITHMETIC_EXT)
-      LIGHT_CASE(MP2G_GATE_MUL_EXT)
+      MP2G_LIGHT_GATES(LIGHT_CASE)
 #undef LIGHT_CASE
       default: break;
     }
@@ -775,30 +667,10 @@ __global__ void __launch_bounds__(256) gate_constraints_lde_light_kernel(LightGa
   }
 }
 
-__global__ void __launch_bounds__(256) gate_constraints_points_kernel(GateTable t, const u64* __restrict__ consts,
-                                                                      const u64* __restrict__ wires, u64 npts, u32 max_j,
-                                                                      const u64* __restrict__ pih, u64* __restrict__ out) {
-  const u64 p = (u64)blockIdx.x * 256 + threadIdx.x;
-  if (p >= npts) return;
-  auto wire = [&](u32 j) { return wires[(u64)j * npts + p]; };
-  auto call = [&](u32 j) { return consts[(u64)j * npts + p]; };
-  const u32 ns = t.num_selectors + t.num_lookup_selectors;
-  auto cst = [&](u32 j) { return consts[(u64)(ns + j) * npts + p]; };
-  for (u32 j = 0; j < max_j; j++) out[(u64)j * npts + p] = 0;
-  for (u32 gi = 0; gi < t.n_gates; gi++) {
-    if (t.g[gi].kind == MP2G_GATE_NOOP) continue;
-    const u64 f = gate_filter(t, gi, call);
-    u32 j = 0;
-    eval_gate<false>(t.g[gi], wire, cst, pih, [&](u64 v) {
-      u64* o = out + (u64)j * npts + p;
-      *o = gl_add(*o, gl_mul(f, v));
-      j++;
-    });
-  }
-}
-
-// The same for B sets of npts points, one set per proof (the verifier's line evaluation, verifier.hip): consts / wires / out of
-// proof b start c_bstride / w_bstride / max_j * npts words after those of proof b - 1, its public-inputs hash is pih[4 b .. 4 b + 4)
+// out[b][j][p] = C_j at point p of proof b, for B sets of npts points (the verifier's line evaluation, verifier.hip; B = 1 is
+// mp2g_eval_gate_constraints): consts / wires / out of proof b start c_bstride / w_bstride / max_j * npts words after those of
+// proof b - 1, its public-inputs hash is pih[4 b .. 4 b + 4). (This kernel and gate_check_kernel read their point-major matrices
+// [.][npts] through their own accessors: behind a shared view struct the check kernel took 256 registers instead of 230.)
 __global__ void __launch_bounds__(256) gate_constraints_points_batch_kernel(GateTable t, u32 B, const u64* __restrict__ consts, u64 c_bstride,
                                                                             const u64* __restrict__ wires, u64 w_bstride, u32 npts,
                                                                             u32 max_j, const u64* __restrict__ pih, u64* __restrict__ out) {
@@ -809,13 +681,12 @@ __global__ void __launch_bounds__(256) gate_constraints_points_batch_kernel(Gate
   const u64* wb = wires + b * w_bstride;
   u64* ob = out + (u64)b * max_j * npts;
   auto wire = [&](u32 j) { return wb[(u64)j * npts + p]; };
-  auto call = [&](u32 j) { return cb[(u64)j * npts + p]; };
   const u32 ns = t.num_selectors + t.num_lookup_selectors;
   auto cst = [&](u32 j) { return cb[(u64)(ns + j) * npts + p]; };
   for (u32 j = 0; j < max_j; j++) ob[(u64)j * npts + p] = 0;
   for (u32 gi = 0; gi < t.n_gates; gi++) {
     if (t.g[gi].kind == MP2G_GATE_NOOP) continue;
-    const u64 f = gate_filter(t, gi, call);
+    const u64 f = gate_filter(t.g[gi], gi, t.num_selectors, cb[(u64)t.g[gi].selector_index * npts + p]);
     u32 j = 0;
     eval_gate<false>(t.g[gi], wire, cst, pih + 4 * b, [&](u64 v) {
       u64* o = ob + (u64)j * npts + p;
@@ -835,13 +706,12 @@ __global__ void __launch_bounds__(256) gate_check_kernel(GateTable t, const u64*
   if (p >= npts) return;
   const u64* w = wires + b * w_bstride;
   auto wire = [&](u32 j) { return w[(u64)j * npts + p]; };
-  auto call = [&](u32 j) { return consts[(u64)j * npts + p]; };
   const u32 ns = t.num_selectors + t.num_lookup_selectors;
   auto cst = [&](u32 j) { return consts[(u64)(ns + j) * npts + p]; };
   bool bad = false;
   for (u32 gi = 0; gi < t.n_gates; gi++) {
     if (t.g[gi].kind == MP2G_GATE_NOOP) continue;
-    if (gate_filter(t, gi, call) == 0) continue;  // not this row's gate
+    if (gate_filter(t.g[gi], gi, t.num_selectors, consts[(u64)t.g[gi].selector_index * npts + p]) == 0) continue;  // not this row's gate
     eval_gate<false>(t.g[gi], wire, cst, pi_hash + 4 * b, [&](u64 v) { bad |= v != 0; });
   }
   if (bad) atomicOr(&flags[b], 2u);
@@ -873,72 +743,44 @@ hipError_t gate_constraints_lde(hipStream_t s, u32 B, const GateTable& t, const 
   if (nc < 1 || nc > 2) return hipErrorInvalidValue;
   const u64 N = (u64)1 << lg;
   const dim3 grid((u32)((N + 255) / 256), B), block(256);
+  const u32 cst_off = t.num_selectors + t.num_lookup_selectors;
   int first = 1;
   // the light gates first, in one launch
   LightGates lgs{};
   u32 light_cons = 0;
   for (u32 gi = 0; gi < t.n_gates; gi++) {
-    const u32 n_cons = gate_num_constraints(t.g[gi]);
-    if (n_cons && gate_is_light(t.g[gi]) && lgs.n < MP2G_MAX_LIGHT_GATES) {
+    const GateShape sh = gate_shape(t.g[gi]);
+    if (sh.constraints && sh.light && lgs.n < MP2G_MAX_LIGHT_GATES) {
       lgs.g[lgs.n] = t.g[gi]; lgs.gi[lgs.n] = gi; lgs.n++;
-      if (n_cons > light_cons) light_cons = n_cons;
+      if (sh.constraints > light_cons) light_cons = sh.constraints;
     }
   }
   if (lgs.n < 2) lgs.n = 0;  // a lone light gate goes the ordinary way
   if (lgs.n) {
-    hipLaunchKernelGGL(gate_constraints_lde_light_kernel, grid, block, 0, s, lgs, t.num_selectors, t.num_selectors + t.num_lookup_selectors,
-                       light_cons, C, W, w_bstride, lg, apw, nc, pi_hash, q, first);
+    hipLaunchKernelGGL(gate_constraints_lde_light_kernel, grid, block, 0, s, lgs, t.num_selectors, cst_off, light_cons, C, W, w_bstride, lg,
+                       apw, nc, pi_hash, q, first);
     first = 0;
   }
   for (u32 gi = 0; gi < t.n_gates; gi++) {
     const mp2g_gate& g = t.g[gi];
-    const u32 n_cons = gate_num_constraints(g);
+    const u32 n_cons = gate_shape(g).constraints;
     if (!n_cons) continue;
     bool fused = false;
     for (u32 k = 0; k < lgs.n; k++) fused |= lgs.gi[k] == gi;
     if (fused) continue;
-#define GATE_CASE(K)                                                                                                        \
-  case K:                                                                                                                   \
-    hipLaunchKernelGGL(gate_constraints_lde_kernel<K>, grid, block, 0, s, g, gi, t.num_selectors,                          \
-                       t.num_selectors + t.num_lookup_selectors, n_cons, C, W, w_bstride, lg, apw, nc, pi_hash, q,             \
-                       first);                                                                                              \
-    break;
     switch (g.kind) {
-      GATE_CASE(MP2G_GATE_CONSTANT)
-      GATE_CASE(MP2G_GATE_PUBLIC_INPUT)
-      GATE_CASE(MP2G_GATE_ARITHMETIC)
-      GATE_CASE(MP2G_GATE_BASE_SUM)
-      GATE_CASE(MP2G_GATE_ARITHMETIC_EXT)
-      GATE_CASE(MP2G_GATE_MUL_EXT)
-      GATE_CASE(MP2G_GATE_POSEIDON2)
-      GATE_CASE(MP2G_GATE_EXPONENTIATION)
-      GATE_CASE(MP2G_GATE_REDUCING)
-      GATE_CASE(MP2G_GATE_REDUCING_EXT)
-      GATE_CASE(MP2G_GATE_RANDOM_ACCESS)
-      GATE_CASE(MP2G_GATE_POSEIDON)
-      GATE_CASE(MP2G_GATE_POSEIDON_MDS)
-      GATE_CASE(MP2G_GATE_COSET_INTERPOLATION)
-      GATE_CASE(MP2G_GATE_U32_ARITHMETIC)
-      GATE_CASE(MP2G_GATE_U32_RANGE_CHECK)
-      GATE_CASE(MP2G_GATE_U32_SUBTRACTION)
-      GATE_CASE(MP2G_GATE_U32_ADD_MANY)
-      GATE_CASE(MP2G_GATE_COMPARISON)
-      GATE_CASE(MP2G_GATE_U32_INTERLEAVE)
-      GATE_CASE(MP2G_GATE_UNINTERLEAVE_TO_B32)
-      GATE_CASE(MP2G_GATE_UNINTERLEAVE_TO_U32)
+#define GATE_CASE(K)                                                                                                            \
+  case K:                                                                                                                       \
+    hipLaunchKernelGGL(gate_constraints_lde_kernel<K>, grid, block, 0, s, g, gi, t.num_selectors, cst_off, n_cons, C, W, w_bstride, lg, \
+                       apw, nc, pi_hash, q, first);                                                                             \
+    break;
+      MP2G_CONSTRAINT_GATES(GATE_CASE)
+#undef GATE_CASE
       default: return hipErrorInvalidValue;
     }
-#undef GATE_CASE
     first = 0;
   }
   if (first) return hipMemsetAsync(q, 0, (size_t)B * nc * N * sizeof(u64), s);  // a table of Noops only
-  return hipGetLastError();
-}
-hipError_t gate_constraints_points(hipStream_t s, const GateTable& t, const u64* consts, const u64* wires, u64 npts, u32 max_j,
-                                   const u64* pi_hash, u64* out) {
-  if (!npts) return hipSuccess;
-  hipLaunchKernelGGL(gate_constraints_points_kernel, dim3((u32)((npts + 255) / 256)), dim3(256), 0, s, t, consts, wires, npts, max_j,
-                     pi_hash, out);
   return hipGetLastError();
 }
 hipError_t gate_constraints_points_batch(hipStream_t s, u32 B, const GateTable& t, const u64* consts, u64 c_bstride, const u64* wires,
@@ -947,5 +789,9 @@ hipError_t gate_constraints_points_batch(hipStream_t s, u32 B, const GateTable& 
   hipLaunchKernelGGL(gate_constraints_points_batch_kernel, dim3((B * npts + 255) / 256), dim3(256), 0, s, t, B, consts, c_bstride, wires,
                      w_bstride, npts, max_j, pi_hash, out);
   return hipGetLastError();
+}
+hipError_t gate_constraints_points(hipStream_t s, const GateTable& t, const u64* consts, const u64* wires, u32 npts, u32 max_j,
+                                   const u64* pi_hash, u64* out) {
+  return gate_constraints_points_batch(s, 1, t, consts, 0, wires, 0, npts, max_j, pi_hash, out);
 }
 }  // namespace mp2g

@@ -780,7 +780,7 @@ int mp2g_eval_gate_constraints(mp2g_ctx* c, const mp2g_gate* gates, uint32_t n_g
   CK(hipMemcpyAsync(dc.p, consts, (size_t)num_constants * npts * sizeof(u64), hipMemcpyHostToDevice, c->stream));
   CK(hipMemcpyAsync(dw.p, wires, (size_t)wires_w * npts * sizeof(u64), hipMemcpyHostToDevice, c->stream));
   CK(hipMemcpyAsync(dp.p, pi_hash, 4 * sizeof(u64), hipMemcpyHostToDevice, c->stream));
-  CK(gate_constraints_points(c->stream, t, dc.p, dw.p, npts, max_j, dp.p, dout.p));
+  CK(gate_constraints_points(c->stream, t, dc.p, dw.p, (u32)npts, max_j, dp.p, dout.p));
   CK(hipMemcpyAsync(out, dout.p, (size_t)max_j * npts * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
   CK(hipStreamSynchronize(c->stream));
   return 0;

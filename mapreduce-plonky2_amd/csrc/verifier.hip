@@ -532,13 +532,13 @@ extern "C" {
 
 uint32_t mp2g_gate_table_line_points(const mp2g_gate* gates, uint32_t n_gates, uint32_t num_selectors) {
   if (!gates && n_gates) return 0;
-  uint32_t deg = 0;
+  uint64_t deg = 0;
   for (uint32_t i = 0; i < n_gates; i++) {
     const mp2g_gate& g = gates[i];
-    if (g.kind > MP2G_GATE_UNINTERLEAVE_TO_U32 || g.group_end <= g.group_start) return 0;
+    if (gate_shape(g).err || g.group_end <= g.group_start) return 0;
     deg = std::max(deg, gate_filtered_degree(g, num_selectors));
   }
-  return deg + 1;
+  return deg < 0xFFFFFFFFull ? (uint32_t)deg + 1 : 0;
 }
 
 int mp2g_verifier_create(mp2g_ctx* c, const mp2g_fri_params* params, const uint64_t* constants_sigmas_cap, const uint64_t circuit_digest[4],

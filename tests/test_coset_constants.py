@@ -3,9 +3,9 @@ csrc/gl.cuh -- gl_root_of_unity, gl_inv, gl_mul, compiled for the host -- and ag
 weights from their definition 1 / prod_{j != i} (x_i - x_j), and every entry as a signed power of two."""
 import os
 import re
-import shutil
 import subprocess
 
+import hosttest
 import oracle as O
 
 P = O.P
@@ -40,9 +40,6 @@ def test_tables_from_the_definition():
 
 
 def test_tables_against_the_host_field_code(tmp_path):
-    hipcc = os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    exe = str(tmp_path / "coset_constants_test")
-    subprocess.check_call([hipcc, "-x", "hip", "--cuda-host-only", "-O2", "-std=c++17", '-DMP2G_DEVCONST=static const', "-I" + CSRC,
-                           os.path.join(O.ROOT, "tools", "hosttest", "coset_constants_test.cpp"), "-o", exe])
+    exe = hosttest.build(tmp_path, "coset_constants_test", flags=("-O2", "-DMP2G_DEVCONST=static const"), mp2g_h=False)
     r = subprocess.run([exe], capture_output=True, text=True)
     assert r.returncode == 0 and r.stdout.split() == ["checked", "60", "bad", "0"], r.stdout + r.stderr

@@ -4,7 +4,6 @@ body on the operand tables of tests/field_cases.py with the checks of tests/fiel
 device bodies face in tests/test_gpu_field_device.py. Device-only routines (ntt_arith.cuh, poseidon_wave.cuh, two_to_one) have no
 host body."""
 import os
-import shutil
 import subprocess
 
 import numpy as np
@@ -12,9 +11,9 @@ import pytest
 
 import field_cases as F
 import field_checks as C
+import hosttest
 import oracle as O
 
-CSRC = os.path.join(O.ROOT, "mapreduce-plonky2_amd", "csrc")
 DEVICE_ONLY = {n for n in F.OPS if n.startswith(("gl_mul_2p", "gl_sub_mul_", "gl_mul_w8_", "bfly_lo_"))}
 
 
@@ -56,12 +55,8 @@ class HostBackend:
 @pytest.fixture(scope="module")
 def exe(tmp_path_factory):
     O.build()
-    hipcc = os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    path = str(tmp_path_factory.mktemp("hosttest") / "perm_host_test")
-    subprocess.check_call([hipcc, "-x", "hip", "--cuda-host-only", "-O2", "-std=c++17", "-DMP2G_DEVCONST=static const", "-I" + CSRC,
-                           os.path.join(O.ROOT, "tools", "hosttest", "perm_host_test.cpp"), "-x", "none", O.LIB,
-                           "-Wl,-rpath," + os.path.dirname(os.path.abspath(O.LIB)), "-o", path])
-    return path
+    return hosttest.build(tmp_path_factory.mktemp("hosttest"), "perm_host_test", flags=("-O2", "-DMP2G_DEVCONST=static const"),
+                          link=("-x", "none", O.LIB, "-Wl,-rpath," + os.path.dirname(os.path.abspath(O.LIB))), mp2g_h=False)
 
 
 @pytest.fixture

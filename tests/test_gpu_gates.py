@@ -66,13 +66,6 @@ def test_witness_check_on_h(ctx, mp2):
     assert out[:, row].any() and not np.delete(out, row, axis=1).any()
 
 
-def test_gate_descriptor_queries(mp2):
-    for k in C.ALL_KINDS:
-        og = C.Gate(*k, 0, 0, 0)
-        g = mp2.Gate(*k, 0, 0, 0)
-        assert g.num_constraints == C.gate_num_constraints(og) and g.degree == C.gate_degree(og)
-
-
 @pytest.mark.parametrize("kinds,log_n,B", [([(C.NOOP, 0, 0, 0), (C.CONSTANT, 2, 0, 0), (C.PUBLIC_INPUT, 0, 0, 0), (C.ARITHMETIC, 20, 0, 0)], 5, 2),
                                             (C.ALL_KINDS, 6, 2), ([(C.NOOP, 0, 0, 0), (C.POSEIDON2, 0, 0, 0), (C.ARITHMETIC, 20, 0, 0)], 8, 1)])
 def test_complete_proof_with_gates(ctx, mp2, kinds, log_n, B):

@@ -5,12 +5,12 @@ the opening offsets enumerate the openings once and agree with fri_batch_poly, a
 BEFORE the layout had one definition -- recorded in the golden file from that build, not recomputed here."""
 import json
 import os
-import shutil
 import subprocess
 
 import pytest
 
 import circuits as C
+import hosttest
 import oracle as O
 from test_verifier_host import SHAPES
 
@@ -21,11 +21,7 @@ FIELDS = ["variant", "log_n", "rate_bits", "cap_height", "pow_bits", "num_querie
 
 @pytest.fixture(scope="module")
 def layout_test(tmp_path_factory):
-    hipcc = os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    exe = str(tmp_path_factory.mktemp("layout") / "layout_test")
-    subprocess.check_call([hipcc, "-x", "hip", "--cuda-host-only", "-O2", "-std=c++17", "-I" + os.path.join(O.ROOT, "mapreduce-plonky2_amd", "csrc"),
-                           "-I" + os.path.join(O.ROOT, "include"), os.path.join(O.ROOT, "tools", "hosttest", "layout_test.cpp"), "-o", exe])
-    return exe
+    return hosttest.build(tmp_path_factory.mktemp("layout"), "layout_test")
 
 
 def words(params):

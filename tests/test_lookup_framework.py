@@ -8,7 +8,6 @@ import importlib
 import json
 import os
 import re
-import shutil
 import subprocess
 from collections import Counter
 
@@ -16,6 +15,7 @@ import numpy as np
 import pytest
 
 import circuits as C
+import hosttest
 import oracle as O
 from test_recursion import OracleProver, verifier_data
 
@@ -128,11 +128,7 @@ def test_header_and_python_agree_on_the_lookup_block():
 
 @pytest.fixture(scope="module")
 def shape_test(tmp_path_factory):
-    hipcc = os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    exe = str(tmp_path_factory.mktemp("witness_shape_lut") / "witness_shape_test")
-    subprocess.check_call([hipcc, "-x", "hip", "--cuda-host-only", "-O2", "-std=c++17", "-I" + os.path.join(ROOT, "mapreduce-plonky2_amd", "csrc"),
-                           "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tools", "hosttest", "witness_shape_test.cpp"), "-o", exe])
-    return exe
+    return hosttest.build(tmp_path_factory.mktemp("witness_shape_lut"), "witness_shape_test")
 
 
 def test_python_table_and_op_shape_agree_on_a_lookup_tape(shape_test):

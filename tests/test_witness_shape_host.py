@@ -5,11 +5,11 @@ of slots read and the same run of slots written (and the slot operands start whe
 import importlib
 import json
 import os
-import shutil
 import subprocess
 
 import pytest
 
+import hosttest
 import oracle as O
 from test_recursion import verifier_data
 from test_witness_tape import leaf_logic_circuit, leaf_logic_inputs
@@ -23,11 +23,7 @@ ALL_OPCODES = set(range(1, 24)) | {32, 33}  # include/mp2g.h: enum mp2g_witness_
 
 @pytest.fixture(scope="module")
 def shape_test(tmp_path_factory):
-    hipcc = os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    exe = str(tmp_path_factory.mktemp("witness_shape") / "witness_shape_test")
-    subprocess.check_call([hipcc, "-x", "hip", "--cuda-host-only", "-O2", "-std=c++17", "-I" + os.path.join(O.ROOT, "mapreduce-plonky2_amd", "csrc"),
-                           "-I" + os.path.join(O.ROOT, "include"), os.path.join(O.ROOT, "tools", "hosttest", "witness_shape_test.cpp"), "-o", exe])
-    return exe
+    return hosttest.build(tmp_path_factory.mktemp("witness_shape"), "witness_shape_test")
 
 
 def tapes():

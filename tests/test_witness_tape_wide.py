@@ -8,13 +8,13 @@ import importlib
 import json
 import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
 import circuits as C
+import hosttest
 import oracle as O
 from test_recursion import verifier_data
 
@@ -169,11 +169,7 @@ def golden_wires(case, log_n):
 
 @pytest.fixture(scope="module")
 def shape_test(tmp_path_factory):
-    hipcc = os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    exe = str(tmp_path_factory.mktemp("witness_shape_wide") / "witness_shape_test")
-    subprocess.check_call([hipcc, "-x", "hip", "--cuda-host-only", "-O2", "-std=c++17", "-I" + os.path.join(ROOT, "mapreduce-plonky2_amd", "csrc"),
-                           "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tools", "hosttest", "witness_shape_test.cpp"), "-o", exe])
-    return exe
+    return hosttest.build(tmp_path_factory.mktemp("witness_shape_wide"), "witness_shape_test")
 
 
 @pytest.fixture(scope="module")
