@@ -351,22 +351,32 @@ __global__ void soa_to_aos_kernel(u32 n, const u64* in, u64 in_bstride, u32 n_in
 
 // ---- proof of work ----------------------------------------------------------------------------
 // witness[b * POW_STRIDE] = min { w : perm(state with w at position n_in)[7] has >= bits leading zeros }.
-// Several blocks of 256 lanes per proof (fri_pow sizes the grid) sweep the candidates in order (four blocks share a CU, so one block's poll and
-// barrier leave the ALUs to the other three; with one 1024-lane block per CU 37 % of the wave cycles were parked: 3.45 -> 3.08 ms
-// per 64 base proofs. Handing the candidates out in chunks from a per-proof counter so that the blocks of finished proofs help the
-// stragglers was measured too and lost, 4.6-11.9 ms: the helpers gang up on a proof and overshoot its nonce). Blocks of one proof
-// talk through one word: a finder publishes with atomicMin, and once per sweep lane 0 of every
-// block reads it back with a returning (no-op) atomicMin -- the per-XCD L2s are not coherent, a
-// plain or sc1 load of a word that another XCD updates atomically can stay stale for seconds,
-// while an atomic executes at the coherence point. Each proof's word sits in its own 128-B line.
+// Several blocks of 256 lanes per proof (fri_pow sizes the grid; four blocks share a CU, so one block's poll and barrier leave the
+// ALUs to the other three; with one 1024-lane block per CU 37 % of the wave cycles were parked: 3.45 -> 3.08 ms per 64 base
+// proofs). The candidates of a proof are handed out IN ORDER, in chunks of 256, from a ticket counter of that proof: at the top of
+// a round lane 0 takes ticket k (a returning atomicAdd) and polls the best witness published so far; the block leaves if
+// k * 256 > best, else its lanes evaluate k * 256 + t and a finder publishes with atomicMin. Why the result is the smallest witness:
+//   - tickets are handed out in increasing order, each once;
+//   - a block never abandons a chunk it has taken: it evaluates all of it unless the chunk's base already exceeds `best`, and
+//     `best` never falls below the final minimum m, so a chunk that is skipped lies wholly above m;
+//   - a block leaves only with a ticket k, k * 256 > best >= m: every chunk at or below m was taken earlier, by a block that
+//     evaluates it before it leaves. So every candidate <= m is evaluated before the kernel ends, and m is what atomicMin keeps.
+// What is evaluated past m is bounded by the chunks in flight when m is published, wherever and whenever the blocks of the proof
+// were scheduled. (Before, block x owned the fixed candidates x * 256 + t + k * stride and a block that started early swept on
+// past m until the block that owned m got there: see profiles/pow_order.) There is no helping across proofs: with a counter
+// shared so that the blocks of finished proofs help the stragglers (measured once, 4.6-11.9 ms against 3.08) the helpers gang up on a
+// proof and overshoot its nonce. Blocks of one proof talk through atomics only -- the per-XCD L2s are not coherent, a plain or
+// sc1 load of a word that another XCD updates atomically can stay stale for seconds, while an atomic executes at the coherence
+// point. Each proof has a 128-B line of its own: word 0 the witness (~0 = none yet), word POW_TICKET the next ticket.
 #define POW_THREADS 256
 #define POW_STRIDE 16
+#define POW_TICKET 1
 template <int V>
 __global__ void __launch_bounds__(POW_THREADS) pow_kernel(const ChState* st, u32 bits, unsigned long long* witness) {
   const u32 b = blockIdx.y;
   const ChState& c = st[b];
   unsigned long long* wit = witness + (u64)b * POW_STRIDE;
-  __shared__ unsigned long long s_best;
+  __shared__ unsigned long long s_best, s_chunk;
   u64 base[12];
 #pragma unroll
   for (int i = 0; i < 12; i++) base[i] = c.state[i];
@@ -374,13 +384,16 @@ __global__ void __launch_bounds__(POW_THREADS) pow_kernel(const ChState* st, u32
 #pragma unroll
   for (int i = 0; i < 8; i++)
     if ((u32)i < pos) base[i] = c.in[i];
-  const u64 stride = (u64)gridDim.x * blockDim.x;
-  for (u64 cand = (u64)blockIdx.x * blockDim.x + threadIdx.x;; cand += stride) {
-    if (threadIdx.x == 0) s_best = atomicMin(wit, ~0ull);
+  for (;;) {
+    if (threadIdx.x == 0) {
+      s_chunk = atomicAdd(wit + POW_TICKET, 1ull);
+      s_best = atomicMin(wit, ~0ull);
+    }
     __syncthreads();
     const unsigned long long best = s_best;
+    const u64 cand = (u64)s_chunk * POW_THREADS + threadIdx.x;
     __syncthreads();
-    // block-uniform exit: the block's smallest candidate of this sweep is already beaten
+    // block-uniform exit: the chunk's smallest candidate is already beaten
     if (cand - threadIdx.x > best) break;
     u64 s[12];
 #pragma unroll
@@ -392,9 +405,10 @@ __global__ void __launch_bounds__(POW_THREADS) pow_kernel(const ChState* st, u32
     if (cand < GL_P && (bits == 0 || (s[7] >> (64 - bits)) == 0)) atomicMin(wit, (unsigned long long)cand);
   }
 }
-__global__ void fill_u64_kernel(u64* p, u64 v, u32 n) {
+// every proof's line before a search: no witness yet, ticket 0
+__global__ void pow_reset_kernel(u64* witness, u32 n) {
   u32 i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) p[i] = v;
+  if (i < n) witness[i] = (i % POW_STRIDE) ? 0 : ~(u64)0;
 }
 
 // ---- query rounds -----------------------------------------------------------------------------
@@ -488,14 +502,16 @@ hipError_t fri_soa_to_aos(hipStream_t s, u32 B, u32 n, const u64* in, u64 in_bst
   return hipGetLastError();
 }
 hipError_t fri_pow(hipStream_t s, int variant, const ChState* st, u32 B, u32 bits, u64* witness) {
-  hipLaunchKernelGGL(fill_u64_kernel, dim3((B * POW_STRIDE + 63) / 64), dim3(64), 0, s, witness, ~(u64)0, B * POW_STRIDE);
-  // blocks per proof. The search returns the SMALLEST witness, so every candidate below it is evaluated whatever the order -- and so is
-  // the rest of the sweep it lies in: with G candidates per sweep and proof the expected work is 2^bits + G / 2 permutations. The
-  // launch is sized to 2^19 lanes over all proofs of the batch instead of 2^20 as in
-  // rounds 1-4 (a batch of 32 proofs: G = 2^14 instead of 2^15, 1.125 x 2^16 permutations a proof instead of 1.25 x). Measured on
-  // the table build (profiles/r05/variants_ab.txt, two alternating repetitions): 2^20 lanes 841.8 / 839.4 proofs/s, 2^19 845.0 /
-  // 842.3, 2^18 840.8 / 838.3, 2^17 824.1 / 823.6 -- narrower sweeps save candidates and pay for it in polls and part-filled
-  // launches; the search is 7 % of a build's VALU instructions either way. A lone proof keeps sweeps of 2^18 candidates
+  hipLaunchKernelGGL(pow_reset_kernel, dim3((B * POW_STRIDE + 63) / 64), dim3(64), 0, s, witness, B * POW_STRIDE);
+  // blocks per proof. The search returns the SMALLEST witness, so every candidate below it is evaluated whatever the order; what is
+  // evaluated beyond it is bounded by the G = 256 x blocks lanes a proof has in flight: the chunks already handed out above the
+  // witness when it is published (G / 2 on average) and those taken while the finder's own permutation runs (another G / 2). Measured
+  // (profiles/pow_order/README.md, evaluated / necessary candidates of 20 x 48 searches of 16 bits alone on the GPU): 2^20 lanes
+  // over the batch 1.310, 2^19 1.155, 2^18 1.076, 2^17 1.036 -- 1 + 0.93 G / 2^16; in the 512-row table build, four workers,
+  // 1.437 / 1.224 / 1.113 / 1.055 (fixed candidates per block, 2^19 lanes: 1.400). The table build itself, two alternating
+  // repetitions: 2^20 lanes 932.6 / 935.3 proofs/s, 2^19 937.4 / 939.6, 2^18 934.8 / 932.5, 2^17 920.5 / 922.1 -- narrower
+  // launches save candidates and lose more than that in the length of the search, which the proofs of the batch wait for. 2^19
+  // stays. A lone proof keeps 2^18 lanes (the cap of 1024 blocks): its latency, not its instruction count, is what matters
   const u32 lanes = 1u << 19;
   u32 blocks = lanes / POW_THREADS / (B ? B : 1);
   if (blocks < 8) blocks = 8;
