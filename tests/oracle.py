@@ -232,3 +232,40 @@ def copy_constraint_circuit(log_n, num_routed, wires_w, n_cycles, seed):
         sa, sb, sc = sig[ja, ia], sig[jb, ib], sig[jc, ic]
         sig[ja, ia], sig[jb, ib], sig[jc, ic] = sb, sc, sa
     return sig, wires
+
+
+class Challenger:
+    """orc_challenger: a transcript on the oracle's side"""
+
+    def __init__(self, variant=0):
+        self.st = (ctypes.c_uint64 * 32)()  # opaque: 12 + 8 + 8 words and three counters
+        lib().orc_ch_init(self.st, variant)
+
+    def observe(self, elems):
+        e = arr(elems).reshape(-1)
+        lib().orc_ch_observe(self.st, p(e), sz(e.size))
+
+
+    def get(self, n):
+        lib().orc_ch_get.restype = ctypes.c_uint64
+        return np.array([lib().orc_ch_get(self.st) for _ in range(n)], dtype=np.uint64)
+
+
+def fri_commit(fp, coeffs):
+    """what orc_fri_prove needs of committed oracles: (coefficients [w_o][n], LDE leaves, Merkle levels) per oracle"""
+    cs = [arr(c) for c in coeffs]
+    leaves = [lde_leaves(c, fp.rate_bits) for c in cs]
+    return cs, leaves, [merkle_build(l, fp.cap_height, fp.variant) for l in leaves]
+
+
+def fri_prove(fp, committed, zeta, challenger):
+    """orc_fri_prove (PolynomialBatch::prove_openings) of fri_commit()'s oracles opened at zeta; the transcript continues the given
+    Challenger. Returns the flat proof."""
+    class G2(ctypes.Structure):
+        _fields_ = [("c", ctypes.c_uint64 * 2)]
+    z = G2()
+    z.c[0], z.c[1] = int(zeta[0]), int(zeta[1])
+    ptrs = [(ctypes.c_void_p * len(group))(*[a.ctypes.data for a in group]) for group in committed]
+    proof = np.zeros(lib().orc_fri_proof_words(ctypes.byref(fp)), dtype=np.uint64)
+    lib().orc_fri_prove(ctypes.byref(fp), ptrs[0], ptrs[1], ptrs[2], z, challenger.st, p(proof))
+    return proof

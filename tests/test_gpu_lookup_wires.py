@@ -74,6 +74,11 @@ def test_lookup_wires_dev_one_entry_and_65536_entry_tables(ctx, mp2):
         assert np.array_equal(got, wires)
         cp.prove(d_w, ctx.to_device(np.stack([ckt.pi_hash] * 2)))
         assert cp.pr.witness_status().tolist() == [0, 0]
+        # every row of RE and of the partial sums, not only where they end: the proof is the oracle's, word for word
+        caps, openings, proofs = cp.results()
+        oc, oo, op, _ = C.prove(ckt, C.oracle_params(ckt, pow_bits=4, num_queries=3), cp.circuit_digest)
+        for b in range(2):
+            assert np.array_equal(caps[b], oc) and np.array_equal(openings[b], oo) and np.array_equal(proofs[b], op)
         cp.free()
 
 
