@@ -266,6 +266,62 @@ int mp2g_row_digest_batch_dev(mp2g_ctx* ctx, int variant, const uint64_t* d_col_
                               const uint32_t* d_values, const uint32_t* d_unique, uint32_t n_unique, uint32_t rows,
                               uint64_t* d_frac_out, uint64_t out_w[5], uint64_t out_weierstrass[11]);
 
+/* ---- node hashes of a table's trees (off-circuit payload side, csrc/index_hash.hip) -------------------------------------------
+ * The hashes a DB host stores for every node and the root proof's first four public inputs must equal: MerkleCell::aggregate
+ * (mp2-v1/src/indexing/cell.rs:120-157), RowPayload::aggregate (row.rs:257-317), IndexNode::aggregate (index.rs:61-101), for a
+ * whole block at once: one launch per tree level, no host round trip between the launches. Sponge input words are taken as
+ * mp2g_hash_no_pad_batch takes them; a missing child hashes as hash_no_pad(&[]) (mp2-common/src/poseidon.rs:44-46, all zero).
+ *
+ * A tree shape: a binary tree or forest over nodes 0..n-1 given by left[n] / right[n] (-1 = no child). From them come every
+ * node's height (0 without children, else 1 + the larger child's: one launch per height), min_idx / max_idx (the node reached by
+ * following left / right children to the end: the reference's rule min = left.min if there is a left child, else the node's own
+ * value, row.rs:261-285, carried as an index, so no U256 is compared), and the roots (nodes without a parent, ascending).
+ * _create refuses, with a message, a child index outside -1..n-1, a node that is its own child, a node with two parents
+ * (left[i] == right[i] != -1 included) and a cycle; n = 0 is the valid empty shape. Host work only: no GPU is needed.
+ * _sbbst: ryhope's self-balanced BST over the positions 1..n (ryhope/src/tree/sbbst.rs: root :251-257, children :301-333 and
+ * :487-503), position k = node k - 1; n <= 2^31 - 1.
+ * Ownership: the first hashing call that uses a shape uploads its arrays to that call's context (on its stream); they stay there
+ * until mp2g_tree_shape_free, and the shape is refused with any other context. _free waits for the device, so it may be called
+ * while hashing calls with the shape are still queued. Free a shape before the context it was used with is destroyed: the shape
+ * remembers that context by its address only, and would take a later context at the same address for it. A shape is not to be
+ * used from two threads at once. */
+typedef struct mp2g_tree_shape mp2g_tree_shape;
+int mp2g_tree_shape_create(const int32_t* left, const int32_t* right, uint32_t n, mp2g_tree_shape** out);
+int mp2g_tree_shape_sbbst(uint32_t n, mp2g_tree_shape** out);
+uint32_t mp2g_tree_shape_size(const mp2g_tree_shape* shape);
+uint32_t mp2g_tree_shape_num_levels(const mp2g_tree_shape* shape); /* largest height + 1; 0 for the empty shape */
+uint32_t mp2g_tree_shape_num_roots(const mp2g_tree_shape* shape);
+/* any output may be NULL; left / right give back the children (what _sbbst made); all [n] but roots [num_roots] */
+int mp2g_tree_shape_describe(const mp2g_tree_shape* shape, int32_t* left, int32_t* right, uint32_t* height, uint32_t* min_idx,
+                             uint32_t* max_idx, uint32_t* roots);
+void mp2g_tree_shape_free(mp2g_tree_shape* shape);
+/* every row's cells tree (cell.rs:120-157: H(H(left) || H(right) || id || value), 17 limbs): the sbbst over the positions
+ * 1..n_cols-1; the cell at position k has the identifier col_ids[k] and the value values[row][k] (column 0 is the secondary index
+ * and is not a cell). values [rows][n_cols][8] as mp2g_row_digests takes them (u256.rs:870-877), so one upload serves both.
+ * roots [rows][4]; nodes [rows][n_cols-1][4] (position k at index k - 1) or NULL. n_cols == 1: no cells, every root is
+ * hash_no_pad(&[]) (row.rs:299-302). Refused before any launch: variant not 0 / 1, n_cols outside 1..256, a col_ids entry >= p
+ * (the reference builds them with from_canonical_u64), rows > 2^31. rows == 0 returns 0 and launches nothing.
+ * _dev: col_ids stays a host array; d_roots / d_nodes 16-byte aligned; stream ordered, no synchronisation (the context keeps a
+ * working buffer of rows * (n_cols-1) * 32 bytes, which grows, with one synchronisation, when a call needs more). */
+int mp2g_cells_tree_hashes(mp2g_ctx* ctx, int variant, const uint64_t* col_ids, uint32_t n_cols, const uint32_t* values /* [rows][n_cols][8] */,
+                           uint32_t rows, uint64_t* roots, uint64_t* nodes);
+int mp2g_cells_tree_hashes_dev(mp2g_ctx* ctx, int variant, const uint64_t* col_ids /* host */, uint32_t n_cols, const uint32_t* d_values,
+                               uint32_t rows, uint64_t* d_roots, uint64_t* d_nodes);
+/* every node of a row tree (row.rs:257-317) or index tree (index.rs:61-101) of shape `shape`:
+ * H(hL || hR || min || max || id || value || payload), 37 limbs. Node i's value is the 8 big-endian u32 words at
+ * values + i * value_stride (value_stride in u32 words, >= 8: pass n_cols * 8 to read column 0 of the table in place); payload
+ * [n][4] is the cells root per row (or the row tree's root per block for the index tree), NULL = hash_no_pad(&[]) for every
+ * node. hashes [n][4]. A right child without a left one is hashed by the row tree's rule (min = the node's own value); the index
+ * tree's caller refuses it beforehand if it wants IndexNode::aggregate's panic. Refused before any launch: variant not 0 / 1,
+ * id >= p, value_stride < 8, a size that overflows. An empty shape returns 0 and launches nothing.
+ * One launch per level: a degenerate chain of height h costs h launches, which is correct but slow; the reference's trees
+ * (sbbst, scapegoat) are logarithmic.
+ * _dev: d_payload / d_hashes 16-byte aligned; stream ordered, no synchronisation. */
+int mp2g_row_tree_hashes(mp2g_ctx* ctx, int variant, const mp2g_tree_shape* shape, uint64_t id, const uint32_t* values, uint32_t value_stride,
+                         const uint64_t* payload, uint64_t* hashes);
+int mp2g_row_tree_hashes_dev(mp2g_ctx* ctx, int variant, const mp2g_tree_shape* shape, uint64_t id, const uint32_t* d_values,
+                             uint32_t value_stride, const uint64_t* d_payload, uint64_t* d_hashes);
+
 /* ---- proof wire format between tree levels / GPUs ------------------------------------------ */
 /* bincode 1.3 (little-endian fixed-width ints, u64 length prefixes) serialization of plonky2's
  * ProofWithPublicInputs<F, C, 2> exactly as mp2-common/src/proof.rs:84-98 `serialize_proof`

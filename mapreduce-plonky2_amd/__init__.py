@@ -43,6 +43,9 @@ def load():
         _lib.mp2g_ctx_stream.restype = ctypes.c_void_p
         _lib.mp2g_stat_leaf_permutations.restype = ctypes.c_uint64
         _lib.mp2g_ctx_stream.argtypes = [ctypes.c_void_p]
+        for f in (_lib.mp2g_tree_shape_size, _lib.mp2g_tree_shape_num_levels, _lib.mp2g_tree_shape_num_roots):
+            f.restype, f.argtypes = ctypes.c_uint32, [ctypes.c_void_p]
+        _lib.mp2g_tree_shape_free.restype, _lib.mp2g_tree_shape_free.argtypes = None, [ctypes.c_void_p]
     return _lib
 
 
@@ -963,6 +966,75 @@ def row_digests(ctx, col_ids, values, unique, variant=POSEIDON2):
     wei = np.empty((rows, 11), dtype=np.uint64)
     _ck(load().mp2g_row_digests(ctx.h, variant, _p(ids), n_cols, _p(v), _p(u), n_unique, rows, _p(w), _p(wei)))
     return w, wei
+
+
+# ---- node hashes of a table's trees (csrc/index_hash.hip) ------------------------------------
+class TreeShape:
+    """mp2g_tree_shape: a binary tree or forest over nodes 0..n-1 by its children arrays (-1 = no child), checked and levelled on
+    the host (csrc/tree_shape.h); needs no GPU. A malformed forest raises Mp2gError with the fault's name."""
+
+    def __init__(self, handle):
+        self.h = handle
+        lib = load()
+        self.size, self.num_levels, self.num_roots = (int(f(self.h)) for f in (lib.mp2g_tree_shape_size, lib.mp2g_tree_shape_num_levels,
+                                                                                 lib.mp2g_tree_shape_num_roots))
+
+    @classmethod
+    def from_children(cls, left, right):
+        l, r = _arr(left, np.int32).ravel(), _arr(right, np.int32).ravel()
+        if l.size != r.size:
+            raise ValueError("left and right differ in length")
+        h = ctypes.c_void_p()
+        _ck(load().mp2g_tree_shape_create(_p(l), _p(r), l.size, ctypes.byref(h)))
+        return cls(h)
+
+    @classmethod
+    def sbbst(cls, n):
+        """ryhope's sbbst over positions 1..n (position k = node k - 1)"""
+        h = ctypes.c_void_p()
+        _ck(load().mp2g_tree_shape_sbbst(ctypes.c_uint32(int(n)), ctypes.byref(h)))
+        return cls(h)
+
+    def describe(self):
+        """{left, right (int32), height, min_idx, max_idx (uint32): [n]; roots: [num_roots] ascending}"""
+        n = self.size
+        out = {k: np.empty(n, dtype=np.int32) for k in ("left", "right")}
+        out.update({k: np.empty(n, dtype=np.uint32) for k in ("height", "min_idx", "max_idx")})
+        out["roots"] = np.empty(self.num_roots, dtype=np.uint32)
+        _ck(load().mp2g_tree_shape_describe(self.h, *(_p(out[k]) for k in ("left", "right", "height", "min_idx", "max_idx", "roots"))))
+        return out
+
+    def free(self):
+        if self.h:
+            load().mp2g_tree_shape_free(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def _raw(x):
+    """a DeviceBuffer, a raw device address or None as the void* of a call"""
+    return x.ptr if isinstance(x, DeviceBuffer) else (None if x is None else ctypes.c_void_p(int(x)))
+
+
+def cells_tree_hashes_dev(ctx, variant, col_ids, d_values, rows, d_roots, d_nodes=None):
+    """mp2g_cells_tree_hashes_dev: stream ordered, no synchronisation; col_ids is a host array"""
+    ids = _arr(col_ids).ravel()
+    _ck(load().mp2g_cells_tree_hashes_dev(ctx.h if ctx is not None else None, int(variant), _p(ids), ids.size, _raw(d_values), ctypes.c_uint32(rows),
+                                          _raw(d_roots), _raw(d_nodes)))
+
+
+def row_tree_hashes_dev(ctx, variant, shape, ident, d_values, value_stride, d_payload, d_hashes):
+    """mp2g_row_tree_hashes_dev: stream ordered, no synchronisation. The shape joins the context's handles: closing the context
+    frees it (a shape is freed before the context it was used with)."""
+    if ctx is not None:
+        ctx._adopt(shape)
+    _ck(load().mp2g_row_tree_hashes_dev(ctx.h if ctx is not None else None, int(variant), shape.h, ctypes.c_uint64(int(ident)), _raw(d_values),
+                                        ctypes.c_uint32(int(value_stride)), _raw(d_payload), _raw(d_hashes)))
 
 
 def leaf_permutations_queued():

@@ -48,6 +48,7 @@ struct mp2g_ctx {
   mp2g::NttEngine ntt;
   mp2g::DevBuf wit_vals;  // slot tables of the device witness executor (mp2g_witness_program_run_dev), grown on demand
   mp2g::DevBuf wit_rows;  // its row-major staging wire matrices
+  mp2g::DevBuf index_work;  // node-major digests of the rows' cells trees (mp2g_cells_tree_hashes_dev), grown on demand
   // The provers' per-batch working buffers (coefficients, LDE values, Merkle levels of oracles 1.., quotient values, FRI layers):
   // everything a prove() recomputes from its inputs and nobody reads once its kernels have run. All provers of a context run on
   // the context's ONE stream, so they can use the same memory one after the other: the scratch is as large as the largest

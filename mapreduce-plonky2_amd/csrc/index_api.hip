@@ -1,0 +1,229 @@
+// C ABI of the tree shapes and the node hashes of a table's trees (include/mp2g.h), over tree_shape.h and the kernels of
+// index_hash.hip. Every argument is judged on the host before anything is launched.
+#include "ctx.h"
+#include "index_hash.h"
+#include "tree_shape.h"
+#include <exception>
+#include <new>
+
+using namespace mp2g;
+
+struct mp2g_tree_shape {
+  TreeShape s;
+  // the shape's arrays on the device (left, right, min_idx, max_idx, order: 5 n words of 32 bits), uploaded by the first hashing
+  // call that uses the shape, on that context's stream, and kept until mp2g_tree_shape_free
+  mutable DevBuf dev;
+  mutable const mp2g_ctx* bound = nullptr;
+};
+
+// No exception crosses the C ABI: the entry points that build vectors (a shape of up to 2^31 - 1 nodes is gigabytes of them) run
+// inside guarded(), which turns bad_alloc and anything else into the library's error code + mp2g_last_error().
+template <class F> static int guarded(F&& f) noexcept {
+  try {
+    return f();
+  } catch (const std::bad_alloc&) {
+    return fail("out of memory");
+  } catch (const std::exception& e) {
+    return fail("internal error: %s", e.what());
+  } catch (...) {
+    return fail("internal error");
+  }
+}
+
+static int shape_new(const int32_t* left, const int32_t* right, uint32_t n, mp2g_tree_shape** out) {
+  mp2g_tree_shape* t = new (std::nothrow) mp2g_tree_shape();
+  if (!t) return fail("out of memory");
+  const char* err;
+  try {
+    err = tree_shape_build(left, right, n, t->s);
+  } catch (...) {
+    delete t;
+    throw;  // to guarded()
+  }
+  if (err) { delete t; return fail("invalid tree shape: %s", err); }
+  *out = t;
+  return 0;
+}
+// the device copy, made once
+static int shape_on_device(const mp2g_tree_shape* t, mp2g_ctx* c, const u32** d) {
+  const size_t n = t->s.size();
+  if (!t->bound) {
+    CK(hipSetDevice(c->device));
+    CK(t->dev.alloc(5 * n * sizeof(u32)));
+    u32* p = (u32*)t->dev.p;
+    const void* src[5] = {t->s.left.data(), t->s.right.data(), t->s.min_idx.data(), t->s.max_idx.data(), t->s.order.data()};
+    for (int k = 0; k < 5; k++) {  // the host arrays live as long as the handle, and freeing the handle waits for the device
+      hipError_t e = hipMemcpyAsync(p + k * n, src[k], n * sizeof(u32), hipMemcpyHostToDevice, c->stream);
+      if (e != hipSuccess) { t->dev.release(); return fail("tree shape upload: %s", hipGetErrorString(e)); }
+    }
+    t->bound = c;
+  }
+  NEED(t->bound == c, "the tree shape was first used with another context (its device arrays belong to that context's stream)");
+  *d = (const u32*)t->dev.p;
+  return 0;
+}
+static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+extern "C" {
+
+int mp2g_tree_shape_create(const int32_t* left, const int32_t* right, uint32_t n, mp2g_tree_shape** out) {
+  NEED(out && ((left && right) || !n), "out / left / right");
+  return guarded([&] { return shape_new(left, right, n, out); });
+}
+int mp2g_tree_shape_sbbst(uint32_t n, mp2g_tree_shape** out) {
+  NEED(out, "out");
+  NEED(n <= 0x7FFFFFFFu, "n <= 2^31 - 1");
+  return guarded([&] {
+    std::vector<int32_t> l(n), r(n);
+    sbbst_fill(n, l.data(), r.data());
+    return shape_new(l.data(), r.data(), n, out);
+  });
+}
+uint32_t mp2g_tree_shape_size(const mp2g_tree_shape* t) { return t ? t->s.size() : 0; }
+uint32_t mp2g_tree_shape_num_levels(const mp2g_tree_shape* t) { return t ? t->s.levels() : 0; }
+uint32_t mp2g_tree_shape_num_roots(const mp2g_tree_shape* t) { return t ? (uint32_t)t->s.roots.size() : 0; }
+int mp2g_tree_shape_describe(const mp2g_tree_shape* t, int32_t* left, int32_t* right, uint32_t* height, uint32_t* min_idx,
+                             uint32_t* max_idx, uint32_t* roots) {
+  NEED(t, "shape");
+  const size_t n = t->s.size();
+  for (size_t i = 0; i < n; i++) {
+    if (left) left[i] = t->s.left[i];
+    if (right) right[i] = t->s.right[i];
+    if (height) height[i] = t->s.height[i];
+    if (min_idx) min_idx[i] = t->s.min_idx[i];
+    if (max_idx) max_idx[i] = t->s.max_idx[i];
+  }
+  if (roots)
+    for (size_t i = 0; i < t->s.roots.size(); i++) roots[i] = t->s.roots[i];
+  return 0;
+}
+void mp2g_tree_shape_free(mp2g_tree_shape* t) {
+  delete t;  // hipFree of the device arrays waits for every kernel that may still read them
+}
+
+// ---- cells trees -----------------------------------------------------------------------------
+static int cells_args(int variant, const uint64_t* col_ids, uint32_t n_cols, uint32_t rows) {
+  NEED(variant == 0 || variant == 1, "variant");
+  NEED(n_cols >= 1 && n_cols <= 256, "1 <= n_cols <= 256");
+  NEED(col_ids, "col_ids");
+  for (uint32_t k = 0; k < n_cols; k++) NEED(col_ids[k] < GL_P, "column identifier not canonical (>= p)");
+  NEED(rows <= 0x80000000u, "rows <= 2^31");  // one lane per row along grid.x
+  return 0;
+}
+int mp2g_cells_tree_hashes_dev(mp2g_ctx* c, int variant, const uint64_t* col_ids, uint32_t n_cols, const uint32_t* d_values,
+                               uint32_t rows, uint64_t* d_roots, uint64_t* d_nodes) {
+  int rc = cells_args(variant, col_ids, n_cols, rows);
+  if (rc) return rc;
+  if (!rows) return 0;
+  NEED(c && d_roots, "ctx / roots");
+  NEED(aligned16(d_roots) && aligned16(d_nodes), "digest buffers must be 16-byte aligned");
+  const uint32_t cells = n_cols - 1;
+  if (!cells) {  // row.rs:299-302: a row without cells carries hash_no_pad(&[])
+    CK(cells_empty_roots(c->stream, (u64*)d_roots, rows));
+    return 0;
+  }
+  NEED(d_values, "values");
+  TreeShape s;
+  rc = guarded([&] {  // at most 255 nodes
+    std::vector<int32_t> l(cells), r(cells);
+    sbbst_fill(cells, l.data(), r.data());
+    const char* err = tree_shape_build(l.data(), r.data(), cells, s);
+    return err ? fail("cells tree: %s", err) : 0;
+  });
+  if (rc) return rc;
+  const size_t work_bytes = (size_t)cells * rows * 4 * sizeof(u64);
+  if (c->index_work.bytes < work_bytes) {
+    CK(hipStreamSynchronize(c->stream));  // a kernel queued earlier may still use the old buffer
+    CK(c->index_work.alloc(work_bytes));
+  }
+  const int root = (int)sbbst_root(cells) - 1;
+  for (uint32_t h = 0; h < s.levels(); h++) {
+    const uint32_t lo = s.level_off[h], count = s.level_off[h + 1] - lo;
+    NEED(count <= MP2G_CELLS_PER_LAUNCH, "cells of one height");  // 255 cells: at most 128
+    CellsLevel lv = {};
+    for (uint32_t j = 0; j < count; j++) {
+      const uint32_t node = s.order[lo + j];
+      lv.id[j] = col_ids[node + 1];
+      lv.node[j] = (int16_t)node;
+      lv.left[j] = (int16_t)s.left[node];
+      lv.right[j] = (int16_t)s.right[node];
+    }
+    CK(cells_level_hash(c->stream, variant, lv, count, d_values, n_cols, rows, c->index_work.p, (u64*)d_nodes, (u64*)d_roots, root));
+  }
+  return 0;
+}
+int mp2g_cells_tree_hashes(mp2g_ctx* c, int variant, const uint64_t* col_ids, uint32_t n_cols, const uint32_t* values, uint32_t rows,
+                           uint64_t* roots, uint64_t* nodes) {
+  int rc = cells_args(variant, col_ids, n_cols, rows);
+  if (rc) return rc;
+  if (!rows) return 0;
+  NEED(c && roots && (values || n_cols == 1), "ctx / roots / values");
+  const size_t cells = n_cols - 1, vbytes = (size_t)rows * n_cols * 32;
+  DevBuf dv, dr, dn;
+  if (cells) CK(dv.alloc(vbytes));  // a table without cells is neither uploaded nor read
+  CK(dr.alloc((size_t)rows * 32));
+  if (nodes && cells) CK(dn.alloc(rows * cells * 32));
+  if (cells) CK(hipMemcpyAsync(dv.p, values, vbytes, hipMemcpyHostToDevice, c->stream));
+  rc = mp2g_cells_tree_hashes_dev(c, variant, col_ids, n_cols, (const u32*)dv.p, rows, dr.p, dn.p);
+  if (rc) return rc;
+  CK(hipMemcpyAsync(roots, dr.p, (size_t)rows * 32, hipMemcpyDeviceToHost, c->stream));
+  if (dn.p) CK(hipMemcpyAsync(nodes, dn.p, rows * cells * 32, hipMemcpyDeviceToHost, c->stream));
+  CK(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+// ---- row tree / index tree ---------------------------------------------------------------------
+// words of `values` a shape of n nodes reads: (n - 1) * stride + 8; refused when the byte count does not fit 64 bits
+static int row_args(int variant, const mp2g_tree_shape* t, uint64_t id, uint32_t value_stride, size_t* value_words) {
+  NEED(variant == 0 || variant == 1, "variant");
+  NEED(t, "shape");
+  NEED(id < GL_P, "identifier not canonical (>= p)");
+  NEED(value_stride >= 8, "value_stride >= 8 (a value is 8 words)");
+  const uint64_t n = t->s.size();
+  *value_words = n ? (size_t)((n - 1) * value_stride + 8) : 0;  // n < 2^31, stride < 2^32: below 2^63 words
+  NEED(*value_words <= (SIZE_MAX >> 2), "values size overflows");
+  return 0;
+}
+int mp2g_row_tree_hashes_dev(mp2g_ctx* c, int variant, const mp2g_tree_shape* t, uint64_t id, const uint32_t* d_values,
+                             uint32_t value_stride, const uint64_t* d_payload, uint64_t* d_hashes) {
+  size_t words;
+  int rc = row_args(variant, t, id, value_stride, &words);
+  if (rc) return rc;
+  const size_t n = t->s.size();
+  if (!n) return 0;
+  NEED(c && d_values && d_hashes, "ctx / values / hashes");
+  NEED(aligned16(d_payload) && aligned16(d_hashes), "digest buffers must be 16-byte aligned");
+  const u32* d;
+  rc = shape_on_device(t, c, &d);
+  if (rc) return rc;
+  const int32_t *left = (const int32_t*)d, *right = (const int32_t*)(d + n);
+  const u32 *mn = d + 2 * n, *mx = d + 3 * n, *order = d + 4 * n;
+  for (uint32_t h = 0; h < t->s.levels(); h++) {
+    const uint32_t lo = t->s.level_off[h], count = t->s.level_off[h + 1] - lo;
+    CK(row_level_hash(c->stream, variant, order + lo, count, left, right, mn, mx, id, d_values, value_stride, (const u64*)d_payload,
+                      (u64*)d_hashes));
+  }
+  return 0;
+}
+int mp2g_row_tree_hashes(mp2g_ctx* c, int variant, const mp2g_tree_shape* t, uint64_t id, const uint32_t* values, uint32_t value_stride,
+                         const uint64_t* payload, uint64_t* hashes) {
+  size_t words;
+  int rc = row_args(variant, t, id, value_stride, &words);
+  if (rc) return rc;
+  const size_t n = t->s.size();
+  if (!n) return 0;
+  NEED(c && values && hashes, "ctx / values / hashes");
+  DevBuf dv, dp, dh;
+  CK(dv.alloc(words * sizeof(u32)));
+  CK(dh.alloc(n * 32));
+  if (payload) CK(dp.alloc(n * 32));
+  CK(hipMemcpyAsync(dv.p, values, words * sizeof(u32), hipMemcpyHostToDevice, c->stream));
+  if (payload) CK(hipMemcpyAsync(dp.p, payload, n * 32, hipMemcpyHostToDevice, c->stream));
+  rc = mp2g_row_tree_hashes_dev(c, variant, t, id, (const u32*)dv.p, value_stride, dp.p, dh.p);
+  if (rc) return rc;
+  CK(hipMemcpyAsync(hashes, dh.p, n * 32, hipMemcpyDeviceToHost, c->stream));
+  CK(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+}  // extern "C"

@@ -78,3 +78,72 @@ def index_node_min_max(value, left=None, right=None):
     if left is None:
         raise ValueError("ryhope sbbst is wrong")  # the reference panics: a right child without a left one
     return left[0], right[1]
+
+
+# ---- whole trees on the device (csrc/index_hash.hip): one call per tree kind, one launch per level, no host round trip --------------
+import ctypes  # noqa: E402
+
+TreeShape = _mp2.TreeShape  # from_children(left, right), sbbst(n), describe()
+
+
+def _h(ctx):
+    return ctx.h if ctx is not None else None
+
+
+def _table_values(values, n_cols):
+    """uint32 [rows][n_cols][8]; without columns the array stays as it comes, and the library refuses n_cols = 0"""
+    v = np.ascontiguousarray(values, dtype=np.uint32)
+    return v.reshape(-1, n_cols, 8) if n_cols else v.reshape(v.shape[0] if v.ndim else 0, -1)
+
+
+def cells_tree_hashes(ctx, col_ids, values, variant=0, nodes=False):
+    """`MerkleCell::aggregate` (cell.rs:120-157) for every row's cells tree (mp2g_cells_tree_hashes): the sbbst over positions
+    1..n_cols-1, the cell at position k has id col_ids[k] and value values[row][k]; column 0 is the secondary index and is not a cell.
+    values: uint32 [rows][n_cols][8] as row_digests takes them. Returns roots [rows][4], and with nodes=True also every node's hash
+    [rows][n_cols-1][4] (position k at index k - 1)."""
+    ids = np.ascontiguousarray(col_ids, dtype=np.uint64).ravel()
+    v = _table_values(values, ids.size)
+    rows = v.shape[0]
+    roots = np.zeros((rows, 4), dtype=np.uint64)
+    all_nodes = np.zeros((rows, max(ids.size, 1) - 1, 4), dtype=np.uint64) if nodes else None
+    _mp2._ck(_mp2.load().mp2g_cells_tree_hashes(_h(ctx), int(variant), _mp2._p(ids), ids.size, _mp2._p(v), ctypes.c_uint32(rows), _mp2._p(roots),
+                                                 _mp2._p(all_nodes) if nodes else None))
+    return (roots, all_nodes) if nodes else roots
+
+
+def row_tree_hashes(ctx, shape, id, values, payload=None, variant=0):
+    """`RowPayload::aggregate` (row.rs:257-317) / `IndexNode::aggregate` (index.rs:61-101) for every node of `shape`
+    (mp2g_row_tree_hashes): H(hL || hR || min || max || id || value || payload) with min / max taken down the left / right spine.
+    values: uint32 [n][8], or [n][n_cols][8] to read column 0 of a table in place; payload [n][4] (cells roots, or row-tree roots for
+    the index tree) or None = the empty hash for every node. Returns hashes [n][4]."""
+    n = shape.size
+    v = np.ascontiguousarray(values, dtype=np.uint32).reshape(n, -1) if n else np.zeros((0, 8), dtype=np.uint32)
+    pl = None if payload is None else np.ascontiguousarray(payload, dtype=np.uint64).reshape(n, 4)
+    out = np.zeros((n, 4), dtype=np.uint64)
+    if ctx is not None:
+        ctx._adopt(shape)  # a shape is freed before the context it was used with: closing the context frees it
+    _mp2._ck(_mp2.load().mp2g_row_tree_hashes(_h(ctx), int(variant), shape.h, ctypes.c_uint64(int(id)), _mp2._p(v), ctypes.c_uint32(v.shape[1]),
+                                               None if pl is None else _mp2._p(pl), _mp2._p(out)))
+    return out
+
+
+def table_hashes(ctx, col_ids, values, shape, variant=0):
+    """both halves for a block of rows: values [rows][n_cols][8] go up once, the cells trees' roots stay on the device as the row
+    tree's payload (the two _dev calls, value_stride = n_cols * 8), one download at the end.
+    Returns (row_hashes [rows][4], cells_roots [rows][4], roots = the row tree's root nodes, ascending)."""
+    ids = np.ascontiguousarray(col_ids, dtype=np.uint64).ravel()
+    v = _table_values(values, ids.size)
+    rows = v.shape[0]
+    if shape.size != rows:
+        raise ValueError("the row tree's shape has not one node per row")
+    roots = shape.describe()["roots"]
+    if rows == 0:
+        return np.zeros((0, 4), dtype=np.uint64), np.zeros((0, 4), dtype=np.uint64), roots
+    d_values, d_cells, d_rows = ctx.to_device(v), ctx.alloc(rows * 32), ctx.alloc(rows * 32)
+    try:
+        _mp2.cells_tree_hashes_dev(ctx, variant, ids, d_values, rows, d_cells)
+        _mp2.row_tree_hashes_dev(ctx, variant, shape, ids[0], d_values, ids.size * 8, d_cells, d_rows)
+        return d_rows.download((rows, 4)), d_cells.download((rows, 4)), roots
+    finally:
+        for d in (d_values, d_cells, d_rows):
+            d.free()
