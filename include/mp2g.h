@@ -295,6 +295,14 @@ uint32_t mp2g_tree_shape_num_roots(const mp2g_tree_shape* shape);
 int mp2g_tree_shape_describe(const mp2g_tree_shape* shape, int32_t* left, int32_t* right, uint32_t* height, uint32_t* min_idx,
                              uint32_t* max_idx, uint32_t* roots);
 void mp2g_tree_shape_free(mp2g_tree_shape* shape);
+/* ryhope's touched() (ryhope/src/lib.rs:216-222): the given nodes and all their ancestors up to the roots -- what
+ * MerkleTreeKvDb::aggregate (:179-209) re-hashes after a block, and what mp2g_row_tree_hashes_update re-hashes. nodes receives them
+ * grouped by height (ascending height, ascending node index inside a height: children before parents), *n_nodes their number.
+ * Duplicates in touched collapse; n_touched == 0 gives the empty set. nodes == NULL only counts. cap < the number of nodes is an
+ * error that still sets *n_nodes. An index >= n is refused with a message that names it. Host work only, no GPU is needed; the cost
+ * is that of the closure (plus a sort of it), not of the shape. */
+int mp2g_tree_shape_touched(const mp2g_tree_shape* shape, const uint32_t* touched, uint32_t n_touched, uint32_t* nodes /* [cap] or NULL */,
+                            uint32_t cap, uint32_t* n_nodes);
 /* every row's cells tree (cell.rs:120-157: H(H(left) || H(right) || id || value), 17 limbs): the sbbst over the positions
  * 1..n_cols-1; the cell at position k has the identifier col_ids[k] and the value values[row][k] (column 0 is the secondary index
  * and is not a cell). values [rows][n_cols][8] as mp2g_row_digests takes them (u256.rs:870-877), so one upload serves both.
@@ -307,6 +315,22 @@ int mp2g_cells_tree_hashes(mp2g_ctx* ctx, int variant, const uint64_t* col_ids, 
                            uint32_t rows, uint64_t* roots, uint64_t* nodes);
 int mp2g_cells_tree_hashes_dev(mp2g_ctx* ctx, int variant, const uint64_t* col_ids /* host */, uint32_t n_cols, const uint32_t* d_values,
                                uint32_t rows, uint64_t* d_roots, uint64_t* d_nodes);
+/* the steady state of a block (MerkleTreeKvDb::aggregate over touched(), ryhope/src/lib.rs:179-222, for the rows' cells trees):
+ * the complete cells trees of the rows row_idx[0..n_idx) recomputed from the current table. values is the WHOLE table
+ * [rows][n_cols][8]; roots [rows][4] and nodes ([rows][n_cols-1][4] or NULL) are the whole table's too, in and out: only the listed
+ * rows' entries are written. Duplicates in row_idx are allowed; n_idx == 0 returns 0 and launches nothing; n_cols == 1 writes
+ * hash_no_pad(&[]) for the listed rows. Refused before any launch: what mp2g_cells_tree_hashes refuses, a row index >= rows (named
+ * in the message), row_idx NULL with n_idx != 0, and for _dev misaligned d_roots / d_nodes.
+ * _dev: col_ids and row_idx stay host arrays (row_idx may be reused or freed as soon as the call returns); stream ordered. The
+ * context keeps the working buffer of mp2g_cells_tree_hashes_dev (here n_idx * (n_cols-1) * 32 bytes) and one device buffer for
+ * the index lists; either grows, with one synchronisation, when a call needs more. The lists are uploaded from a ring of 4 pinned
+ * slots of the context's, so update calls with different lists may be queued back to back without a synchronisation by the caller:
+ * a call waits only when the upload of the fourth call before it has not finished yet. */
+int mp2g_cells_tree_hashes_rows(mp2g_ctx* ctx, int variant, const uint64_t* col_ids, uint32_t n_cols, const uint32_t* values /* whole table */,
+                                uint32_t rows, const uint32_t* row_idx, uint32_t n_idx, uint64_t* roots /* [rows][4] in and out */,
+                                uint64_t* nodes /* in and out, or NULL */);
+int mp2g_cells_tree_hashes_rows_dev(mp2g_ctx* ctx, int variant, const uint64_t* col_ids /* host */, uint32_t n_cols, const uint32_t* d_values,
+                                    uint32_t rows, const uint32_t* row_idx /* host */, uint32_t n_idx, uint64_t* d_roots, uint64_t* d_nodes);
 /* every node of a row tree (row.rs:257-317) or index tree (index.rs:61-101) of shape `shape`:
  * H(hL || hR || min || max || id || value || payload), 37 limbs. Node i's value is the 8 big-endian u32 words at
  * values + i * value_stride (value_stride in u32 words, >= 8: pass n_cols * 8 to read column 0 of the table in place); payload
@@ -321,6 +345,28 @@ int mp2g_row_tree_hashes(mp2g_ctx* ctx, int variant, const mp2g_tree_shape* shap
                          const uint64_t* payload, uint64_t* hashes);
 int mp2g_row_tree_hashes_dev(mp2g_ctx* ctx, int variant, const mp2g_tree_shape* shape, uint64_t id, const uint32_t* d_values,
                              uint32_t value_stride, const uint64_t* d_payload, uint64_t* d_hashes);
+/* the same for the touched nodes and their ancestors only (MerkleTreeKvDb::aggregate, ryhope/src/lib.rs:179-209, re-aggregates
+ * touched(), :216-222; the set is mp2g_tree_shape_touched's). On entry hashes [n][4] holds valid hashes for every node outside
+ * that set; on return every node of the set holds its hash under the current values, payload and shape, and no word outside the
+ * set has been written. The caller lists in touched every node whose value, payload or children differ from what hashes was
+ * computed for: after an insertion the shape is a new mp2g_tree_shape, and touched holds the new node and the nodes whose child
+ * pointers changed. min / max need no entry of their own: a node's min_idx and max_idx lie in its own subtree (row.rs:261-285), so a
+ * change under them puts the node in the set. n_touched == 0 returns 0 and launches nothing. Refused before any launch: what
+ * mp2g_row_tree_hashes refuses, a touched index >= n (named in the message), touched NULL with n_touched != 0, and for _dev
+ * misaligned d_payload / d_hashes.
+ * Poseidon2, while no level of the set has more than mp2g_row_tree_update_fused_width() nodes and the set has at most 256 levels:
+ * ONE launch of one workgroup for the whole set (16 lanes per node, a barrier between levels). Everything else (original Poseidon,
+ * wider sets, degenerate chains): one launch per level of the set.
+ * _dev: touched stays a host array (it may be reused or freed as soon as the call returns); stream ordered; the index lists go
+ * through the context's ring of pinned slots as mp2g_cells_tree_hashes_rows_dev describes, so calls with different lists may be
+ * queued back to back. */
+uint32_t mp2g_row_tree_update_fused_width(void);
+int mp2g_row_tree_hashes_update(mp2g_ctx* ctx, int variant, const mp2g_tree_shape* shape, uint64_t id, const uint32_t* values,
+                                uint32_t value_stride, const uint64_t* payload, const uint32_t* touched, uint32_t n_touched,
+                                uint64_t* hashes /* [n][4] in and out */);
+int mp2g_row_tree_hashes_update_dev(mp2g_ctx* ctx, int variant, const mp2g_tree_shape* shape, uint64_t id, const uint32_t* d_values,
+                                    uint32_t value_stride, const uint64_t* d_payload, const uint32_t* touched /* host */, uint32_t n_touched,
+                                    uint64_t* d_hashes);
 
 /* ---- proof wire format between tree levels / GPUs ------------------------------------------ */
 /* bincode 1.3 (little-endian fixed-width ints, u64 length prefixes) serialization of plonky2's

@@ -46,6 +46,7 @@ def load():
         for f in (_lib.mp2g_tree_shape_size, _lib.mp2g_tree_shape_num_levels, _lib.mp2g_tree_shape_num_roots):
             f.restype, f.argtypes = ctypes.c_uint32, [ctypes.c_void_p]
         _lib.mp2g_tree_shape_free.restype, _lib.mp2g_tree_shape_free.argtypes = None, [ctypes.c_void_p]
+        _lib.mp2g_row_tree_update_fused_width.restype, _lib.mp2g_row_tree_update_fused_width.argtypes = ctypes.c_uint32, []
     return _lib
 
 
@@ -1004,6 +1005,16 @@ class TreeShape:
         _ck(load().mp2g_tree_shape_describe(self.h, *(_p(out[k]) for k in ("left", "right", "height", "min_idx", "max_idx", "roots"))))
         return out
 
+    def touched(self, nodes):
+        """mp2g_tree_shape_touched: the given nodes and all their ancestors (ryhope's touched(), ryhope/src/lib.rs:216-222), uint32,
+        grouped by height (ascending height, ascending node index inside a height); duplicates collapse. Needs no GPU."""
+        t = _arr(nodes, np.uint32).ravel()
+        n = ctypes.c_uint32()
+        _ck(load().mp2g_tree_shape_touched(self.h, _p(t), ctypes.c_uint32(t.size), None, ctypes.c_uint32(0), ctypes.byref(n)))
+        out = np.empty(n.value, dtype=np.uint32)
+        _ck(load().mp2g_tree_shape_touched(self.h, _p(t), ctypes.c_uint32(t.size), _p(out), n, ctypes.byref(n)))
+        return out
+
     def free(self):
         if self.h:
             load().mp2g_tree_shape_free(self.h)
@@ -1035,6 +1046,29 @@ def row_tree_hashes_dev(ctx, variant, shape, ident, d_values, value_stride, d_pa
         ctx._adopt(shape)
     _ck(load().mp2g_row_tree_hashes_dev(ctx.h if ctx is not None else None, int(variant), shape.h, ctypes.c_uint64(int(ident)), _raw(d_values),
                                         ctypes.c_uint32(int(value_stride)), _raw(d_payload), _raw(d_hashes)))
+
+
+def row_tree_update_fused_width():
+    """mp2g_row_tree_update_fused_width: the widest level of a touched closure that mp2g_row_tree_hashes_update still hashes in one launch"""
+    return int(load().mp2g_row_tree_update_fused_width())
+
+
+def cells_tree_hashes_rows_dev(ctx, variant, col_ids, d_values, rows, row_idx, d_roots, d_nodes=None):
+    """mp2g_cells_tree_hashes_rows_dev: the cells trees of the listed rows only; stream ordered; col_ids and row_idx are host arrays"""
+    ids, idx = _arr(col_ids).ravel(), _arr(row_idx, np.uint32).ravel()
+    _ck(load().mp2g_cells_tree_hashes_rows_dev(ctx.h if ctx is not None else None, int(variant), _p(ids), ids.size, _raw(d_values),
+                                               ctypes.c_uint32(rows), _p(idx), ctypes.c_uint32(idx.size), _raw(d_roots), _raw(d_nodes)))
+
+
+def row_tree_hashes_update_dev(ctx, variant, shape, ident, d_values, value_stride, d_payload, touched, d_hashes):
+    """mp2g_row_tree_hashes_update_dev: the touched nodes and their ancestors only; stream ordered; touched is a host array. The
+    shape joins the context's handles as in row_tree_hashes_dev."""
+    if ctx is not None:
+        ctx._adopt(shape)
+    t = _arr(touched, np.uint32).ravel()
+    _ck(load().mp2g_row_tree_hashes_update_dev(ctx.h if ctx is not None else None, int(variant), shape.h, ctypes.c_uint64(int(ident)),
+                                               _raw(d_values), ctypes.c_uint32(int(value_stride)), _raw(d_payload), _p(t),
+                                               ctypes.c_uint32(t.size), _raw(d_hashes)))
 
 
 def leaf_permutations_queued():

@@ -65,6 +65,10 @@ void mp2g_ctx_destroy(mp2g_ctx* c) {
   (void)hipEventDestroy(c->ev1);
   c->ntt.plans.clear();
   c->ntt.cosets.clear();
+  for (auto& st : c->index_stage) {
+    if (st.host) (void)hipHostFree(st.host);
+    if (st.done) (void)hipEventDestroy(st.done);
+  }
   if (c->own_stream) (void)hipStreamDestroy(c->stream);
   delete c;
 }

@@ -49,6 +49,20 @@ struct mp2g_ctx {
   mp2g::DevBuf wit_vals;  // slot tables of the device witness executor (mp2g_witness_program_run_dev), grown on demand
   mp2g::DevBuf wit_rows;  // its row-major staging wire matrices
   mp2g::DevBuf index_work;  // node-major digests of the rows' cells trees (mp2g_cells_tree_hashes_dev), grown on demand
+  // The index lists of the update calls (mp2g_cells_tree_hashes_rows_dev, mp2g_row_tree_hashes_update_dev) are host arrays of the
+  // caller's that the kernels read on the device. index_lists is their ONE device copy: an upload is ordered on the stream behind the
+  // kernels of the call before, so one buffer serves calls queued back to back. What an upload reads on the host must outlive the
+  // call, so it comes from a ring of pinned slots: a call copies its lists into the next slot and records `done` behind the upload;
+  // a slot is written again only after its `done` has passed (a wait only when INDEX_STAGE_SLOTS uploads are still queued).
+  mp2g::DevBuf index_lists;
+  static constexpr uint32_t INDEX_STAGE_SLOTS = 4;
+  struct IndexStage {
+    uint32_t* host = nullptr;  // hipHostMalloc
+    size_t bytes = 0;
+    hipEvent_t done = nullptr;
+    bool pending = false;
+  } index_stage[INDEX_STAGE_SLOTS];
+  uint32_t index_stage_next = 0;
   // The provers' per-batch working buffers (coefficients, LDE values, Merkle levels of oracles 1.., quotient values, FRI layers):
   // everything a prove() recomputes from its inputs and nobody reads once its kernels have run. All provers of a context run on
   // the context's ONE stream, so they can use the same memory one after the other: the scratch is as large as the largest

@@ -3,6 +3,8 @@
 #include "ctx.h"
 #include "index_hash.h"
 #include "tree_shape.h"
+#include <algorithm>
+#include <cstring>
 #include <exception>
 #include <new>
 
@@ -64,6 +66,66 @@ static int shape_on_device(const mp2g_tree_shape* t, mp2g_ctx* c, const u32** d)
 }
 static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
+// a[0..na) followed by b[0..nb), host words, to the context's list buffer on its stream (ctx.h: one device copy, a ring of pinned
+// slots under it); *d is the device address of a[0]
+static int stage_lists(mp2g_ctx* c, const u32* a, size_t na, const u32* b, size_t nb, const u32** d) {
+  const size_t need = (na + nb) * sizeof(u32);
+  CK(hipSetDevice(c->device));
+  mp2g_ctx::IndexStage& slot = c->index_stage[c->index_stage_next++ % mp2g_ctx::INDEX_STAGE_SLOTS];
+  if (slot.pending) {  // the upload that last read this slot
+    CK(hipEventSynchronize(slot.done));
+    slot.pending = false;
+  }
+  if (!slot.done) CK(hipEventCreateWithFlags(&slot.done, hipEventDisableTiming));
+  if (slot.bytes < need) {
+    if (slot.host) (void)hipHostFree(slot.host);
+    slot.host = nullptr;
+    slot.bytes = 0;
+    const size_t cap = need < 4096 ? 4096 : need + need / 2;
+    CK(hipHostMalloc((void**)&slot.host, cap, hipHostMallocDefault));
+    slot.bytes = cap;
+  }
+  if (c->index_lists.bytes < need) {
+    CK(hipStreamSynchronize(c->stream));  // a kernel queued earlier may still read the old buffer
+    CK(c->index_lists.alloc(need < 4096 ? 4096 : need + need / 2));
+  }
+  if (na) memcpy(slot.host, a, na * sizeof(u32));
+  if (nb) memcpy(slot.host + na, b, nb * sizeof(u32));
+  CK(hipMemcpyAsync(c->index_lists.p, slot.host, need, hipMemcpyHostToDevice, c->stream));
+  CK(hipEventRecord(slot.done, c->stream));
+  slot.pending = true;
+  *d = (const u32*)c->index_lists.p;
+  return 0;
+}
+
+// the level schedule of the sbbst over `cells` positions: launch(lv, count, root) for the cells of each height, lowest first
+template <class F> static int cells_levels(const uint64_t* col_ids, uint32_t cells, F&& launch) {
+  TreeShape s;
+  int rc = guarded([&] {  // at most 255 nodes
+    std::vector<int32_t> l(cells), r(cells);
+    sbbst_fill(cells, l.data(), r.data());
+    const char* err = tree_shape_build(l.data(), r.data(), cells, s);
+    return err ? fail("cells tree: %s", err) : 0;
+  });
+  if (rc) return rc;
+  const int root = (int)sbbst_root(cells) - 1;
+  for (uint32_t h = 0; h < s.levels(); h++) {
+    const uint32_t lo = s.level_off[h], count = s.level_off[h + 1] - lo;
+    NEED(count <= MP2G_CELLS_PER_LAUNCH, "cells of one height");  // 255 cells: at most 128
+    CellsLevel lv = {};
+    for (uint32_t j = 0; j < count; j++) {
+      const uint32_t node = s.order[lo + j];
+      lv.id[j] = col_ids[node + 1];
+      lv.node[j] = (int16_t)node;
+      lv.left[j] = (int16_t)s.left[node];
+      lv.right[j] = (int16_t)s.right[node];
+    }
+    rc = launch(lv, count, root);
+    if (rc) return rc;
+  }
+  return 0;
+}
+
 extern "C" {
 
 int mp2g_tree_shape_create(const int32_t* left, const int32_t* right, uint32_t n, mp2g_tree_shape** out) {
@@ -97,6 +159,21 @@ int mp2g_tree_shape_describe(const mp2g_tree_shape* t, int32_t* left, int32_t* r
     for (size_t i = 0; i < t->s.roots.size(); i++) roots[i] = t->s.roots[i];
   return 0;
 }
+int mp2g_tree_shape_touched(const mp2g_tree_shape* t, const uint32_t* touched, uint32_t n_touched, uint32_t* nodes, uint32_t cap,
+                            uint32_t* n_nodes) {
+  NEED(t && n_nodes, "shape / n_nodes");
+  NEED(touched || !n_touched, "touched list missing");
+  return guarded([&] {
+    TreeTouched c;
+    if (tree_shape_touched(t->s, touched, n_touched, c)) return fail("invalid argument: %s", c.err);
+    *n_nodes = (uint32_t)c.nodes.size();
+    if (!nodes) return 0;
+    if (cap < c.nodes.size()) return fail("invalid argument: cap %u is below the closure's %zu nodes", cap, c.nodes.size());
+    std::copy(c.nodes.begin(), c.nodes.end(), nodes);
+    return 0;
+  });
+}
+uint32_t mp2g_row_tree_update_fused_width(void) { return MP2G_ROW_UPDATE_FUSED_WIDTH; }
 void mp2g_tree_shape_free(mp2g_tree_shape* t) {
   delete t;  // hipFree of the device arrays waits for every kernel that may still read them
 }
@@ -108,6 +185,22 @@ static int cells_args(int variant, const uint64_t* col_ids, uint32_t n_cols, uin
   NEED(col_ids, "col_ids");
   for (uint32_t k = 0; k < n_cols; k++) NEED(col_ids[k] < GL_P, "column identifier not canonical (>= p)");
   NEED(rows <= 0x80000000u, "rows <= 2^31");  // one lane per row along grid.x
+  return 0;
+}
+static int cells_rows_args(int variant, const uint64_t* col_ids, uint32_t n_cols, uint32_t rows, const uint32_t* row_idx, uint32_t n_idx) {
+  int rc = cells_args(variant, col_ids, n_cols, rows);
+  if (rc) return rc;
+  NEED(row_idx || !n_idx, "row_idx list missing");
+  for (uint32_t j = 0; j < n_idx; j++)
+    if (row_idx[j] >= rows) return fail("invalid argument: row index %u is outside the table's %u rows", row_idx[j], rows);
+  return 0;
+}
+// the context's working buffer, grown when a call needs more
+static int cells_work(mp2g_ctx* c, size_t work_bytes) {
+  if (c->index_work.bytes < work_bytes) {
+    CK(hipStreamSynchronize(c->stream));  // a kernel queued earlier may still use the old buffer
+    CK(c->index_work.alloc(work_bytes));
+  }
   return 0;
 }
 int mp2g_cells_tree_hashes_dev(mp2g_ctx* c, int variant, const uint64_t* col_ids, uint32_t n_cols, const uint32_t* d_values,
@@ -123,32 +216,68 @@ int mp2g_cells_tree_hashes_dev(mp2g_ctx* c, int variant, const uint64_t* col_ids
     return 0;
   }
   NEED(d_values, "values");
-  TreeShape s;
-  rc = guarded([&] {  // at most 255 nodes
-    std::vector<int32_t> l(cells), r(cells);
-    sbbst_fill(cells, l.data(), r.data());
-    const char* err = tree_shape_build(l.data(), r.data(), cells, s);
-    return err ? fail("cells tree: %s", err) : 0;
+  rc = cells_work(c, (size_t)cells * rows * 4 * sizeof(u64));
+  if (rc) return rc;
+  return cells_levels(col_ids, cells, [&](const CellsLevel& lv, uint32_t count, int root) {
+    CK(cells_level_hash(c->stream, variant, lv, count, d_values, n_cols, rows, c->index_work.p, (u64*)d_nodes, (u64*)d_roots, root));
+    return 0;
+  });
+}
+// the listed rows only: the schedule above with a row indirection and a compact working buffer
+int mp2g_cells_tree_hashes_rows_dev(mp2g_ctx* c, int variant, const uint64_t* col_ids, uint32_t n_cols, const uint32_t* d_values,
+                                    uint32_t rows, const uint32_t* row_idx, uint32_t n_idx, uint64_t* d_roots, uint64_t* d_nodes) {
+  int rc = cells_rows_args(variant, col_ids, n_cols, rows, row_idx, n_idx);
+  if (rc) return rc;
+  if (!n_idx) return 0;
+  NEED(aligned16(d_roots) && aligned16(d_nodes), "digest buffers must be 16-byte aligned");
+  NEED(c && d_roots, "ctx / roots");
+  const uint32_t cells = n_cols - 1;
+  NEED(d_values || !cells, "values");
+  const u32* d_idx;
+  rc = stage_lists(c, row_idx, n_idx, nullptr, 0, &d_idx);
+  if (rc) return rc;
+  if (!cells) {  // row.rs:299-302
+    CK(cells_rows_empty_roots(c->stream, (u64*)d_roots, d_idx, n_idx));
+    return 0;
+  }
+  rc = cells_work(c, (size_t)cells * n_idx * 4 * sizeof(u64));
+  if (rc) return rc;
+  return cells_levels(col_ids, cells, [&](const CellsLevel& lv, uint32_t count, int root) {
+    CK(cells_rows_level_hash(c->stream, variant, lv, count, d_values, n_cols, d_idx, n_idx, c->index_work.p, (u64*)d_nodes, (u64*)d_roots,
+                             root));
+    return 0;
+  });
+}
+int mp2g_cells_tree_hashes_rows(mp2g_ctx* c, int variant, const uint64_t* col_ids, uint32_t n_cols, const uint32_t* values, uint32_t rows,
+                                const uint32_t* row_idx, uint32_t n_idx, uint64_t* roots, uint64_t* nodes) {
+  int rc = cells_rows_args(variant, col_ids, n_cols, rows, row_idx, n_idx);
+  if (rc) return rc;
+  if (!n_idx) return 0;
+  NEED(c && roots && (values || n_cols == 1), "ctx / roots / values");
+  const size_t cells = n_cols - 1, vbytes = (size_t)rows * n_cols * 32;
+  // the device's view of roots / nodes: only the listed rows of it are meaningful, and only they are copied out. Declared before
+  // the device buffers, whose release waits for the device: a copy still in flight on an error path ends before these go
+  std::vector<u64> hr, hn;
+  DevBuf dv, dr, dn;
+  rc = guarded([&] {
+    hr.resize((size_t)rows * 4);
+    if (nodes && cells) hn.resize((size_t)rows * cells * 4);
+    return 0;
   });
   if (rc) return rc;
-  const size_t work_bytes = (size_t)cells * rows * 4 * sizeof(u64);
-  if (c->index_work.bytes < work_bytes) {
-    CK(hipStreamSynchronize(c->stream));  // a kernel queued earlier may still use the old buffer
-    CK(c->index_work.alloc(work_bytes));
-  }
-  const int root = (int)sbbst_root(cells) - 1;
-  for (uint32_t h = 0; h < s.levels(); h++) {
-    const uint32_t lo = s.level_off[h], count = s.level_off[h + 1] - lo;
-    NEED(count <= MP2G_CELLS_PER_LAUNCH, "cells of one height");  // 255 cells: at most 128
-    CellsLevel lv = {};
-    for (uint32_t j = 0; j < count; j++) {
-      const uint32_t node = s.order[lo + j];
-      lv.id[j] = col_ids[node + 1];
-      lv.node[j] = (int16_t)node;
-      lv.left[j] = (int16_t)s.left[node];
-      lv.right[j] = (int16_t)s.right[node];
-    }
-    CK(cells_level_hash(c->stream, variant, lv, count, d_values, n_cols, rows, c->index_work.p, (u64*)d_nodes, (u64*)d_roots, root));
+  if (cells) CK(dv.alloc(vbytes));
+  CK(dr.alloc((size_t)rows * 32));
+  if (nodes && cells) CK(dn.alloc(rows * cells * 32));
+  if (cells) CK(hipMemcpyAsync(dv.p, values, vbytes, hipMemcpyHostToDevice, c->stream));
+  rc = mp2g_cells_tree_hashes_rows_dev(c, variant, col_ids, n_cols, (const u32*)dv.p, rows, row_idx, n_idx, dr.p, dn.p);
+  if (rc) return rc;
+  CK(hipMemcpyAsync(hr.data(), dr.p, (size_t)rows * 32, hipMemcpyDeviceToHost, c->stream));
+  if (dn.p) CK(hipMemcpyAsync(hn.data(), dn.p, rows * cells * 32, hipMemcpyDeviceToHost, c->stream));
+  CK(hipStreamSynchronize(c->stream));
+  for (uint32_t j = 0; j < n_idx; j++) {
+    const size_t r = row_idx[j];
+    std::copy(hr.begin() + r * 4, hr.begin() + r * 4 + 4, roots + r * 4);
+    if (dn.p) std::copy(hn.begin() + r * cells * 4, hn.begin() + (r + 1) * cells * 4, nodes + r * cells * 4);
   }
   return 0;
 }
@@ -223,6 +352,78 @@ int mp2g_row_tree_hashes(mp2g_ctx* c, int variant, const mp2g_tree_shape* t, uin
   if (rc) return rc;
   CK(hipMemcpyAsync(hashes, dh.p, n * 32, hipMemcpyDeviceToHost, c->stream));
   CK(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+// ---- the touched nodes and their ancestors only (MerkleTreeKvDb::aggregate over touched(), ryhope/src/lib.rs:179-222) ----------------
+// everything that is decided on the host: the full call's refusals, the list, the closure
+static int row_update_args(int variant, const mp2g_tree_shape* t, uint64_t id, uint32_t value_stride, const uint32_t* touched,
+                           uint32_t n_touched, size_t* value_words, TreeTouched& closure) {
+  int rc = row_args(variant, t, id, value_stride, value_words);
+  if (rc) return rc;
+  NEED(touched || !n_touched, "touched list missing");
+  return guarded([&] { return tree_shape_touched(t->s, touched, n_touched, closure) ? fail("invalid argument: %s", closure.err) : 0; });
+}
+static int row_update_launch(mp2g_ctx* c, int variant, const mp2g_tree_shape* t, uint64_t id, const uint32_t* d_values,
+                             uint32_t value_stride, const uint64_t* d_payload, const TreeTouched& closure, uint64_t* d_hashes) {
+  const size_t n = t->s.size();
+  const u32* d;
+  int rc = shape_on_device(t, c, &d);
+  if (rc) return rc;
+  const int32_t *left = (const int32_t*)d, *right = (const int32_t*)(d + n);
+  const u32 *mn = d + 2 * n, *mx = d + 3 * n;
+  const u32* d_order;
+  rc = stage_lists(c, closure.nodes.data(), closure.nodes.size(), closure.level_off.data(), closure.level_off.size(), &d_order);
+  if (rc) return rc;
+  if (variant == MP2G_POSEIDON2 && closure.widest <= MP2G_ROW_UPDATE_FUSED_WIDTH && closure.levels() <= MP2G_ROW_UPDATE_FUSED_LEVELS) {
+    CK(row_update_fused(c->stream, d_order, d_order + closure.nodes.size(), closure.levels(), left, right, mn, mx, id, d_values, value_stride,
+                        (const u64*)d_payload, (u64*)d_hashes));
+    return 0;
+  }
+  for (uint32_t l = 0; l < closure.levels(); l++) {
+    const uint32_t lo = closure.level_off[l], count = closure.level_off[l + 1] - lo;
+    CK(row_level_hash(c->stream, variant, d_order + lo, count, left, right, mn, mx, id, d_values, value_stride, (const u64*)d_payload,
+                      (u64*)d_hashes));
+  }
+  return 0;
+}
+int mp2g_row_tree_hashes_update_dev(mp2g_ctx* c, int variant, const mp2g_tree_shape* t, uint64_t id, const uint32_t* d_values,
+                                    uint32_t value_stride, const uint64_t* d_payload, const uint32_t* touched, uint32_t n_touched,
+                                    uint64_t* d_hashes) {
+  size_t words;
+  TreeTouched closure;
+  int rc = row_update_args(variant, t, id, value_stride, touched, n_touched, &words, closure);
+  if (rc) return rc;
+  if (closure.nodes.empty()) return 0;
+  NEED(aligned16(d_payload) && aligned16(d_hashes), "digest buffers must be 16-byte aligned");
+  NEED(c && d_values && d_hashes, "ctx / values / hashes");
+  return row_update_launch(c, variant, t, id, d_values, value_stride, d_payload, closure, d_hashes);
+}
+int mp2g_row_tree_hashes_update(mp2g_ctx* c, int variant, const mp2g_tree_shape* t, uint64_t id, const uint32_t* values,
+                                uint32_t value_stride, const uint64_t* payload, const uint32_t* touched, uint32_t n_touched,
+                                uint64_t* hashes) {
+  size_t words;
+  TreeTouched closure;
+  int rc = row_update_args(variant, t, id, value_stride, touched, n_touched, &words, closure);
+  if (rc) return rc;
+  if (closure.nodes.empty()) return 0;
+  NEED(c && values && hashes, "ctx / values / hashes");
+  const size_t n = t->s.size();
+  std::vector<u64> back;  // the device's hashes: only the closure's entries are copied out to the caller's (declared first: see above)
+  DevBuf dv, dp, dh;
+  rc = guarded([&] { back.resize(n * 4); return 0; });
+  if (rc) return rc;
+  CK(dv.alloc(words * sizeof(u32)));
+  CK(dh.alloc(n * 32));
+  if (payload) CK(dp.alloc(n * 32));
+  CK(hipMemcpyAsync(dv.p, values, words * sizeof(u32), hipMemcpyHostToDevice, c->stream));
+  CK(hipMemcpyAsync(dh.p, hashes, n * 32, hipMemcpyHostToDevice, c->stream));
+  if (payload) CK(hipMemcpyAsync(dp.p, payload, n * 32, hipMemcpyHostToDevice, c->stream));
+  rc = row_update_launch(c, variant, t, id, (const u32*)dv.p, value_stride, dp.p, closure, dh.p);
+  if (rc) return rc;
+  CK(hipMemcpyAsync(back.data(), dh.p, n * 32, hipMemcpyDeviceToHost, c->stream));
+  CK(hipStreamSynchronize(c->stream));
+  for (uint32_t i : closure.nodes) std::copy(back.begin() + (size_t)i * 4, back.begin() + (size_t)i * 4 + 4, hashes + (size_t)i * 4);
   return 0;
 }
 

@@ -12,9 +12,15 @@
 //
 // Also ryhope's self-balanced BST over the positions 1..n (ryhope/src/tree/sbbst.rs: root :251-257, children :301-333 and :487-503),
 // the shape of a cells tree and of the block tree; position k is node k - 1.
-// Host code only, no HIP: tools/hosttest/tree_shape_test.cpp compiles it alone.
+//
+// tree_shape_touched is ryhope's touched() (ryhope/src/lib.rs:216-222): the dirty nodes and their lineages up to the roots, which is
+// all that MerkleTreeKvDb::aggregate (:179-209) re-hashes after a block. It walks parent[] from each given node until it meets a node
+// it has already taken, so its cost is the closure's size plus a sort, whatever the shape's.
+// Host code only, no HIP: tools/hosttest/tree_shape_test.cpp and tree_touched_test.cpp compile it alone.
 #pragma once
 #include <stdint.h>
+#include <stdio.h>
+#include <algorithm>
 #include <vector>
 
 namespace mp2g {
@@ -25,6 +31,9 @@ struct TreeShape {
   std::vector<uint32_t> roots;                      // nodes without a parent, ascending
   std::vector<uint32_t> order;                      // [n] the nodes sorted by height (ascending node index inside a height)
   std::vector<uint32_t> level_off;                  // [levels + 1]: level h is order[level_off[h] .. level_off[h + 1])
+  std::vector<int32_t> parent;                      // [n], -1 for a root
+  mutable std::vector<uint8_t> mark;                // [n] all zero between calls: tree_shape_touched's "already taken" (why a shape
+                                                    // is not to be used from two threads at once)
   uint32_t size() const { return (uint32_t)left.size(); }
   uint32_t levels() const { return (uint32_t)level_off.size() - 1; }
 };
@@ -59,6 +68,8 @@ inline const char* tree_shape_build(const int32_t* left, const int32_t* right, u
   s.left.assign(left, left + n);
   s.right.assign(right, right + n);
   s.height.assign(n, 0);
+  s.parent.assign(n, -1);
+  s.mark.assign(n, 0);
   s.min_idx.resize(n);
   s.max_idx.resize(n);
   uint32_t top = 0;
@@ -71,6 +82,8 @@ inline const char* tree_shape_build(const int32_t* left, const int32_t* right, u
     s.height[i] = h;
     s.min_idx[i] = l >= 0 ? s.min_idx[l] : i;
     s.max_idx[i] = r >= 0 ? s.max_idx[r] : i;
+    if (l >= 0) s.parent[l] = (int32_t)i;
+    if (r >= 0) s.parent[r] = (int32_t)i;
     if (h > top) top = h;
   }
   s.roots.swap(roots);
@@ -82,6 +95,51 @@ inline const char* tree_shape_build(const int32_t* left, const int32_t* right, u
     s.order.resize(n);
     for (uint32_t i = 0; i < n; i++) s.order[fill[s.height[i]]++] = i;
   }
+  return nullptr;
+}
+
+// The closure of a set of touched nodes: they and all their ancestors, as the compact level lists the update kernels take.
+struct TreeTouched {
+  std::vector<uint32_t> nodes;      // grouped by height in the shape's own order: ascending height, ascending node index inside one
+  std::vector<uint32_t> level_off;  // [levels + 1]: the nodes of the l-th height that occurs are nodes[level_off[l] .. level_off[l + 1])
+  uint32_t widest = 0;              // the largest level
+  char err[96] = {0};               // why the last call was refused
+  uint32_t levels() const { return (uint32_t)level_off.size() - 1; }
+};
+// nullptr, or why the list is refused (out.err: an index >= n, named; nothing out of bounds is read, and out is then empty).
+// Duplicates collapse; k = 0 gives the empty closure (no level). Heights that no closure node has make no level.
+inline const char* tree_shape_touched(const TreeShape& s, const uint32_t* touched, size_t k, TreeTouched& out) {
+  out.nodes.clear();
+  out.level_off.assign(1, 0);
+  out.widest = 0;
+  out.err[0] = 0;
+  const uint32_t n = s.size();
+  if (k && !touched) {
+    snprintf(out.err, sizeof out.err, "touched list missing");
+    return out.err;
+  }
+  for (size_t j = 0; j < k; j++) {
+    const uint32_t t = touched[j];
+    if (t >= n) {
+      for (uint32_t i : out.nodes) s.mark[i] = 0;
+      out.nodes.clear();
+      snprintf(out.err, sizeof out.err, "touched index %u is outside the shape's %u nodes", t, n);
+      return out.err;
+    }
+    for (int64_t i = t; i >= 0 && !s.mark[i]; i = s.parent[i]) {  // up to the root or to a lineage already taken
+      s.mark[i] = 1;
+      out.nodes.push_back((uint32_t)i);
+    }
+  }
+  for (uint32_t i : out.nodes) s.mark[i] = 0;
+  std::sort(out.nodes.begin(), out.nodes.end(), [&s](uint32_t a, uint32_t b) {
+    return s.height[a] != s.height[b] ? s.height[a] < s.height[b] : a < b;
+  });
+  for (size_t j = 0; j < out.nodes.size(); j++) {
+    if (j && s.height[out.nodes[j]] != s.height[out.nodes[j - 1]]) out.level_off.push_back((uint32_t)j);
+  }
+  if (!out.nodes.empty()) out.level_off.push_back((uint32_t)out.nodes.size());
+  for (uint32_t l = 0; l + 1 < out.level_off.size(); l++) out.widest = std::max(out.widest, out.level_off[l + 1] - out.level_off[l]);
   return nullptr;
 }
 

@@ -147,3 +147,91 @@ def table_hashes(ctx, col_ids, values, shape, variant=0):
     finally:
         for d in (d_values, d_cells, d_rows):
             d.free()
+
+
+# ---- the steady state: a block changes a handful of rows (MerkleTreeKvDb::aggregate over touched(), ryhope/src/lib.rs:179-222) ---------
+def cells_tree_hashes_rows(ctx, col_ids, values, row_idx, roots, nodes=None, variant=0):
+    """mp2g_cells_tree_hashes_rows: the complete cells trees of the rows `row_idx` recomputed from the current table `values`
+    (uint32 [rows][n_cols][8], the whole table). roots [rows][4] and nodes ([rows][n_cols-1][4] or None) are uint64 arrays of the
+    caller's, written in place at the listed rows only; duplicates in row_idx are allowed. Returns roots."""
+    ids = np.ascontiguousarray(col_ids, dtype=np.uint64).ravel()
+    v = _table_values(values, ids.size)
+    rows = v.shape[0]
+    idx = np.ascontiguousarray(row_idx, dtype=np.uint32).ravel()
+    for a, shape in ((roots, (rows, 4)), (nodes, (rows, max(ids.size, 1) - 1, 4))):
+        if a is not None and not (isinstance(a, np.ndarray) and a.dtype == np.uint64 and a.flags.c_contiguous and a.shape == shape):
+            raise ValueError(f"roots / nodes: a contiguous uint64 array of shape {shape} that the call can write in place")
+    _mp2._ck(_mp2.load().mp2g_cells_tree_hashes_rows(_h(ctx), int(variant), _mp2._p(ids), ids.size, _mp2._p(v), ctypes.c_uint32(rows), _mp2._p(idx),
+                                                      ctypes.c_uint32(idx.size), None if roots is None else _mp2._p(roots),
+                                                      None if nodes is None else _mp2._p(nodes)))
+    return roots
+
+
+def row_tree_hashes_update(ctx, shape, id, values, payload, touched, hashes, variant=0):
+    """mp2g_row_tree_hashes_update: re-hash the nodes `touched` and their ancestors (shape.touched(touched)) under the current
+    values / payload, arguments as row_tree_hashes takes them. hashes: uint64 [n][4] of the caller's, valid outside that set on
+    entry, written in place inside it and nowhere else. Returns hashes."""
+    n = shape.size
+    v = np.ascontiguousarray(values, dtype=np.uint32).reshape(n, -1) if n else np.zeros((0, 8), dtype=np.uint32)
+    pl = None if payload is None else np.ascontiguousarray(payload, dtype=np.uint64).reshape(n, 4)
+    t = np.ascontiguousarray(touched, dtype=np.uint32).ravel()
+    if hashes is not None and not (isinstance(hashes, np.ndarray) and hashes.dtype == np.uint64 and hashes.flags.c_contiguous and hashes.shape == (n, 4)):
+        raise ValueError(f"hashes: a contiguous uint64 array of shape {(n, 4)} that the call can write in place")
+    if ctx is not None:
+        ctx._adopt(shape)
+    _mp2._ck(_mp2.load().mp2g_row_tree_hashes_update(_h(ctx), int(variant), shape.h, ctypes.c_uint64(int(id)), _mp2._p(v), ctypes.c_uint32(v.shape[1]),
+                                                      None if pl is None else _mp2._p(pl), _mp2._p(t), ctypes.c_uint32(t.size),
+                                                      None if hashes is None else _mp2._p(hashes)))
+    return hashes
+
+
+class TableHashes:
+    """A block of rows whose table, cells roots and row-tree hashes stay on the device between blocks: built by the two full calls
+    (what table_hashes chains), then kept current by update(), which re-hashes the changed rows' cells trees
+    (mp2g_cells_tree_hashes_rows_dev) and the changed nodes' lineages in the row tree (mp2g_row_tree_hashes_update_dev) -- where a
+    Rust host calls MerkleTreeKvDb::aggregate. values: uint32 [rows][n_cols][8]; shape: the row tree, one node per row."""
+
+    def __init__(self, ctx, col_ids, values, shape, variant=0):
+        self.ctx, self.shape, self.variant = ctx, shape, int(variant)
+        self.ids = np.ascontiguousarray(col_ids, dtype=np.uint64).ravel()
+        v = _table_values(values, self.ids.size)
+        self.rows = v.shape[0]
+        if shape.size != self.rows:
+            raise ValueError("the row tree's shape has not one node per row")
+        self.d_values = self.d_cells = self.d_rows = None
+        if self.rows:
+            self.d_values, self.d_cells, self.d_rows = ctx.to_device(v), ctx.alloc(self.rows * 32), ctx.alloc(self.rows * 32)
+            _mp2.cells_tree_hashes_dev(ctx, self.variant, self.ids, self.d_values, self.rows, self.d_cells)
+            _mp2.row_tree_hashes_dev(ctx, self.variant, shape, self.ids[0], self.d_values, self.ids.size * 8, self.d_cells, self.d_rows)
+
+    def update(self, rows, new_values):
+        """rows: the indices of the changed rows (distinct); new_values: uint32 [len(rows)][n_cols][8]. Returns the row-tree nodes
+        that were re-hashed (shape.touched(rows))."""
+        idx = np.ascontiguousarray(rows, dtype=np.uint32).ravel()
+        nv = np.ascontiguousarray(new_values, dtype=np.uint32).reshape(idx.size, self.ids.size, 8)
+        if idx.size and int(idx.max()) >= self.rows:
+            raise ValueError("row index outside the table")
+        touched = self.shape.touched(idx)
+        row_bytes = self.ids.size * 32
+        for j, r in enumerate(idx.tolist()):
+            self.d_values.upload_at(nv[j], r * row_bytes)
+        _mp2.cells_tree_hashes_rows_dev(self.ctx, self.variant, self.ids, self.d_values, self.rows, idx, self.d_cells)
+        _mp2.row_tree_hashes_update_dev(self.ctx, self.variant, self.shape, self.ids[0], self.d_values, self.ids.size * 8, self.d_cells, idx,
+                                        self.d_rows)
+        return touched
+
+    def row_hashes(self):
+        return self.d_rows.download((self.rows, 4)) if self.rows else np.zeros((0, 4), dtype=np.uint64)
+
+    def cells_roots(self):
+        return self.d_cells.download((self.rows, 4)) if self.rows else np.zeros((0, 4), dtype=np.uint64)
+
+    def roots(self):
+        """the row tree's root nodes, ascending"""
+        return self.shape.describe()["roots"]
+
+    def free(self):
+        for d in (self.d_values, self.d_cells, self.d_rows):
+            if d is not None:
+                d.free()
+        self.d_values = self.d_cells = self.d_rows = None
