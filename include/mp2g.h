@@ -230,7 +230,9 @@ int mp2g_map_to_curve_batch(mp2g_ctx* ctx, int variant, const uint64_t* in, uint
  * mp2g_map_to_curve_batch does after its hash. Limbs may be any u64 and are read mod p, as GoldilocksField(x) reads them. */
 int mp2g_swu_batch(mp2g_ctx* ctx, const uint64_t* u /* [count][5] */, uint32_t count, uint64_t* out_w /* [count][5] */,
                    uint64_t* out_weierstrass /* [count][11] or NULL */);
-/* add_curve_point (curve_add.rs:17-22) over `count` encoded points; fails on an invalid encoding */
+/* add_curve_point (curve_add.rs:17-22) over `count` encoded points; fails on an invalid encoding.
+ * Encodings are canonical: this entry, mp2g_curve_sum_ranges and mp2g_scalar_mul_batch refuse a point with a limb >= p ("point
+ * encoding is not canonical"), checked on the host before anything is uploaded; (p,0,0,0,0) is not read as the neutral point. */
 int mp2g_curve_sum(mp2g_ctx* ctx, const uint64_t* pts_w /* [count][5] */, uint32_t count, uint64_t out_w[5],
                    uint64_t out_weierstrass[11]);
 /* the same sum over n_ranges index ranges [start, end) of one point array at once: the accumulated digest of every node of a

@@ -40,8 +40,14 @@ int mp2g_swu_batch(mp2g_ctx* c, const uint64_t* u, uint32_t count, uint64_t* out
   return copy_out(c, dw, dwei, count, out_w, out_wei);
 }
 
-// decode `count` encodings into a fractional-coordinate buffer; errors on invalid encodings
+// decode `count` encodings into a fractional-coordinate buffer; errors on invalid encodings.
+// A limb >= p is refused here, on the host, before the upload: the field routines behind pt_decode take canonical values only
+// (gl5_is_zero compares raw bits, gl_sqrt's loops end on the canonical 1), so such words never reach the kernel.
 static int decode_host(mp2g_ctx* c, const uint64_t* pts_w, uint32_t count, DevBuf& frac) {
+  for (size_t i = 0; i < (size_t)count * 5; i++)
+    if (pts_w[i] >= GL_P)
+      return fail("point encoding is not canonical: limb %u of point %zu is 0x%016llx >= p", (unsigned)(i % 5), i / 5,
+                  (unsigned long long)pts_w[i]);
   DevBuf dw, dbad;
   CK(dw.alloc((size_t)count * 5 * sizeof(u64)));
   CK(dbad.alloc(8));
