@@ -14,6 +14,8 @@ import weakref
 
 import numpy as np
 
+from ._abi import prototypes
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MP2G_LIB", os.path.join(_HERE, "libmp2gpu.so"))
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mp2g.h")
@@ -38,15 +40,15 @@ def load():
         if not os.path.exists(LIB_PATH):
             raise Mp2gError(f"{LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'`; "
                             "there is no CPU fallback for the product path")
-        _lib = ctypes.CDLL(LIB_PATH)
-        _lib.mp2g_last_error.restype = ctypes.c_char_p
-        _lib.mp2g_ctx_stream.restype = ctypes.c_void_p
-        _lib.mp2g_stat_leaf_permutations.restype = ctypes.c_uint64
-        _lib.mp2g_ctx_stream.argtypes = [ctypes.c_void_p]
-        for f in (_lib.mp2g_tree_shape_size, _lib.mp2g_tree_shape_num_levels, _lib.mp2g_tree_shape_num_roots):
-            f.restype, f.argtypes = ctypes.c_uint32, [ctypes.c_void_p]
-        _lib.mp2g_tree_shape_free.restype, _lib.mp2g_tree_shape_free.argtypes = None, [ctypes.c_void_p]
-        _lib.mp2g_row_tree_update_fused_width.restype, _lib.mp2g_row_tree_update_fused_width.argtypes = ctypes.c_uint32, []
+        if not os.path.exists(HEADER_PATH):
+            raise Mp2gError(f"{HEADER_PATH} is missing: the prototype of every library call is read from it")
+        lib = ctypes.CDLL(LIB_PATH)
+        for name, (restype, argtypes) in prototypes(HEADER_PATH).items():
+            if not hasattr(lib, name):
+                raise Mp2gError(f"{LIB_PATH} does not export {name}, which include/mp2g.h declares")
+            f = getattr(lib, name)
+            f.restype, f.argtypes = restype, argtypes
+        _lib = lib
     return _lib
 
 
@@ -64,29 +66,31 @@ def _p(a):
 
 
 class DeviceBuffer:
+    _as_parameter_ = property(lambda self: self.ptr)  # passed to a library call, a buffer is its device address
+
     def __init__(self, ctx, nbytes):
         self.ctx, self.nbytes = ctx, nbytes
         ptr = ctypes.c_void_p()
-        _ck(load().mp2g_dev_alloc(ctx.h, ctypes.c_size_t(nbytes), ctypes.byref(ptr)))
+        _ck(load().mp2g_dev_alloc(ctx.h, nbytes, ctypes.byref(ptr)))
         self.ptr = ptr
         ctx._adopt(self)
 
     def upload(self, a):
         a = np.ascontiguousarray(a)
         assert a.nbytes <= self.nbytes
-        _ck(load().mp2g_h2d(self.ctx.h, self.ptr, _p(a), ctypes.c_size_t(a.nbytes)))
+        _ck(load().mp2g_h2d(self.ctx.h, self, _p(a), a.nbytes))
         return self
 
     def upload_at(self, a, offset):
         a = np.ascontiguousarray(a)
         assert offset + a.nbytes <= self.nbytes
-        _ck(load().mp2g_h2d(self.ctx.h, ctypes.c_void_p(self.ptr.value + offset), _p(a), ctypes.c_size_t(a.nbytes)))
+        _ck(load().mp2g_h2d(self.ctx.h, self.ptr.value + offset, _p(a), a.nbytes))
         return self
 
     def download(self, shape, dtype=np.uint64):
         out = np.empty(shape, dtype=dtype)
         assert out.nbytes <= self.nbytes
-        _ck(load().mp2g_d2h(self.ctx.h, _p(out), self.ptr, ctypes.c_size_t(out.nbytes)))
+        _ck(load().mp2g_d2h(self.ctx.h, _p(out), self, out.nbytes))
         return out
 
     def free(self):
@@ -103,6 +107,7 @@ class DeviceBuffer:
 
 class Context:
     """One per GPU (mp2g_ctx)."""
+    _as_parameter_ = property(lambda self: self.h)  # a library call takes a Context, or None where it needs no device
 
     def __init__(self, device=0):
         self.h = ctypes.c_void_p()
@@ -154,7 +159,7 @@ class Context:
     def host_alloc(self, nbytes):
         """Pinned host buffer as a numpy uint8 view (freed with host_free)."""
         ptr = ctypes.c_void_p()
-        _ck(load().mp2g_host_alloc(self.h, ctypes.c_size_t(nbytes), ctypes.byref(ptr)))
+        _ck(load().mp2g_host_alloc(self.h, nbytes, ctypes.byref(ptr)))
         buf = (ctypes.c_uint8 * nbytes).from_address(ptr.value)
         return np.frombuffer(buf, dtype=np.uint8), ptr
 
@@ -162,23 +167,21 @@ class Context:
         _ck(load().mp2g_host_free(self.h, ptr))
 
     def h2d_async(self, d_dst, host_ptr, nbytes, dst_offset=0):
-        _ck(load().mp2g_h2d_async(self.h, ctypes.c_void_p(d_dst.ptr.value + dst_offset), host_ptr, ctypes.c_size_t(nbytes)))
+        _ck(load().mp2g_h2d_async(self.h, d_dst.ptr.value + dst_offset, host_ptr, nbytes))
 
     def d2d_2d(self, d_dst, dst_offset, dst_pitch, d_src, src_offset, src_pitch, width, rows):
         """stream-ordered strided device copy (all sizes in bytes): `rows` pieces of `width` bytes"""
-        _ck(load().mp2g_d2d_2d(self.h, ctypes.c_void_p(d_dst.ptr.value + dst_offset), ctypes.c_size_t(dst_pitch),
-                               ctypes.c_void_p(d_src.ptr.value + src_offset), ctypes.c_size_t(src_pitch), ctypes.c_size_t(width), ctypes.c_size_t(rows)))
+        _ck(load().mp2g_d2d_2d(self.h, d_dst.ptr.value + dst_offset, dst_pitch, d_src.ptr.value + src_offset, src_pitch, width, rows))
 
     def d2h_raw(self, src_ptr, shape, dtype=np.uint64):
         """download from a raw device address"""
         out = np.empty(shape, dtype=dtype)
-        _ck(load().mp2g_d2h(self.h, _p(out), ctypes.c_void_p(int(src_ptr)), ctypes.c_size_t(out.nbytes)))
+        _ck(load().mp2g_d2h(self.h, _p(out), int(src_ptr), out.nbytes))
         return out
 
     def d2d_raw(self, d_dst, dst_offset, src_ptr, nbytes):
         """stream-ordered device copy of nbytes from a raw device address into a DeviceBuffer"""
-        _ck(load().mp2g_d2d_2d(self.h, ctypes.c_void_p(d_dst.ptr.value + dst_offset), ctypes.c_size_t(nbytes), ctypes.c_void_p(int(src_ptr)),
-                               ctypes.c_size_t(nbytes), ctypes.c_size_t(nbytes), ctypes.c_size_t(1)))
+        _ck(load().mp2g_d2d_2d(self.h, d_dst.ptr.value + dst_offset, nbytes, int(src_ptr), nbytes, nbytes, 1))
 
     def wires_from_rows_dev(self, d_rows, d_wires, log_n, batch, num_wires=135):
         """[batch][n][num_wires] (the witness executor's row layout) -> [batch][num_wires][n] (the prover's), on the device"""
@@ -198,11 +201,11 @@ class Context:
         batch, n = (1, a.shape[0]) if a.ndim == 1 else a.shape
         log_n = int(n).bit_length() - 1
         assert 1 << log_n == n
-        _ck(load().mp2g_ntt(self.h, _p(a), log_n, batch, int(inverse), ctypes.c_uint64(coset_shift), int(bitrev_out)))
+        _ck(load().mp2g_ntt(self.h, _p(a), log_n, batch, int(inverse), coset_shift, int(bitrev_out)))
         return a
 
     def ntt_dev(self, d_in, d_out, log_n, batch, inverse=False, coset_shift=0, bitrev_out=False):
-        _ck(load().mp2g_ntt_dev(self.h, d_in.ptr, d_out.ptr, log_n, batch, int(inverse), ctypes.c_uint64(coset_shift), int(bitrev_out)))
+        _ck(load().mp2g_ntt_dev(self.h, d_in.ptr, d_out.ptr, log_n, batch, int(inverse), coset_shift, int(bitrev_out)))
 
     def lde_leaves(self, coeffs, rate_bits):
         c = _arr(coeffs)
@@ -351,15 +354,11 @@ class FriParams(ctypes.Structure):
 
     @property
     def proof_words(self):
-        f = load().mp2g_fri_proof_words
-        f.restype = ctypes.c_size_t
-        return f(ctypes.byref(self))
+        return load().mp2g_fri_proof_words(ctypes.byref(self))
 
     @property
     def n_openings(self):
-        f = load().mp2g_fri_n_openings
-        f.restype = ctypes.c_size_t
-        return f(ctypes.byref(self))
+        return load().mp2g_fri_n_openings(ctypes.byref(self))
 
     @property
     def cap_words(self):
@@ -415,7 +414,7 @@ def fri_fold(ctx, evals, arity_bits, beta, shift):
     log_m = int(m).bit_length() - 1
     out = np.empty((m >> arity_bits, 2), dtype=np.uint64)
     b = _arr(beta)
-    _ck(load().mp2g_fri_fold(ctx.h, _p(a), log_m, arity_bits, _p(b), ctypes.c_uint64(shift), _p(out)))
+    _ck(load().mp2g_fri_fold(ctx.h, _p(a), log_m, arity_bits, _p(b), shift, _p(out)))
     return out
 
 
@@ -487,7 +486,7 @@ def eval_gate_constraints(ctx, gates, num_selectors, consts, wires, pi_hash):
     max_j = max(arr[i].num_constraints for i in range(len(gates)))
     out = np.zeros((max_j, w.shape[1]), dtype=np.uint64)
     _ck(load().mp2g_eval_gate_constraints(ctx.h, arr, len(gates), num_selectors, _p(c), c.shape[0], _p(w), w.shape[0],
-                                          ctypes.c_uint64(w.shape[1]), _p(ph), _p(out)))
+                                          w.shape[1], _p(ph), _p(out)))
     return out
 
 
@@ -525,7 +524,7 @@ class BatchedProver:
         """prove()'s set_lookup_wires on the device, in place on d_wires [batch][wires_w][n] (needs set_lookups): n_lookups[t] =
         the looked-up slots of table t; the padding, the table rows and the multiplicities are written"""
         nl = np.ascontiguousarray(n_lookups, dtype=np.uint32)
-        _ck(load().mp2g_prover_lookup_wires_dev(self.h, nl.ctypes.data_as(ctypes.c_void_p), d_wires.ptr, int(batch)))
+        _ck(load().mp2g_prover_lookup_wires_dev(self.h, _p(nl), d_wires.ptr, int(batch)))
 
     def set_lookups(self, luts):
         """Lookup tables of the circuit (CommonCircuitData::luts + ProverOnlyCircuitData::lookup_rows): prove() then
@@ -537,7 +536,7 @@ class BatchedProver:
     def bind_public_inputs(self, row):
         """PublicInputGate's generator on the device: wires 0..3 of `row` of every proof's wire matrix are
         overwritten (in place) with that proof's public-inputs hash before the commitment."""
-        _ck(load().mp2g_prover_bind_public_inputs(self.h, ctypes.c_int64(-1 if row is None else int(row))))
+        _ck(load().mp2g_prover_bind_public_inputs(self.h, -1 if row is None else int(row)))
 
     def enable_witness_check(self, on=True):
         """Check gate and copy constraints of every witness on the device (plonky2 panics on a bad one)."""
@@ -621,13 +620,11 @@ class Verifier:
         larr, keep = lookup_array(luts or [])
         self.h = ctypes.c_void_p()
         _ck(load().mp2g_verifier_create(ctx.h, ctypes.byref(fp), _p(cap), _p(dig), int(num_routed), int(degree), arr, len(gates),
-                                        int(num_selectors), larr if luts else None, len(luts or []), ctypes.c_uint32(n_public_inputs),
+                                        int(num_selectors), larr if luts else None, len(luts or []), n_public_inputs,
                                         self.capacity, ctypes.byref(self.h)))
         ctx._adopt(self)
         parts = (ctypes.c_uint32 * 4)()
-        f = load().mp2g_verifier_proof_words
-        f.restype = ctypes.c_size_t
-        self.proof_words = int(f(self.h, parts))
+        self.proof_words = load().mp2g_verifier_proof_words(self.h, parts)
         self.part_words = [int(x) for x in parts]
 
     def verify_dev(self, d_parts, strides, count):
@@ -676,7 +673,7 @@ class WitnessProgram:
         self.probe = _arr(np.concatenate([ckt.pi_hash_sids, ckt.public_input_sids]), np.uint32)
         self.n_public_inputs = int(ckt.public_input_sids.size)
         self.h = ctypes.c_void_p()
-        _ck(load().mp2g_witness_program_create(_p(tape), ctypes.c_size_t(tape.size), int(ckt.n_slots), int(ckt.log_n), _p(ins), int(ins.size),
+        _ck(load().mp2g_witness_program_create(_p(tape), tape.size, int(ckt.n_slots), int(ckt.log_n), _p(ins), int(ins.size),
                                                _p(cs), int(cs.shape[0]), ctypes.byref(self.h)))
         if getattr(ckt, "luts", None):
             self.set_lookups(ckt.luts)
@@ -832,15 +829,15 @@ class Forest:
 
     def proof_words(self, node_id):
         n = ctypes.c_uint32()
-        _ck(load().mp2g_forest_proof(self.h, ctypes.c_uint64(int(node_id)), None, ctypes.byref(n)))
+        _ck(load().mp2g_forest_proof(self.h, int(node_id), None, ctypes.byref(n)))
         out = np.empty(n.value, dtype=np.uint64)
-        _ck(load().mp2g_forest_proof(self.h, ctypes.c_uint64(int(node_id)), _p(out), ctypes.byref(n)))
+        _ck(load().mp2g_forest_proof(self.h, int(node_id), _p(out), ctypes.byref(n)))
         return out
 
     def device_proof(self, node_id):
         """(device address, words) of a proved node's proof in the pool: public inputs, caps of oracles 1..3, openings, FRI words"""
         ptr, n = ctypes.c_void_p(), ctypes.c_uint32()
-        _ck(load().mp2g_forest_device_proof(self.h, ctypes.c_uint64(int(node_id)), ctypes.byref(ptr), ctypes.byref(n)))
+        _ck(load().mp2g_forest_device_proof(self.h, int(node_id), ctypes.byref(ptr), ctypes.byref(n)))
         return int(ptr.value), int(n.value)
 
     def verify(self, ids, verifier):
@@ -852,12 +849,11 @@ class Forest:
         return status
 
     def release(self, node_id):
-        _ck(load().mp2g_forest_release(self.h, ctypes.c_uint64(int(node_id))))
+        _ck(load().mp2g_forest_release(self.h, int(node_id)))
 
     @property
     def proved(self):
-        load().mp2g_forest_proved.restype = ctypes.c_uint64
-        return int(load().mp2g_forest_proved(self.h))
+        return load().mp2g_forest_proved(self.h)
 
     def free(self):
         if self.h and all(c.h for c in self.ctxs):
@@ -993,7 +989,7 @@ class TreeShape:
     def sbbst(cls, n):
         """ryhope's sbbst over positions 1..n (position k = node k - 1)"""
         h = ctypes.c_void_p()
-        _ck(load().mp2g_tree_shape_sbbst(ctypes.c_uint32(int(n)), ctypes.byref(h)))
+        _ck(load().mp2g_tree_shape_sbbst(int(n), ctypes.byref(h)))
         return cls(h)
 
     def describe(self):
@@ -1010,9 +1006,9 @@ class TreeShape:
         grouped by height (ascending height, ascending node index inside a height); duplicates collapse. Needs no GPU."""
         t = _arr(nodes, np.uint32).ravel()
         n = ctypes.c_uint32()
-        _ck(load().mp2g_tree_shape_touched(self.h, _p(t), ctypes.c_uint32(t.size), None, ctypes.c_uint32(0), ctypes.byref(n)))
+        _ck(load().mp2g_tree_shape_touched(self.h, _p(t), t.size, None, 0, ctypes.byref(n)))
         out = np.empty(n.value, dtype=np.uint32)
-        _ck(load().mp2g_tree_shape_touched(self.h, _p(t), ctypes.c_uint32(t.size), _p(out), n, ctypes.byref(n)))
+        _ck(load().mp2g_tree_shape_touched(self.h, _p(t), t.size, _p(out), n.value, ctypes.byref(n)))
         return out
 
     def free(self):
@@ -1027,16 +1023,10 @@ class TreeShape:
             pass
 
 
-def _raw(x):
-    """a DeviceBuffer, a raw device address or None as the void* of a call"""
-    return x.ptr if isinstance(x, DeviceBuffer) else (None if x is None else ctypes.c_void_p(int(x)))
-
-
 def cells_tree_hashes_dev(ctx, variant, col_ids, d_values, rows, d_roots, d_nodes=None):
     """mp2g_cells_tree_hashes_dev: stream ordered, no synchronisation; col_ids is a host array"""
     ids = _arr(col_ids).ravel()
-    _ck(load().mp2g_cells_tree_hashes_dev(ctx.h if ctx is not None else None, int(variant), _p(ids), ids.size, _raw(d_values), ctypes.c_uint32(rows),
-                                          _raw(d_roots), _raw(d_nodes)))
+    _ck(load().mp2g_cells_tree_hashes_dev(ctx, int(variant), _p(ids), ids.size, d_values, rows, d_roots, d_nodes))
 
 
 def row_tree_hashes_dev(ctx, variant, shape, ident, d_values, value_stride, d_payload, d_hashes):
@@ -1044,8 +1034,7 @@ def row_tree_hashes_dev(ctx, variant, shape, ident, d_values, value_stride, d_pa
     frees it (a shape is freed before the context it was used with)."""
     if ctx is not None:
         ctx._adopt(shape)
-    _ck(load().mp2g_row_tree_hashes_dev(ctx.h if ctx is not None else None, int(variant), shape.h, ctypes.c_uint64(int(ident)), _raw(d_values),
-                                        ctypes.c_uint32(int(value_stride)), _raw(d_payload), _raw(d_hashes)))
+    _ck(load().mp2g_row_tree_hashes_dev(ctx, int(variant), shape.h, int(ident), d_values, int(value_stride), d_payload, d_hashes))
 
 
 def row_tree_update_fused_width():
@@ -1056,8 +1045,7 @@ def row_tree_update_fused_width():
 def cells_tree_hashes_rows_dev(ctx, variant, col_ids, d_values, rows, row_idx, d_roots, d_nodes=None):
     """mp2g_cells_tree_hashes_rows_dev: the cells trees of the listed rows only; stream ordered; col_ids and row_idx are host arrays"""
     ids, idx = _arr(col_ids).ravel(), _arr(row_idx, np.uint32).ravel()
-    _ck(load().mp2g_cells_tree_hashes_rows_dev(ctx.h if ctx is not None else None, int(variant), _p(ids), ids.size, _raw(d_values),
-                                               ctypes.c_uint32(rows), _p(idx), ctypes.c_uint32(idx.size), _raw(d_roots), _raw(d_nodes)))
+    _ck(load().mp2g_cells_tree_hashes_rows_dev(ctx, int(variant), _p(ids), ids.size, d_values, rows, _p(idx), idx.size, d_roots, d_nodes))
 
 
 def row_tree_hashes_update_dev(ctx, variant, shape, ident, d_values, value_stride, d_payload, touched, d_hashes):
@@ -1066,9 +1054,8 @@ def row_tree_hashes_update_dev(ctx, variant, shape, ident, d_values, value_strid
     if ctx is not None:
         ctx._adopt(shape)
     t = _arr(touched, np.uint32).ravel()
-    _ck(load().mp2g_row_tree_hashes_update_dev(ctx.h if ctx is not None else None, int(variant), shape.h, ctypes.c_uint64(int(ident)),
-                                               _raw(d_values), ctypes.c_uint32(int(value_stride)), _raw(d_payload), _p(t),
-                                               ctypes.c_uint32(t.size), _raw(d_hashes)))
+    _ck(load().mp2g_row_tree_hashes_update_dev(ctx, int(variant), shape.h, int(ident), d_values, int(value_stride), d_payload,
+                                               _p(t), t.size, d_hashes))
 
 
 def leaf_permutations_queued():
@@ -1094,7 +1081,7 @@ def deserialize_proof(fp, num_constants, data, n_public_inputs):
     openings = np.zeros((fp.n_openings, 2), dtype=np.uint64)
     fri = np.zeros(fp.proof_words, dtype=np.uint64)
     pis = np.zeros(n_public_inputs, dtype=np.uint64)
-    _ck(load().mp2g_proof_deserialize(ctypes.byref(fp), num_constants, _p(buf), ctypes.c_size_t(buf.size), _p(caps), _p(openings),
+    _ck(load().mp2g_proof_deserialize(ctypes.byref(fp), num_constants, _p(buf), buf.size, _p(caps), _p(openings),
                                       _p(fri), _p(pis), n_public_inputs))
     return caps, openings, fri, pis
 
@@ -1104,9 +1091,9 @@ def serialize_proof_with_vk(proof_bytes, vk_cap, vk_circuit_digest):
     pb = np.frombuffer(proof_bytes, dtype=np.uint8).copy()
     cap, dig = _arr(vk_cap).reshape(-1, 4), _arr(vk_circuit_digest)
     n = ctypes.c_size_t()
-    _ck(load().mp2g_proof_with_vk_serialize(_p(pb), ctypes.c_size_t(pb.size), _p(cap), cap.shape[0], _p(dig), None, ctypes.byref(n)))
+    _ck(load().mp2g_proof_with_vk_serialize(_p(pb), pb.size, _p(cap), cap.shape[0], _p(dig), None, ctypes.byref(n)))
     out = np.empty(n.value, dtype=np.uint8)
-    _ck(load().mp2g_proof_with_vk_serialize(_p(pb), ctypes.c_size_t(pb.size), _p(cap), cap.shape[0], _p(dig), _p(out), ctypes.byref(n)))
+    _ck(load().mp2g_proof_with_vk_serialize(_p(pb), pb.size, _p(cap), cap.shape[0], _p(dig), _p(out), ctypes.byref(n)))
     return out.tobytes()
 
 
@@ -1121,7 +1108,7 @@ def deserialize_proof_with_vk(fp, num_constants, data, n_public_inputs, vk_cap_l
     pis = np.zeros(n_public_inputs, dtype=np.uint64)
     vk_cap = np.zeros((n_cap, 4), dtype=np.uint64)
     dig = np.zeros(4, dtype=np.uint64)
-    _ck(load().mp2g_proof_with_vk_deserialize(ctypes.byref(fp), num_constants, _p(buf), ctypes.c_size_t(buf.size), _p(caps), _p(openings),
+    _ck(load().mp2g_proof_with_vk_deserialize(ctypes.byref(fp), num_constants, _p(buf), buf.size, _p(caps), _p(openings),
                                               _p(fri), _p(pis), n_public_inputs, _p(vk_cap), n_cap, _p(dig)))
     if vk_cap.size == caps[0].size:
         caps[0] = vk_cap.ravel()

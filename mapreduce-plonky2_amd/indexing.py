@@ -81,13 +81,7 @@ def index_node_min_max(value, left=None, right=None):
 
 
 # ---- whole trees on the device (csrc/index_hash.hip): one call per tree kind, one launch per level, no host round trip --------------
-import ctypes  # noqa: E402
-
 TreeShape = _mp2.TreeShape  # from_children(left, right), sbbst(n), describe()
-
-
-def _h(ctx):
-    return ctx.h if ctx is not None else None
 
 
 def _table_values(values, n_cols):
@@ -106,7 +100,7 @@ def cells_tree_hashes(ctx, col_ids, values, variant=0, nodes=False):
     rows = v.shape[0]
     roots = np.zeros((rows, 4), dtype=np.uint64)
     all_nodes = np.zeros((rows, max(ids.size, 1) - 1, 4), dtype=np.uint64) if nodes else None
-    _mp2._ck(_mp2.load().mp2g_cells_tree_hashes(_h(ctx), int(variant), _mp2._p(ids), ids.size, _mp2._p(v), ctypes.c_uint32(rows), _mp2._p(roots),
+    _mp2._ck(_mp2.load().mp2g_cells_tree_hashes(ctx, int(variant), _mp2._p(ids), ids.size, _mp2._p(v), rows, _mp2._p(roots),
                                                  _mp2._p(all_nodes) if nodes else None))
     return (roots, all_nodes) if nodes else roots
 
@@ -122,7 +116,7 @@ def row_tree_hashes(ctx, shape, id, values, payload=None, variant=0):
     out = np.zeros((n, 4), dtype=np.uint64)
     if ctx is not None:
         ctx._adopt(shape)  # a shape is freed before the context it was used with: closing the context frees it
-    _mp2._ck(_mp2.load().mp2g_row_tree_hashes(_h(ctx), int(variant), shape.h, ctypes.c_uint64(int(id)), _mp2._p(v), ctypes.c_uint32(v.shape[1]),
+    _mp2._ck(_mp2.load().mp2g_row_tree_hashes(ctx, int(variant), shape.h, int(id), _mp2._p(v), v.shape[1],
                                                None if pl is None else _mp2._p(pl), _mp2._p(out)))
     return out
 
@@ -161,8 +155,8 @@ def cells_tree_hashes_rows(ctx, col_ids, values, row_idx, roots, nodes=None, var
     for a, shape in ((roots, (rows, 4)), (nodes, (rows, max(ids.size, 1) - 1, 4))):
         if a is not None and not (isinstance(a, np.ndarray) and a.dtype == np.uint64 and a.flags.c_contiguous and a.shape == shape):
             raise ValueError(f"roots / nodes: a contiguous uint64 array of shape {shape} that the call can write in place")
-    _mp2._ck(_mp2.load().mp2g_cells_tree_hashes_rows(_h(ctx), int(variant), _mp2._p(ids), ids.size, _mp2._p(v), ctypes.c_uint32(rows), _mp2._p(idx),
-                                                      ctypes.c_uint32(idx.size), None if roots is None else _mp2._p(roots),
+    _mp2._ck(_mp2.load().mp2g_cells_tree_hashes_rows(ctx, int(variant), _mp2._p(ids), ids.size, _mp2._p(v), rows, _mp2._p(idx),
+                                                      idx.size, None if roots is None else _mp2._p(roots),
                                                       None if nodes is None else _mp2._p(nodes)))
     return roots
 
@@ -179,8 +173,8 @@ def row_tree_hashes_update(ctx, shape, id, values, payload, touched, hashes, var
         raise ValueError(f"hashes: a contiguous uint64 array of shape {(n, 4)} that the call can write in place")
     if ctx is not None:
         ctx._adopt(shape)
-    _mp2._ck(_mp2.load().mp2g_row_tree_hashes_update(_h(ctx), int(variant), shape.h, ctypes.c_uint64(int(id)), _mp2._p(v), ctypes.c_uint32(v.shape[1]),
-                                                      None if pl is None else _mp2._p(pl), _mp2._p(t), ctypes.c_uint32(t.size),
+    _mp2._ck(_mp2.load().mp2g_row_tree_hashes_update(ctx, int(variant), shape.h, int(id), _mp2._p(v), v.shape[1],
+                                                      None if pl is None else _mp2._p(pl), _mp2._p(t), t.size,
                                                       None if hashes is None else _mp2._p(hashes)))
     return hashes
 

@@ -2521,14 +2521,7 @@ class DeviceProof:
 
     def to_host(self, ctx):
         """(caps [4][cap words], openings [n][2], fri words, public inputs): the host form of the same proof"""
-        import ctypes
-        from . import _ck, load
-        out = []
-        for ptr, n in self.parts:
-            a = np.empty(n, dtype=np.uint64)
-            _ck(load().mp2g_d2h(ctx.h, a.ctypes.data_as(ctypes.c_void_p), ctypes.c_void_p(ptr), ctypes.c_size_t(n * 8)))
-            out.append(a)
-        pis, caps3, openings, fri = out
+        pis, caps3, openings, fri = (ctx.d2h_raw(ptr, (n,)) for ptr, n in self.parts)
         caps = np.concatenate([np.zeros(caps3.size // 3, dtype=np.uint64), caps3]).reshape(4, -1)  # oracle 0's cap is verifier data, not proof
         return caps, openings.reshape(-1, 2), fri, pis
 

@@ -17,20 +17,9 @@ import ctypes
 
 import numpy as np
 
-from . import Mp2gError, _ck, load
+from . import Mp2gError, _ck, _p, load
 
 PLAN_FINISHED, PLAN_READY, PLAN_NOT_YET = 0, 1, 2
-
-
-def _lib():
-    lib = load()
-    if not getattr(lib, "_workplan_typed", False):
-        lib.mp2g_update_tree_size.restype = ctypes.c_uint32
-        lib.mp2g_update_tree_epoch.restype = ctypes.c_int64
-        lib.mp2g_update_tree_free.argtypes = [ctypes.c_void_p]
-        lib.mp2g_update_plan_free.argtypes = [ctypes.c_void_p]
-        lib._workplan_typed = True
-    return lib
 
 
 class UpdateTree:
@@ -45,8 +34,7 @@ class UpdateTree:
         keys = np.ascontiguousarray([k for p in paths for k in p], dtype=np.uint64)
         lens = np.ascontiguousarray([len(p) for p in paths], dtype=np.uint32)
         h = ctypes.c_void_p()
-        _ck(_lib().mp2g_update_tree_from_paths(keys.ctypes.data_as(ctypes.c_void_p), lens.ctypes.data_as(ctypes.c_void_p),
-                                               len(paths), ctypes.c_int64(epoch), ctypes.byref(h)))
+        _ck(load().mp2g_update_tree_from_paths(_p(keys), _p(lens), len(paths), epoch, ctypes.byref(h)))
         return cls(h)
 
     @classmethod
@@ -59,9 +47,7 @@ class UpdateTree:
         hl = np.ascontiguousarray([l is not None for l, _ in lr], dtype=np.uint8)
         hr = np.ascontiguousarray([r is not None for _, r in lr], dtype=np.uint8)
         h = ctypes.c_void_p()
-        vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
-        _ck(_lib().mp2g_update_tree_from_map(vp(keys), vp(left), vp(right), vp(hl), vp(hr), len(keys), ctypes.c_uint64(root),
-                                             ctypes.c_int64(epoch), ctypes.byref(h)))
+        _ck(load().mp2g_update_tree_from_map(_p(keys), _p(left), _p(right), _p(hl), _p(hr), len(keys), root, epoch, ctypes.byref(h)))
         return cls(h)
 
     @classmethod
@@ -77,23 +63,22 @@ class UpdateTree:
 
     def extend_with_path(self, path):
         p = np.ascontiguousarray(list(path), dtype=np.uint64)
-        _ck(_lib().mp2g_update_tree_extend_with_path(self._live(), p.ctypes.data_as(ctypes.c_void_p), len(p)))
+        _ck(load().mp2g_update_tree_extend_with_path(self._live(), _p(p), len(p)))
 
     def __len__(self):
-        return int(_lib().mp2g_update_tree_size(self._live()))
+        return int(load().mp2g_update_tree_size(self._live()))
 
     @property
     def epoch(self):
-        return int(_lib().mp2g_update_tree_epoch(self._live()))
+        return int(load().mp2g_update_tree_epoch(self._live()))
 
     def contains_key(self, k):
-        return bool(_lib().mp2g_update_tree_contains_key(self._live(), ctypes.c_uint64(k)))
+        return bool(load().mp2g_update_tree_contains_key(self._live(), k))
 
     def _dump(self):
         n = len(self)
         keys, parents, ends = np.empty(n, np.uint64), np.empty(n, np.int32), np.empty(n, np.uint8)
-        _ck(_lib().mp2g_update_tree_nodes(self._live(), keys.ctypes.data_as(ctypes.c_void_p),
-                                          parents.ctypes.data_as(ctypes.c_void_p), ends.ctypes.data_as(ctypes.c_void_p)))
+        _ck(load().mp2g_update_tree_nodes(self._live(), _p(keys), _p(parents), _p(ends)))
         return keys, parents, ends
 
     def nodes(self):
@@ -114,7 +99,7 @@ class UpdateTree:
 
     def subtree_size(self, k):
         out = ctypes.c_uint32()
-        _ck(_lib().mp2g_update_tree_subtree_size(self._live(), ctypes.c_uint64(k), ctypes.byref(out)))
+        _ck(load().mp2g_update_tree_subtree_size(self._live(), k, ctypes.byref(out)))
         return out.value
 
     def bottom_up(self):
@@ -133,7 +118,7 @@ class UpdateTree:
 
     def free(self):
         if self.h is not None:
-            _lib().mp2g_update_tree_free(self.h)
+            load().mp2g_update_tree_free(self.h)
             self.h = None
 
     def __del__(self):
@@ -174,7 +159,7 @@ class UpdatePlan:
 
     def __init__(self, tree, subtree_size):
         h = ctypes.c_void_p()
-        _ck(_lib().mp2g_update_plan_create(tree._live(), subtree_size, ctypes.byref(h)))
+        _ck(load().mp2g_update_plan_create(tree._live(), subtree_size, ctypes.byref(h)))
         self.h, self.batch_size = h, subtree_size
         self._tree = UpdateTree(tree.h)  # view for tree(); owned by the plan
         tree.h = None
@@ -185,7 +170,7 @@ class UpdatePlan:
     def next(self):
         """None when every node is done, else Next (ready or not-yet)."""
         k, end, sub = ctypes.c_uint64(), ctypes.c_int(), ctypes.c_void_p()
-        st = _lib().mp2g_update_plan_next(self.h, ctypes.byref(k), ctypes.byref(end), ctypes.byref(sub))
+        st = load().mp2g_update_plan_next(self.h, ctypes.byref(k), ctypes.byref(end), ctypes.byref(sub))
         if st < 0:
             raise Mp2gError(load().mp2g_last_error().decode())
         if st == PLAN_FINISHED:
@@ -204,15 +189,15 @@ class UpdatePlan:
         return n
 
     def done(self, k):
-        _ck(_lib().mp2g_update_plan_done(self.h, ctypes.c_uint64(k)))
+        _ck(load().mp2g_update_plan_done(self.h, k))
 
     def completed(self):
-        return bool(_lib().mp2g_update_plan_completed(self.h))
+        return bool(load().mp2g_update_plan_completed(self.h))
 
     def free(self):
         if self.h is not None:
             self._tree.h = None
-            _lib().mp2g_update_plan_free(self.h)
+            load().mp2g_update_plan_free(self.h)
             self.h = None
 
     def __del__(self):
