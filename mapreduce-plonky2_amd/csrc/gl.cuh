@@ -215,6 +215,52 @@ GLHD u64 gl_mul_addw(u64 a, u64 b, u64 c) {
   return gl_reduce128w(lo, hi);
 }
 GLHD u64 gl_mul_add(u64 a, u64 b, u64 c) { return gl_canon(gl_mul_addw(a, b, c)); }  // canonical a b + c, any u64 inputs
+// a * d + c as some u64 representative for a CONSTANT d whose fold e = d 2^32 mod p is known when the library is built: with
+// a = a0 + 2^32 a1 the integer X = a0 d + a1 e + c is congruent to a d + c and has 97 bits at most, not 128, so the tail is
+// gl_reduce96w (one multiply-add, one select, one carry-less add) where gl_mul_addw pays gl_reduce128w with its subtract chain: 16.2
+// (narrow) and 18.7 (any pair) against 23.7 issue slots (tools/ubench, profiles/p2_diag). a, c: any u64; d, e: canonical and
+// wave-uniform (they are read from SGPRs), e = d 2^32 (mod p). Write d = d0 + 2^32 d1, e = e0 + 2^32 e1, c = c0 + 2^32 c1, M = 2^32 - 1:
+//   p0 = a0 d0 + c0               <= M^2 + M         = 2^64 - 2^32
+//   p1 = a0 d1 + (p0 >> 32) + c1  <= M d1 + 2 M      <= 2^64 - 1                a0 d + c = lo32(p0) + 2^32 p1
+//   q0 = a1 e0 + lo32(p0)         <= M^2 + M         = 2^64 - 2^32
+//   q1 = a1 e1 + p1 + (q0 >> 32)  <= M (d1 + e1) + 3 M                          X = lo32(q0) + 2^32 q1
+// The halves of c ride in the addend slots as in gl_mul_add_wide, p1 as a whole in q1's: the 64-bit addend p1 + (q0 >> 32) cannot wrap
+// (d1 <= M - 1 bounds it by M^2 + 2 M = 2^64 - 1; a canonical d with d1 = M has d0 = 0, hence p0 >> 32 = 0 and the same bound). Only q1
+// can exceed 64 bits, and how far is a property of the pair:
+//   NARROW, d1 + e1 <= 2^32 - 3 (GL_MULC_NARROW): q1 <= M (M - 2) + 3 M = 2^64 - 2^32. Nothing wraps and no carry is taken.
+//   any canonical pair: q1 <= 2 M^2 + 3 M = 2^65 - 2^32 - 1. The multiply-add hands its carry k over in an SGPR pair; k has weight 2^96 in
+//     X, and since 2^32 p k = 0 (mod p), X = lo32(q0) + 2^32 (q1 - k p): the 64-bit register, which holds q1 - k 2^64, takes + k EPS
+//     (2^64 - p = EPS). With k = 1 it holds at most 2^64 - 2^32 - 1, so the carry-less add of the mask cannot wrap, for every input. The
+//     correction is an addition: folding 2^96 = -1 into the result instead would wrap at X = 2^96, which operands do reach.
+// Either way X = lo32(q0) + 2^32 lo32(q1) + 2^64 (q1 >> 32) (mod p) with a top word below 2^32, which is what gl_reduce96w takes for any
+// lo. Hazards as in gl_reduce128w: the carry pair is read by one v_cndmask two wait states after the multiply-add that wrote it.
+#define GL_MULC_NARROW(d, e) (((d) >> 32) + ((e) >> 32) <= 0xFFFFFFFDULL)
+// The four multiply-adds are spelled out and kept in program order (asm volatile; the three that cannot carry name VCC as the carry
+// they do not use): left to the compiler the last one loses its addend to a separate 64-bit add and the products of neighbouring
+// limbs interleave, which costs 10-20 VGPRs in the sponge kernels (an occupancy step) and 2 % of the permutation.
+template <bool NARROW>
+GLHD u64 gl_mulc_addw(u64 a, u64 d, u64 e, u64 c) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  const u32 a0 = (u32)a, a1 = (u32)(a >> 32);
+  u64 p0, p1, q0, q1, k;
+#define GL_MAD_(r, x, y, z) asm volatile("v_mad_u64_u32 %0, vcc, %1, %2, %3" : "=&v"(r) : "v"(x), "s"((u32)(y)), "v"((u64)(z)) : "vcc")
+  GL_MAD_(p0, a0, d, (u64)(u32)c);
+  GL_MAD_(p1, a0, d >> 32, (p0 >> 32) + (c >> 32));
+  GL_MAD_(q0, a1, e, p0 & GL_EPS);
+#undef GL_MAD_
+  asm volatile("v_mad_u64_u32 %0, %1, %2, %3, %4" : "=&v"(q1), "=s"(k) : "v"(a1), "s"((u32)(e >> 32)), "v"(p1 + (q0 >> 32)));
+  if (!NARROW) {
+    u32 m;
+    asm("s_nop 1\n\t"  // 2 wait states between the mad's SGPR carry and its first VALU reader
+        "v_cndmask_b32 %0, 0, -1, %1" : "=v"(m) : "s"(k));
+    q1 += (u64)m;
+  }
+  return gl_reduce96w(gl_mk((u32)q0, (u32)q1), q1 >> 32);
+#else
+  (void)e;  // the host path is not the target
+  return gl_mul_addw(a, d, c);
+#endif
+}
 GLHD u64 gl_mulw(u64 a, u64 b) {
   u64 lo, hi;
   gl_mul_wide(a, b, lo, hi);

@@ -11,12 +11,41 @@
 #include "gl.cuh"
 #include "perm_constants.h"
 
+// What gl_mulc_addw needs beside the diagonal is no table of literals: the compiler derives it here from POSEIDON2_DIAG_M1, the one
+// place where the diagonal is written down,
+//   POSEIDON2_DIAG_M1_SHL32[i] = d_i 2^32 mod p, in constant memory beside the diagonal and read like it,
+//   POSEIDON2_DIAG_NARROW, bit i set: the pair (d_i, d_i 2^32 mod p) is narrow (GL_MULC_NARROW).
+// perm_constants.h itself stays what tools/gen_constants.py writes and tests/test_oracle_pins.py pins name by name against the CPU
+// checker's header: a thirteenth table of literals there would be one that no second generator vouches for, and that test refuses it.
+// To read the diagonal in constant expressions the header is included a second time, on purpose past its include guard, inside a
+// namespace with its tables as `static constexpr` (<stdint.h> is in already through gl.cuh, so nothing else lands in the namespace;
+// no copy is odr-used, so none reaches the code object). tests/test_p2_diag_constants.py recomputes what comes out.
+#pragma push_macro("MP2G_DEVCONST")
+#undef MP2G_DEVCONST
+#undef MP2G_PERM_CONSTANTS_H
+#define MP2G_DEVCONST static constexpr
+namespace p2_cx {
+#include "perm_constants.h"
+constexpr u64 diag_shl32(int i) { return (u64)(((unsigned __int128)POSEIDON2_DIAG_M1[i] << 32) % GL_P); }
+constexpr unsigned diag_narrow(int i = 0) {
+  return i == 12 ? 0u : (GL_MULC_NARROW(POSEIDON2_DIAG_M1[i], diag_shl32(i)) ? 1u << i : 0u) | diag_narrow(i + 1);
+}
+}  // namespace p2_cx
+#pragma pop_macro("MP2G_DEVCONST")
+MP2G_DEVCONST uint64_t POSEIDON2_DIAG_M1_SHL32[12] = {
+  p2_cx::diag_shl32(0), p2_cx::diag_shl32(1), p2_cx::diag_shl32(2), p2_cx::diag_shl32(3), p2_cx::diag_shl32(4), p2_cx::diag_shl32(5),
+  p2_cx::diag_shl32(6), p2_cx::diag_shl32(7), p2_cx::diag_shl32(8), p2_cx::diag_shl32(9), p2_cx::diag_shl32(10), p2_cx::diag_shl32(11),
+};
+constexpr unsigned POSEIDON2_DIAG_NARROW = p2_cx::diag_narrow();
+static_assert(POSEIDON2_DIAG_NARROW == 0xcfeu, "limbs 0, 8 and 9 take gl_mulc_addw's carry (profiles/p2_diag measured this split)");
+
 #define MP2G_POSEIDON2 0
 #define MP2G_POSEIDON 1
 
 #define c_p2_ext POSEIDON2_RC_EXT
 #define c_p2_int POSEIDON2_RC_INT
 #define c_p2_diag POSEIDON2_DIAG_M1
+#define c_p2_diag_shl32 POSEIDON2_DIAG_M1_SHL32
 #define c_p_rc POSEIDON_RC
 
 // ---- Poseidon2, weak-representative form ------------------------------------------------------
@@ -89,6 +118,13 @@ GLHD u64 p2_sbox0(u64 t) {
   u64 t2 = gl_mulw(t, t), t4 = gl_mulw(t2, t2), t3 = gl_mulw(t, t2);
   return gl_mulw(t3, t4);
 }
+// d_i a + c for limb i of the internal layer's diagonal, as some u64 representative (a, c: any u64; i a constant after unrolling). d_i is
+// known when the library is built, so the product takes gl_mulc_addw and its 96-bit tail: without the carry for the nine limbs whose
+// pair (d_i, d_i 2^32 mod p) is narrow, with it for limbs 0, 8 and 9 (the permutation 2.83 -> 3.10 G perm/s: profiles/p2_diag)
+GLHD u64 p2_diag_mul_addw(int i, u64 a, u64 c) {
+  if ((POSEIDON2_DIAG_NARROW >> i) & 1) return gl_mulc_addw<true>(a, c_p2_diag[i], c_p2_diag_shl32[i], c);
+  return gl_mulc_addw<false>(a, c_p2_diag[i], c_p2_diag_shl32[i], c);
+}
 // s_i <- d_i s_i + sum_j s_j. Device code: sum reduced once, then a weak multiply and a weak add per limb (2.60 -> 2.71 G perm/s against the
 // fused form of the host code below -- 128-bit product plus the 68-bit sum, one reduction --, whose carry chains cost more than the second
 // reduction saves)
@@ -105,7 +141,12 @@ GLHD void p2_internal(u64 s[12]) {
   ah += al >> 32;  // < 2^37
   const u64 sum = gl_reduce96w(gl_mk((u32)al, (u32)ah), ah >> 32);  // any representative will do below
 #pragma unroll
-  for (int i = 0; i < 12; i++) s[i] = gl_mul_addw(s[i], c_p2_diag[i], sum);  // the sum rides in the product's addend slots
+  for (int i = 0; i < 12; i++) {
+    s[i] = p2_diag_mul_addw(i, s[i], sum);  // the sum rides in the product's addend slots
+    // one limb after the other: without the fence hipcc zeroes the high words of every limb's addend pairs ahead of time, 10 VGPRs in
+    // the sponge and 12-14 in the tree kernels of index_hash.hip (past 128, an occupancy step) for no gain in rate (profiles/p2_diag)
+    __builtin_amdgcn_sched_barrier(0);
+  }
 #else
   u64 acc = s[0];
   u64 top = 0;
