@@ -14,6 +14,7 @@ import re
 import numpy as np
 
 from . import Gate, MULT_GEN, P
+from . import lut
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -439,8 +440,68 @@ def selector_polynomials(gates, instances, max_degree=MAX_DEGREE + 1):
 
 
 class Circuit:
-    """gates: list of Gate with selector fields filled; pre = constants ‖ sigmas [num_constants + 80][n];
-    wires [135][n]; num_selectors; pi_hash."""
+    """A built circuit. gates: list of Gate with selector fields filled (gate_array: the same as a ctypes array); pre = constants ‖
+    sigmas [num_constants + 80][n], the constants being selectors ‖ lookup selectors ‖ 2 gate constants; instances[row] = gate
+    index; wires [135][n] (None: a circuit read from a parameter file has no witness); pi_hash, and pi_row = the PublicInputGate
+    row bound to it (None: none). luts: one dict per lookup table (lut.info). The fields from n_used_rows on are the witness program
+    recursion.Builder records and stay None for a circuit made any other way."""
+
+    def __init__(self):
+        self.log_n = self.gates = self.gate_array = self.num_selectors = self.num_constants = self.pre = self.instances = None
+        self.wires = self.pi_hash = self.pi_row = self.public_inputs = None
+        self.luts, self.num_lookup_selectors, self.num_lookup_polys = [], 0, 0
+        self.domain_separator = []  # CircuitBuilder::set_domain_separator: part of the circuit digest
+        self.n_used_rows = self.tape = self.n_slots = self.input_sids = self.const_slots = None
+        self.pi_hash_sids = self.public_input_sids = self.input_values = None
+        self._prover_key = None  # framework.GpuProver.circuit_key's cache
+
+    def oracle_widths(self):
+        """widths of the four committed oracles under standard_recursion_config: constants + sigmas, 135 wires, 2 x (1 + 9) Z /
+        partial products (+ 2 x 7 lookup polynomials when the circuit has lookup tables), 2 x 8 quotient chunks"""
+        return (int(self.pre.shape[0]), NUM_WIRES, 2 * (NUM_ROUTED // 8 + self.num_lookup_polys), 16)
+
+
+def finish(log_n, gates, instances, gate_consts, wires, copy_classes, lut_info, pi_row, pi_hash):
+    """What CircuitBuilder::build does once the rows are laid out, for build() below and for recursion.Builder.build: the selector
+    fields of `gates` (sorted by the caller; instances[row] = gate index), the sigma polynomials -- the identity with each class
+    of copy_classes (an iterable of collections of routed cells (row, col)) rotated by one --, the lookup selectors of lut_info
+    (gates/selectors.rs selectors_lookup, selector_ends_lookups: between the selectors and the gate constants) and
+    constants ‖ sigmas. gate_consts[row] = the row's 2 gate constants, wires [135][n]. Draws nothing at random."""
+    n = 1 << log_n
+    cols, sel_idx, groups = selector_polynomials(gates, instances)
+    for i, g in enumerate(gates):
+        g.selector_index, (g.group_start, g.group_end) = sel_idx[i], groups[sel_idx[i]]
+    wN = pow(7277203076849721926, 1 << (32 - log_n), P)
+    xs = [pow(wN, i, P) for i in range(n)]
+    ks = [pow(MULT_GEN, j, P) for j in range(NUM_ROUTED)]
+    sig = [[ks[j] * xs[i] % P for i in range(n)] for j in range(NUM_ROUTED)]
+    for cells in copy_classes:
+        cells = sorted(cells)
+        ids = [ks[c] * xs[r] % P for r, c in cells]
+        for (r, c), v in zip(cells, ids[1:] + ids[:1]):
+            sig[c][r] = v
+    lookup_sel = []
+    if lut_info:
+        lookup_sel = [[0] * n for _ in range(LOOKUP_SELECTORS + len(lut_info))]
+        for t, info in enumerate(lut_info):
+            for r in range(info["last_lut_row"], info["first_lut_row"] + 1):
+                lookup_sel[0][r] = 1  # TransSre
+            for r in range(info["last_lu_row"], info["last_lut_row"]):
+                lookup_sel[1][r] = 1  # TransLdc
+            lookup_sel[2][info["first_lut_row"] + 1] = 1  # InitSre
+            lookup_sel[3][info["last_lu_row"]] = 1        # LastLdc
+            lookup_sel[LOOKUP_SELECTORS + t][info["last_lut_row"]] = 1  # end of table t: RE must equal the table's polynomial
+    consts = np.array(cols + lookup_sel + [[gate_consts[r][k] for r in range(n)] for k in range(2)], dtype=np.uint64)
+    ckt = Circuit()
+    ckt.log_n, ckt.gates, ckt.num_selectors, ckt.pi_hash = log_n, gates, len(cols), pi_hash
+    ckt.gate_array = (Gate * len(gates))(*gates)
+    ckt.luts, ckt.num_lookup_selectors = lut_info, len(lookup_sel)
+    ckt.num_lookup_polys = NUM_LOOKUP_POLYS if lut_info else 0
+    ckt.pre = np.concatenate([consts, np.array(sig, dtype=np.uint64)])
+    ckt.num_constants = consts.shape[0]
+    ckt.wires, ckt.instances = wires, instances
+    ckt.pi_row = pi_row  # the PublicInputGate row (mp2g_prover_bind_public_inputs)
+    return ckt
 
 
 def build(log_n, kinds, seed, copy_prob=0.35, luts=None):
@@ -456,13 +517,9 @@ def build(log_n, kinds, seed, copy_prob=0.35, luts=None):
     gates = [Gate(k, p0, p1, p2, 0, 0, 0) for (k, p0, p1, p2) in kinds]
     gates.sort(key=lambda g: (gate_degree(g), g.kind, g.p0))  # CircuitBuilder sorts gates by (degree, id)
     order = [i for i, g in enumerate(gates) if g.kind not in (LOOKUP, LOOKUP_TABLE)]
-    # rows of the lookup argument, at the end of the circuit
-    lookup_rows, n_tail = [], 0
-    for table, n_lookups in (luts or []):
-        n_lu = max(1, -(-n_lookups // NUM_LU_SLOTS))
-        n_lut = -(-len(table) // NUM_LUT_SLOTS)
-        lookup_rows.append([n_lu, n_lut])
-        n_tail += n_lu + n_lut + 1
+    # rows of the lookup argument, at the end of the circuit: per table its LookupGate rows, its LookupTableGate rows and a Noop
+    luts = luts or []
+    n_tail = sum(sum(lut.rows_needed(len(table), n_lookups)) + 1 for table, n_lookups in luts)
     assert n_tail < n - 1, "the lookup rows do not fit"
     instances = [order[i % len(order)] for i in range(n)]
     rng.shuffle(instances)
@@ -472,23 +529,17 @@ def build(log_n, kinds, seed, copy_prob=0.35, luts=None):
         instances = [instances[0]] + [g if g != pi_rows[0] else order[(r + 1) % len(order)] if gates[order[(r + 1) % len(order)]].kind != PUBLIC_INPUT else order[0]
                                       for r, g in enumerate(instances[1:], 1)]
     lut_info = []
-    if luts:
-        gi = {g.kind: i for i, g in enumerate(gates)}
-        row = n - n_tail
-        for (table, n_lookups), (n_lu, n_lut) in zip(luts, lookup_rows):
-            info = {"table": np.array(table, dtype=np.uint16).reshape(-1, 2), "n_lookups": n_lookups, "last_lu_row": row,
-                    "last_lut_row": row + n_lu, "first_lut_row": row + n_lu + n_lut - 1}
-            for r in range(row, row + n_lu):
-                instances[r] = gi[LOOKUP]
-            for r in range(row + n_lu, row + n_lu + n_lut):
-                instances[r] = gi[LOOKUP_TABLE]
-            instances[row + n_lu + n_lut] = gi[NOOP]
-            row += n_lu + n_lut + 1
-            lut_info.append(info)
-    cols, sel_idx, groups = selector_polynomials(gates, instances)
-    for i, g in enumerate(gates):
-        g.selector_index, (g.group_start, g.group_end) = sel_idx[i], groups[sel_idx[i]]
-    num_selectors = len(cols)
+    gi = {g.kind: i for i, g in enumerate(gates)}
+    row = n - n_tail
+    for table, n_lookups in luts:
+        info = lut.info(table, n_lookups, row)
+        for r in range(info["last_lu_row"], info["last_lut_row"]):
+            instances[r] = gi[LOOKUP]
+        for r in range(info["last_lut_row"], info["first_lut_row"] + 1):
+            instances[r] = gi[LOOKUP_TABLE]
+        instances[info["first_lut_row"] + 1] = gi[NOOP]
+        row = info["first_lut_row"] + 2
+        lut_info.append(info)
     pi_hash = rand_field(4, seed + 1)
     gate_consts = [[int(x) for x in rand_field(2, seed * 1000 + r)] for r in range(n)]
     wires = [[None] * NUM_WIRES for _ in range(n)]
@@ -517,44 +568,14 @@ def build(log_n, kinds, seed, copy_prob=0.35, luts=None):
             fill_row(g, w, gate_consts[r], inp, rng, pi_hash)
         if g.kind != PUBLIC_INPUT:  # nothing is copied from the public-input row: proofs of one circuit may differ there
             filled += [(r, c) for c in range(0, NUM_ROUTED, 7)]
-    # sigma: identity with each equivalence class of copy-constrained cells rotated by one
-    wN = pow(7277203076849721926, 1 << (32 - log_n), P)
-    xs = [pow(wN, i, P) for i in range(n)]
-    ks = [pow(MULT_GEN, j, P) for j in range(NUM_ROUTED)]
-    sig = [[ks[j] * xs[i] % P for i in range(n)] for j in range(NUM_ROUTED)]
+    # the equivalence classes of copy-constrained cells
     classes = {}
     for c in list(parent):
-        classes.setdefault(find(c), set()).add(c)
-    for root, members in classes.items():
-        cells = sorted(members | {root})
-        vals = {wires[r][c] for r, c in cells}
-        assert len(vals) == 1
-        ids = [ks[c] * xs[r] % P for r, c in cells]
-        for (r, c), v in zip(cells, ids[1:] + ids[:1]):
-            sig[c][r] = v
-    lookup_sel = []
-    if lut_info:
-        lookup_sel = [[0] * n for _ in range(LOOKUP_SELECTORS + len(lut_info))]
-        for t, info in enumerate(lut_info):
-            for r in range(info["last_lut_row"], info["first_lut_row"] + 1):
-                lookup_sel[0][r] = 1  # TransSre
-            for r in range(info["last_lu_row"], info["last_lut_row"]):
-                lookup_sel[1][r] = 1  # TransLdc
-            lookup_sel[2][info["first_lut_row"] + 1] = 1  # InitSre
-            lookup_sel[3][info["last_lu_row"]] = 1        # LastLdc
-            lookup_sel[LOOKUP_SELECTORS + t][info["last_lut_row"]] = 1  # end of table t: RE must equal the table's polynomial
-    consts = np.array(cols + lookup_sel + [[gate_consts[r][k] for r in range(n)] for k in range(2)], dtype=np.uint64)
-    ckt = Circuit()
-    ckt.luts, ckt.num_lookup_selectors = lut_info, len(lookup_sel)
-    ckt.num_lookup_polys = NUM_LOOKUP_POLYS if lut_info else 0
-    ckt.log_n, ckt.gates, ckt.num_selectors, ckt.pi_hash = log_n, gates, num_selectors, pi_hash
-    ckt.pre = np.concatenate([consts, np.array(sig, dtype=np.uint64)])
-    ckt.wires = np.array(wires, dtype=np.uint64).T.copy()
-    ckt.num_constants = consts.shape[0]
-    ckt.instances = instances
-    ckt.pi_row = 0 if pi_rows else None  # the PublicInputGate row (mp2g_prover_bind_public_inputs)
-    ckt.gate_array = (Gate * len(gates))(*gates)
-    return ckt
+        root = find(c)
+        classes.setdefault(root, {root}).add(c)
+    assert all(len({wires[r][c] for r, c in cells}) == 1 for cells in classes.values())
+    return finish(log_n, gates, instances, gate_consts, np.array(wires, dtype=np.uint64).T.copy(), classes.values(), lut_info,
+                  0 if pi_rows else None, pi_hash)
 
 
 ALL_KINDS = [(NOOP, 0, 0, 0), (CONSTANT, 2, 0, 0), (PUBLIC_INPUT, 0, 0, 0), (ARITHMETIC, 20, 0, 0), (BASE_SUM, 63, 2, 0),

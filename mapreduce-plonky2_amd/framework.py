@@ -14,11 +14,14 @@ leaf and of plonky2's recursive verifier, random satisfied rows): the proving wo
 of the reference's node, the circuit logic is not (a parent's witness does not contain its
 children's proofs; recursion.py builds the real verifier circuit for small trees).
 """
+import hashlib
+
 import numpy as np
 
-from . import (BatchedProver, CircuitSet, PI_HASH_GIVEN, POSEIDON2, PolynomialBatch, Verifier, circuit_digest, deserialize_proof_with_vk,
-               standard_recursion_params)
+from . import (BatchedProver, CircuitSet, PI_HASH_GIVEN, POSEIDON2, PolynomialBatch, ProofChain, Verifier, circuit_digest,
+               deserialize_proof_with_vk, standard_recursion_params)
 from . import circuits as C
+from .recursion import DeviceProof, ProverBackend
 
 NUM_ROUTED = C.NUM_ROUTED
 # recursion-framework/tests/integration.rs:55: the sum of the even elements and the hash of the elements
@@ -27,12 +30,8 @@ INPUT_CHUNK_SIZE = 4
 
 
 def circuit_fri_params(ckt, variant=POSEIDON2, **kw):
-    """FRI / oracle shape of a built circuit under standard_recursion_config: constants + sigmas, 135 wires,
-    2 x (1 + 9) Z / partial products (+ 2 x 7 lookup polynomials when the circuit has lookup tables), 2 x 8 quotient
-    chunks."""
-    nlp = getattr(ckt, "num_lookup_polys", 0)
-    return standard_recursion_params(ckt.log_n, (int(ckt.pre.shape[0]), C.NUM_WIRES, 2 * (NUM_ROUTED // 8 + nlp), 16), variant=variant,
-                                     num_lookup_polys=nlp, **kw)
+    """FRI / oracle shape of a built circuit under standard_recursion_config (Circuit.oracle_widths)"""
+    return standard_recursion_params(ckt.log_n, ckt.oracle_widths(), variant=variant, num_lookup_polys=ckt.num_lookup_polys, **kw)
 
 
 class CircuitProver:
@@ -48,7 +47,7 @@ class CircuitProver:
         pr.enable_permutation(NUM_ROUTED, 8)
         pr.enable_quotient()
         pr.set_gates(ckt.gates, ckt.num_selectors)
-        if getattr(ckt, "luts", None):
+        if ckt.luts:
             pr.set_lookups(ckt.luts)
         if witness_check:
             pr.enable_witness_check()
@@ -61,7 +60,7 @@ class CircuitProver:
         pre = PolynomialBatch.from_values(ctx, ckt.pre, self.fp.rate_bits, self.fp.cap_height, variant)
         self.constants_sigmas_cap = pre.cap
         pre.free()
-        self.circuit_digest = circuit_digest(ctx, self.constants_sigmas_cap, ckt.log_n, variant, getattr(ckt, "domain_separator", ()))
+        self.circuit_digest = circuit_digest(ctx, self.constants_sigmas_cap, ckt.log_n, variant, ckt.domain_separator)
         self.d_circuit_digest = ctx.to_device(self.circuit_digest)
 
     def prove(self, d_wires, d_pi_hash, d_circuit_digest=None):
@@ -95,11 +94,11 @@ class CircuitVerifier:
             constants_sigmas_cap = pre.cap
             pre.free()
         if circuit_digest is None:
-            circuit_digest = globals()["circuit_digest"](ctx, constants_sigmas_cap, ckt.log_n, variant, getattr(ckt, "domain_separator", ()))
+            circuit_digest = globals()["circuit_digest"](ctx, constants_sigmas_cap, ckt.log_n, variant, ckt.domain_separator)
         self.constants_sigmas_cap, self.circuit_digest = np.asarray(constants_sigmas_cap, dtype=np.uint64), np.asarray(circuit_digest, dtype=np.uint64)
         self.n_public_inputs = n_public_inputs
         self.v = Verifier(ctx, self.fp, self.constants_sigmas_cap, self.circuit_digest, ckt.gates, ckt.num_selectors,
-                          luts=getattr(ckt, "luts", None) or None, num_routed=NUM_ROUTED, degree=8, n_public_inputs=n_public_inputs,
+                          luts=ckt.luts or None, num_routed=NUM_ROUTED, degree=8, n_public_inputs=n_public_inputs,
                           capacity=capacity)
         self.num_constants = int(ckt.pre.shape[0]) - NUM_ROUTED
 
@@ -284,8 +283,8 @@ class MapReduce:
             f.free()
 
 
-class GpuProver:
-    """The proving back end recursion.RecursiveCircuits drives: prove() of one circuit built by recursion.Builder on
+class GpuProver(ProverBackend):
+    """The proving back end recursion.RecursiveCircuits drives (recursion.ProverBackend): prove() of one circuit built by recursion.Builder on
     the device, the circuit's verifier data from the preprocessed commitment, and the Merkle node hash of the circuit
     set. One CircuitProver (preprocessed oracle, gate table) per distinct circuit, kept for reuse."""
 
@@ -305,7 +304,7 @@ class GpuProver:
 
     rows_layout = True  # generate_proofs_batch fills [B][n][135] (rows) for this prover; prove_batch_launch transposes on the device
 
-    def pinned_wires(self, shape):
+    def wire_matrix(self, shape):
         """a wire matrix ([B][135][n], or [B][n][135] in the row layout) in pinned host memory: prove_batch_launch sends it up with
         an asynchronous copy on the context's stream instead of a blocking pageable one"""
         nbytes = int(np.prod(shape)) * 8
@@ -318,14 +317,13 @@ class GpuProver:
     def circuit_key(ckt):
         """identity of a circuit for the prover cache: a 128-bit digest of everything a CircuitProver is built from (preprocessed
         polynomials, gate table with selector groups, lookup tables, public-input row, domain separator)"""
-        key = getattr(ckt, "_prover_key", None)
+        key = ckt._prover_key
         if key is None:
-            import hashlib
             h = hashlib.blake2b(digest_size=16)
             h.update(np.ascontiguousarray(ckt.pre).tobytes())
             h.update(repr((ckt.log_n, ckt.num_selectors, [(g.kind, g.p0, g.p1, g.p2, g.selector_index, g.group_start, g.group_end) for g in ckt.gates],
-                           getattr(ckt, "pi_row", None), list(getattr(ckt, "domain_separator", ())))).encode())
-            for lut in (getattr(ckt, "luts", None) or []):
+                           ckt.pi_row, list(ckt.domain_separator))).encode())
+            for lut in ckt.luts:
                 h.update(repr((lut["last_lu_row"], lut["last_lut_row"], lut["first_lut_row"])).encode())
                 h.update(np.ascontiguousarray(lut["table"], dtype=np.uint16).tobytes())
             key = ckt._prover_key = h.hexdigest()
@@ -384,7 +382,6 @@ class GpuProver:
     def _chain(self, ckts, progs, B):
         """the mp2g_chain of a framework circuit (base + wraps) on this context, created for `capacity` proofs (or B when no capacity
         is set) and kept: every narrower batch runs in the same device buffers"""
-        from . import ProofChain
         cap = max(B, self.capacity) if self.capacity else B
         key = ("chain", tuple(self.circuit_key(c) for c in ckts), cap)
         ch = self.chains.get(key)
@@ -425,7 +422,6 @@ class GpuProver:
     def last_device_proof(self, b=0):
         """proof b of the last prove_chain as a recursion.DeviceProof over the chain's output buffers: valid until the next run of
         that chain (hand it on -- to a parent's generate_proofs_batch or to another rank -- before that)"""
-        from .recursion import DeviceProof
         return DeviceProof(self.last_chain.device_proof(b), keep=self.last_chain)
 
     def prove_batch_finish(self, handle):

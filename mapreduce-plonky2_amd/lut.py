@@ -4,6 +4,8 @@ the eager values of recursion.Builder.add_lookup_from_index, and prove()'s set_l
 csrc/lookup_wires.hip and csrc/witness_ops.h; nothing here is on a hot path."""
 from collections import Counter
 
+import numpy as np
+
 # the third opcode block of the public tape format (the first block's numbers are recursion.py's OP_*, the second gf5.py's)
 OP_LOOKUP, OP_LUT_END = 40, 41
 NUM_LU_SLOTS, NUM_LUT_SLOTS = 40, 26  # LookupGate / LookupTableGate num_slots with 80 routed wires
@@ -29,9 +31,17 @@ def rows_needed(table_len, n_lookups):
     return max(1, -(-n_lookups // NUM_LU_SLOTS)), -(-table_len // NUM_LUT_SLOTS)
 
 
+def info(pairs, n_lookups, first_row):
+    """the dict a built circuit keeps per table (Circuit.luts): the table and where its rows are -- the LookupGate rows from
+    first_row = last_lu_row up, then the LookupTableGate rows last_lut_row .. first_lut_row (the table runs DOWN from the last)"""
+    n_lu, n_lut = rows_needed(len(pairs), n_lookups)
+    return {"table": np.array(pairs, dtype=np.uint16).reshape(-1, 2), "n_lookups": n_lookups, "last_lu_row": first_row,
+            "last_lut_row": first_row + n_lu, "first_lut_row": first_row + n_lu + n_lut - 1}
+
+
 def fill_wires(wires, info):
-    """set_lookup_wires for one table on wires[col][row] (anything indexable that way): info = the dict circuits.build keeps per
-    table (table, n_lookups, last_lu_row, last_lut_row, first_lut_row). The looked-up slots are read, everything else written."""
+    """set_lookup_wires for one table on wires[col][row] (anything indexable that way), info as above. The looked-up slots are read,
+    everything else written."""
     pairs = [(int(a), int(b)) for a, b in info["table"]]
     entry = {p: e for e, p in enumerate(pairs)}
     mult = Counter()

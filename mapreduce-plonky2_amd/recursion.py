@@ -18,9 +18,11 @@ parity unpinned; the external anchors are the oracle's verifier accepting the wr
 Host-side Python (witness generation stays on the host in this back end); a 2^12..2^13-row verifier circuit
 takes seconds to fill. Nothing here touches the GPU library or the CPU oracle.
 """
+import io
+
 import numpy as np
 
-from . import Gate, MULT_GEN
+from . import Gate, MULT_GEN, WitnessProgram
 from . import circuits as C
 from . import gf5
 from . import lut
@@ -272,6 +274,7 @@ class Builder:
         self.input_sids = []    # slots the caller fills, in add_virtual order
         self.input_vals = []
         self.const_slots = []   # (sid, value)
+        self.domain_separator = []
         self.luts = []          # lookup tables: [(input, output)] each
         self.lookups = []       # per table: (input target, output target, tape position of its OP_LOOKUP)
 
@@ -1070,8 +1073,7 @@ class Builder:
                 self._put(row, 2 * i, x)
                 self._put(row, 2 * i + 1, out)
                 self.tape[pos + 1], self.tape[pos + 2] = row, i
-            info = {"table": np.array(pairs, dtype=np.uint16).reshape(-1, 2), "n_lookups": len(lookups), "last_lu_row": first,
-                    "last_lut_row": first + n_lu, "first_lut_row": first + n_lu + n_lut - 1}
+            info = lut.info(pairs, len(lookups), first)
 
             class _Cells:  # wires[col][row] over the builder's rows, for lut.fill_wires
                 def __init__(s, col):
@@ -1191,54 +1193,22 @@ class Builder:
         gates.sort(key=lambda g: (C.gate_degree(g), g.kind, g.p0, g.p1))
         index = {(g.kind, g.p0, g.p1, g.p2): i for i, g in enumerate(gates)}
         instances = [index[(r.kind, r.p0, r.p1, r.p2)] for r in self.rows]
-        cols, sel_idx, groups = C.selector_polynomials(gates, instances)
-        for i, g in enumerate(gates):
-            g.selector_index, (g.group_start, g.group_end) = sel_idx[i], groups[sel_idx[i]]
         wires = np.zeros((NUM_WIRES, n), dtype=np.uint64)
         for r, row in enumerate(self.rows):
             for c, v in enumerate(row.wires):
                 if v is not None:
                     wires[c, r] = v
-        wN = root_of_unity(log_n)
-        xs = np.array([pow(wN, i, P) for i in range(n)], dtype=object)
-        ks = [pow(MULT_GEN, j, P) for j in range(NUM_ROUTED)]
-        sig = [[ks[j] * int(x) % P for x in xs] for j in range(NUM_ROUTED)]
         classes = {}
         for c in list(self.parent):
-            classes.setdefault(self._find(c), set()).add(c)
-        for root, members in classes.items():
-            cells = sorted(members | {root})
-            ids = [ks[c] * int(xs[r]) % P for r, c in cells]
-            for (r, c), v in zip(cells, ids[1:] + ids[:1]):
-                sig[c][r] = v
-        lookup_sel = []
-        if lut_info:  # gates/selectors.rs selectors_lookup, selector_ends_lookups: between the selectors and the gate constants
-            lookup_sel = [[0] * n for _ in range(C.LOOKUP_SELECTORS + len(lut_info))]
-            for t, info in enumerate(lut_info):
-                for r in range(info["last_lut_row"], info["first_lut_row"] + 1):
-                    lookup_sel[0][r] = 1  # TransSre
-                for r in range(info["last_lu_row"], info["last_lut_row"]):
-                    lookup_sel[1][r] = 1  # TransLdc
-                lookup_sel[2][info["first_lut_row"] + 1] = 1  # InitSre
-                lookup_sel[3][info["last_lu_row"]] = 1        # LastLdc
-                lookup_sel[C.LOOKUP_SELECTORS + t][info["last_lut_row"]] = 1  # end of table t
-        consts = np.array(cols + lookup_sel + [[row.consts[k] for row in self.rows] for k in range(2)], dtype=np.uint64)
-        ckt = C.Circuit()
-        ckt.log_n, ckt.gates, ckt.num_selectors = log_n, gates, len(cols)
-        ckt.pi_hash = np.array([t.v for t in pi_hash], dtype=np.uint64)
+            root = self._find(c)
+            classes.setdefault(root, {root}).add(c)
+        ckt = C.finish(log_n, gates, instances, [row.consts for row in self.rows], wires, classes.values(), lut_info, pi_row,
+                       np.array([t.v for t in pi_hash], dtype=np.uint64))
         ckt.public_inputs = np.array([t.v for t in self.public_inputs], dtype=np.uint64)
-        ckt.pre = np.concatenate([consts, np.array(sig, dtype=np.uint64)])
-        ckt.wires = wires
-        ckt.num_constants = consts.shape[0]
-        ckt.instances = instances
-        ckt.pi_row = pi_row
-        ckt.gate_array = (Gate * len(gates))(*gates)
-        ckt.luts, ckt.num_lookup_selectors = lut_info, len(lookup_sel)
-        ckt.num_lookup_polys = C.NUM_LOOKUP_POLYS if lut_info else 0
+        ckt.domain_separator = list(self.domain_separator)
         ckt.n_used_rows = n_rows - 1
         # the witness program of this circuit (see the OP_* table above) and the inputs this build was run with
         ckt.tape = np.array(self.tape, dtype=np.uint64)
-        ckt.domain_separator = list(getattr(self, "domain_separator", []))  # CircuitBuilder::set_domain_separator: part of the circuit digest
         ckt.n_slots = self.n_slots
         ckt.input_sids = np.array(self.input_sids, dtype=np.uint32)
         ckt.const_slots = np.array([[sid, v] for sid, v in self.const_slots], dtype=np.uint64).reshape(-1, 2)
@@ -1633,8 +1603,7 @@ class InnerCircuit:
         self.circuit_digest = [int(x) for x in circuit_digest]
         self.n_public_inputs = n_public_inputs
         # CommonCircuitData::luts and the rows of each table (the dicts of ckt.luts), num_lookup_selectors
-        self.luts = list(getattr(ckt, "luts", None) or [])
-        self.num_lookup_selectors = getattr(ckt, "num_lookup_selectors", 0) if self.luts else 0
+        self.luts, self.num_lookup_selectors = list(ckt.luts), ckt.num_lookup_selectors
 
 
 def check_lookup_constraints_circuit(b, luts, sel, wires, zs, zs_next, deltas, lut_polys):
@@ -1938,13 +1907,13 @@ def map_circuit(inputs, builder=None):
     return b.build()
 
 
-def wrap_circuit(inner, caps, openings, fri, public_inputs, strict=True):
-    """WrapCircuit::build_wrap_circuit, first step (wrap_circuit.rs:58-99): verify the inner proof with the inner
-    circuit's verifier data as constants and expose the inner proof's public inputs"""
+def wrap_circuit(inner, caps, openings, fri, public_inputs, strict=True, min_log_n=6):
+    """WrapCircuit::build_wrap_circuit, one step (wrap_circuit.rs:58-99): verify the inner proof with the inner
+    circuit's verifier data as constants and expose the inner proof's public inputs. The framework's chains pad every step
+    to min_log_n = RECURSION_THRESHOLD."""
     b = Builder(strict)
-    pis = verify_proof_circuit(b, inner, caps, openings, fri, public_inputs)
-    b.register_public_inputs(pis)
-    return b.build()
+    b.register_public_inputs(verify_proof_circuit(b, inner, caps, openings, fri, public_inputs))
+    return b.build(min_log_n=min_log_n)
 
 
 # ---- the recursion framework (recursion-framework/src: circuit_builder.rs, universal_verifier_gadget/*, framework.rs) --------------------
@@ -2035,10 +2004,7 @@ def build_wrap_chain(prover, fri_params, base_vd):
     cur = base_vd
     for _ in range(4):
         inner = InnerCircuit(cur[0], fri_params(cur[0]), cur[1], cur[2], len(cur[0].public_inputs))
-        b = Builder(strict=False)
-        pis = verify_proof_circuit(b, inner, *dummy_proof(inner))
-        b.register_public_inputs(pis)
-        w = b.build(min_log_n=RECURSION_THRESHOLD)
+        w = wrap_circuit(inner, *dummy_proof(inner), strict=False, min_log_n=RECURSION_THRESHOLD)
         cap, digest = prover.verifier_data(w)
         cur = (w, cap, digest)
         chain.append(cur)
@@ -2055,10 +2021,7 @@ def wrap_proof_chain(prover, fri_params, chain, base, proof):
     for step, (wckt, wcap, wdig) in enumerate(chain[1:]):
         prev = chain[step]
         inner = InnerCircuit(cur_ckt, fri_params(cur_ckt), prev[1], prev[2], len(cur_ckt.public_inputs))
-        b = Builder()
-        pis = verify_proof_circuit(b, inner, *cur_proof)
-        b.register_public_inputs(pis)
-        w = b.build(min_log_n=RECURSION_THRESHOLD)
+        w = wrap_circuit(inner, *cur_proof, min_log_n=RECURSION_THRESHOLD)
         assert np.array_equal(w.pre, wckt.pre)
         caps, openings, proof = prover.prove(w)
         cur_ckt, cur_proof = w, (caps, openings, proof, w.public_inputs)
@@ -2077,6 +2040,28 @@ def dummy_circuit(num_gates_log, num_public_inputs):
     b = Builder()
     b.register_public_inputs([b.add_virtual(0) for _ in range(num_public_inputs)])
     return b.build(min_log_n=num_gates_log)
+
+
+class ProverBackend:
+    """The proving back end WrapCircuit, RecursiveCircuits and FinalWrapCircuit drive: framework.GpuProver in production, the CPU
+    oracle in the tests. A back end defines
+        verifier_data(ckt) -> (constants_sigmas cap, circuit digest)   VerifierOnlyCircuitData of a built circuit
+        prove(ckt) -> (caps, openings, proof)                          of the circuit's own witness (ckt.wires, ckt.pi_hash)
+        prove_batch(ckt, wires, pi_hash) -> [(caps, openings, proof)]  of B witnesses: wires [B][135][n], pi_hash [B][4]
+        two_to_one(left, right) -> 4 ints                              the node hash of the circuit set's Merkle tree
+    and may change the capabilities below. One that is handed DeviceProofs and leaves device_witness off also has `ctx`, the
+    context that downloads them."""
+    device_witness = False  # True: ProofSession.prove_chain hands whole chains to prove_chain, the witnesses are made on the device
+    rows_layout = False     # True: prove_batch takes the wires in the witness executor's row layout [B][n][135]
+    capacity = 0            # > 0: a session's wire matrices are made for this many proofs and serve every narrower batch
+
+    def wire_matrix(self, shape):
+        """the host wire matrix ProofSession fills and hands to prove_batch"""
+        return np.empty(shape, dtype=np.uint64)
+
+    def prove_chain(self, ckts, progs, cur, capture=None, name="", patches=()):
+        """device_witness: a chain's proofs from its first step's inputs cur [B][n_inputs] (see framework.GpuProver.prove_chain)"""
+        raise NotImplementedError("a back end with device_witness defines prove_chain")
 
 
 class WrapCircuit:
@@ -2101,8 +2086,8 @@ class WrapCircuit:
 class RecursiveCircuits:
     """framework.rs RecursiveCircuits + the per-circuit wrap chains: build every circuit's structure once (dummy
     witnesses), collect the digests of the final wrap circuits into the circuit set, then generate_proof().
-    prover(ckt) -> (caps, openings, proof, constants_sigmas_cap, circuit_digest) is the proving back end (the HIP
-    prover in production, the oracle in the CPU tests)."""
+    prover: a ProverBackend (the HIP prover in production, the oracle in the CPU tests); fri_params(ckt): the FRI shape of a
+    circuit's proofs under the prover's hasher (framework.circuit_fri_params)."""
 
     def __init__(self, circuits, prover, fri_params):
         self.prover, self.fri_params = prover, fri_params
@@ -2112,7 +2097,7 @@ class RecursiveCircuits:
         # build_data_for_universal_verifier does (universal_verifier_gadget/mod.rs:66-87)
         n_pi = circuits[0].num_public_inputs + 4
         assert all(c.num_public_inputs + 4 == n_pi for c in circuits)
-        dummy = self._dummy_circuit(n_pi)
+        dummy = dummy_circuit(6, n_pi)
         chain = self._wrap_structure(dummy)
         self.rec = InnerCircuit(chain[-1][0], fri_params(chain[-1][0]), chain[-1][1], chain[-1][2], n_pi)
         self.rec_common = common_data(chain[-1][0])
@@ -2120,7 +2105,7 @@ class RecursiveCircuits:
         self.chains, self.vds = {}, {}
         zero_set = [0, 0, 0, 0]
         for c in circuits:
-            proofs = [self._dummy_proof(self.rec) for _ in range(c.num_verifiers)]
+            proofs = [dummy_proof(self.rec) for _ in range(c.num_verifiers)]
             vds = [(np.zeros((16, 4), dtype=np.uint64), np.zeros(4, dtype=np.uint64))] * c.num_verifiers
             height = max(0, (self.set_size - 1).bit_length())
             mems = [([0] * height, [[0, 0, 0, 0]] * height)] * c.num_verifiers
@@ -2129,24 +2114,21 @@ class RecursiveCircuits:
             assert common_data(chain[-1][0]) == self.rec_common, f"{c.name}: the final wrap circuit does not have the shared shape"
             self.chains[c.name] = [self._verifier_data(base)] + chain
             self.vds[c.name] = (chain[-1][1], chain[-1][2])
-        # the circuit set: Merkle tree (cap height 0) over the final wrap circuits' digests, padded with [0] leaves
-        self.digests = [self.vds[c.name][1] for c in circuits]
+        self._circuit_set()
+
+    def _circuit_set(self):
+        """the circuit set: Merkle tree (cap height 0) over the final wrap circuits' digests, padded with [0] leaves; and what
+        generate_proofs_batch keeps: the witness programs per circuit and the session of the framework's own prover"""
+        self.digests = [self.vds[n][1] for n in self.circuits]
         self.set_levels = self._set_tree(self.digests)
         self.set_digest = self.set_levels[-1][0]
+        self.programs, self._session = {}, ProofSession(self.prover)
 
     # -- structure helpers (dummy witnesses, strict off)
-    def _dummy_circuit(self, n_pi):
-        b = Builder()
-        b.register_public_inputs([b.add_virtual(0) for _ in range(n_pi)])
-        return b.build(min_log_n=6)
-
     def _verifier_data(self, ckt):
         """(circuit, constants_sigmas cap, circuit digest): the preprocessed commitment by the proving back end"""
         cap, digest = self.prover.verifier_data(ckt)
         return (ckt, cap, digest)
-
-    def _dummy_proof(self, inner):
-        return dummy_proof(inner)
 
     def _wrap_structure(self, base):
         return build_wrap_chain(self.prover, self.fri_params, self._verifier_data(base))
@@ -2184,6 +2166,94 @@ class RecursiveCircuits:
         caps, openings, proof = self.prover.prove(base)
         return wrap_proof_chain(self.prover, self.fri_params, self.chains[name], base, (caps, openings, proof, base.public_inputs))
 
+    def to_bytes(self):
+        """RecursiveCircuits -> bytes: every circuit's base + wrap chain (preprocessed polynomials, gate tables, witness programs),
+        their verifier data, the circuit set. The circuit logic (Python callables), the prover and the FRI parameter rule are not
+        part of the file: from_bytes takes them again."""
+        out = {"version": np.array([PARAMS_VERSION, self.set_size], dtype=np.int64),
+               "names": np.array([n.encode() for n in self.circuits]),
+               "shape": np.array([[c.num_verifiers, c.num_public_inputs, len(self.chains[n])] for n, c in self.circuits.items()], dtype=np.int64),
+               "set_digest": np.asarray(self.set_digest, dtype=np.uint64)}
+        for n in self.circuits:
+            for step, (ckt, cap, digest) in enumerate(self.chains[n]):
+                pre = f"{n}/{step}/"
+                circuit_to_arrays(ckt, pre, out)
+                out[pre + "cap"], out[pre + "digest"] = np.asarray(cap, dtype=np.uint64), np.asarray(digest, dtype=np.uint64)
+        circuit_to_arrays(self.rec.ckt, "rec/", out)
+        out["rec/cap"], out["rec/digest"] = np.array(self.rec.cap, dtype=np.uint64), np.array(self.rec.circuit_digest, dtype=np.uint64)
+        buf = io.BytesIO()
+        np.savez_compressed(buf, **out)
+        return buf.getvalue()
+
+    @classmethod
+    def from_bytes(cls, data, circuits, prover, fri_params):
+        """bytes of to_bytes() -> RecursiveCircuits, without building a circuit: `circuits` are the FrameworkCircuit objects (names,
+        verifier counts and public-input counts must be the file's), prover / fri_params as for the constructor. The circuit set is
+        re-hashed by the prover and must give the file's digest (a file made with the other hasher fails here)."""
+        z = np.load(io.BytesIO(data), allow_pickle=False)
+        version, set_size = (int(x) for x in z["version"])
+        if version != PARAMS_VERSION:
+            raise ValueError(f"parameter file version {version}, expected {PARAMS_VERSION}")
+        names = [n.decode() for n in z["names"]]
+        shape = z["shape"]
+        if names != [c.name for c in circuits] or any((c.num_verifiers, c.num_public_inputs) != (int(s[0]), int(s[1])) for c, s in zip(circuits, shape)):
+            raise ValueError("the parameter file was built for another set of circuits")
+        self = cls.__new__(cls)
+        self.prover, self.fri_params = prover, fri_params
+        self.circuits = {c.name: c for c in circuits}
+        self.set_size = set_size
+        self.chains, self.vds = {}, {}
+        for n, s in zip(names, shape):
+            self.chains[n] = [(circuit_from_arrays(z, f"{n}/{step}/"), z[f"{n}/{step}/cap"], z[f"{n}/{step}/digest"]) for step in range(int(s[2]))]
+            self.vds[n] = (self.chains[n][-1][1], self.chains[n][-1][2])
+        rec = circuit_from_arrays(z, "rec/")
+        self.rec = InnerCircuit(rec, fri_params(rec), z["rec/cap"], z["rec/digest"], circuits[0].num_public_inputs + 4)
+        self.rec_common = common_data(rec)
+        self._circuit_set()
+        if [int(x) for x in self.set_digest] != [int(x) for x in z["set_digest"]]:
+            raise ValueError("the circuit set of the parameter file does not hash to its digest with this prover")
+        return self
+
+    def generate_proofs_batch(self, name, jobs, threads=0, session=None, capture=None):
+        """RecursiveCircuits.generate_proof for a batch of nodes of circuit `name`: jobs = [(child_proofs, child_names, inputs)].
+        Witnesses come from the circuits' recorded programs (csrc/witness.hip: host threads, one proof each), proving from
+        prover.prove_batch(circuit, wires [B][135][n], pi_hash [B][4]). Returns the final proofs, one per job.
+        `session` (ProofSession): the prover and the host wire matrices to use instead of the framework's own -- independent trees
+        (the reference's independent rows / blocks) run in one thread each with a session of their own, so that one tree's witness
+        generation fills the time another's prove() spends on the GPU; circuits, verifier data and witness programs are shared.
+        `capture` (a list): receives, per job and chain step, (name, step, circuit, circuit digest, wire matrix [135][n], pi_hash, caps,
+        openings, proof) -- what a checker needs to prove the same witness again."""
+        sess = session if session is not None else self.default_session()
+        progs = self.witness_programs(name)
+        rows, patches = [], []
+        for j, (child_proofs, child_names, inputs) in enumerate(jobs):
+            parts = [np.asarray(self.set_digest, dtype=np.uint64)]
+            for pr, cn in zip(child_proofs, child_names):
+                vd = self.vds[cn]
+                if isinstance(pr, DeviceProof) and not sess.prover.device_witness:
+                    pr = pr.to_host(sess.prover.ctx)
+                if isinstance(pr, DeviceProof):  # the proof words are copied in on the device; the host fills what surrounds them
+                    bits, sib = self.membership(vd[1])
+                    head = np.concatenate([np.asarray(vd[0], dtype=np.uint64).ravel(), np.asarray(vd[1], dtype=np.uint64).ravel()])
+                    patches.append((j, sum(p.size for p in parts) + head.size, pr))
+                    parts += [head, np.zeros(pr.n_words, dtype=np.uint64), np.asarray(bits, dtype=np.uint64).ravel(), np.asarray(sib, dtype=np.uint64).ravel()]
+                else:
+                    parts.append(universal_inputs(pr, vd, self.membership(vd[1])))
+            if inputs is not None:
+                parts.append(np.asarray(inputs, dtype=np.uint64).ravel())
+            rows.append(np.concatenate(parts))
+        return sess.prove_chain(name, self.chains[name], progs, np.stack(rows), threads, capture, patches)
+
+    def default_session(self):
+        return self._session
+
+    def witness_programs(self, name):
+        """the recorded witness programs of a circuit's chain (base, wraps); read-only once made, shared by every session"""
+        progs = self.programs.get(name)
+        if progs is None:
+            progs = self.programs[name] = [WitnessProgram(c[0]) for c in self.chains[name]]
+        return progs
+
 
 # ---- parameter files: the built framework without rebuilding it (framework.rs derives Serialize / Deserialize for RecursiveCircuits;
 # the container here is numpy's .npz -- plain arrays, loaded with allow_pickle=False -- not bincode of plonky2's CircuitData)
@@ -2202,10 +2272,9 @@ def circuit_to_arrays(ckt, prefix, out):
                                      dtype=np.uint32).reshape(-1, 7)
     out[prefix + "instances"] = np.asarray(ckt.instances, dtype=np.uint32)
     out[prefix + "domain_separator"] = np.asarray(ckt.domain_separator, dtype=np.uint64)
-    luts = getattr(ckt, "luts", None) or []
-    if luts:  # only a circuit with lookup tables has these entries: a file without one is what it was
-        out[prefix + "lut_rows"] = np.array([[t[k] for k in _LUT_ROWS] for t in luts], dtype=np.int64)
-        for i, t in enumerate(luts):
+    if ckt.luts:  # only a circuit with lookup tables has these entries: a file without one is what it was
+        out[prefix + "lut_rows"] = np.array([[t[k] for k in _LUT_ROWS] for t in ckt.luts], dtype=np.int64)
+        for i, t in enumerate(ckt.luts):
             out[prefix + f"lut_table/{i}"] = np.ascontiguousarray(t["table"], dtype=np.uint16).reshape(-1, 2)
 
 
@@ -2219,66 +2288,11 @@ def circuit_from_arrays(data, prefix):
     ckt.gate_array = (Gate * len(ckt.gates))(*ckt.gates)
     ckt.instances = [int(x) for x in data[prefix + "instances"]]
     ckt.domain_separator = [int(x) for x in data[prefix + "domain_separator"]]
-    ckt.luts, ckt.num_lookup_selectors, ckt.num_lookup_polys = [], 0, 0
-    if prefix + "lut_rows" in getattr(data, "files", data):
+    if prefix + "lut_rows" in data:
         for i, row in enumerate(data[prefix + "lut_rows"]):
             ckt.luts.append({**{k: int(v) for k, v in zip(_LUT_ROWS, row)}, "table": np.array(data[prefix + f"lut_table/{i}"], dtype=np.uint16)})
         ckt.num_lookup_selectors, ckt.num_lookup_polys = C.LOOKUP_SELECTORS + len(ckt.luts), C.NUM_LOOKUP_POLYS
-    ckt.wires = None  # a parameter file holds circuits, not witnesses
-    return ckt
-
-
-def _params_to_bytes(self):
-    """RecursiveCircuits -> bytes: every circuit's base + wrap chain (preprocessed polynomials, gate tables, witness programs),
-    their verifier data, the circuit set. The circuit logic (Python callables), the prover and the FRI parameter rule are not
-    part of the file: from_bytes takes them again."""
-    import io
-    out = {"version": np.array([PARAMS_VERSION, self.set_size], dtype=np.int64),
-           "names": np.array([n.encode() for n in self.circuits]),
-           "shape": np.array([[c.num_verifiers, c.num_public_inputs, len(self.chains[n])] for n, c in self.circuits.items()], dtype=np.int64),
-           "set_digest": np.asarray(self.set_digest, dtype=np.uint64)}
-    for n in self.circuits:
-        for step, (ckt, cap, digest) in enumerate(self.chains[n]):
-            pre = f"{n}/{step}/"
-            circuit_to_arrays(ckt, pre, out)
-            out[pre + "cap"], out[pre + "digest"] = np.asarray(cap, dtype=np.uint64), np.asarray(digest, dtype=np.uint64)
-    circuit_to_arrays(self.rec.ckt, "rec/", out)
-    out["rec/cap"], out["rec/digest"] = np.array(self.rec.cap, dtype=np.uint64), np.array(self.rec.circuit_digest, dtype=np.uint64)
-    buf = io.BytesIO()
-    np.savez_compressed(buf, **out)
-    return buf.getvalue()
-
-
-def _params_from_bytes(cls, data, circuits, prover, fri_params):
-    """bytes of to_bytes() -> RecursiveCircuits, without building a circuit: `circuits` are the FrameworkCircuit objects (names,
-    verifier counts and public-input counts must be the file's), prover / fri_params as for the constructor. The circuit set is
-    re-hashed by the prover and must give the file's digest (a file made with the other hasher fails here)."""
-    import io
-    z = np.load(io.BytesIO(data), allow_pickle=False)
-    version, set_size = (int(x) for x in z["version"])
-    if version != PARAMS_VERSION:
-        raise ValueError(f"parameter file version {version}, expected {PARAMS_VERSION}")
-    names = [n.decode() for n in z["names"]]
-    shape = z["shape"]
-    if names != [c.name for c in circuits] or any((c.num_verifiers, c.num_public_inputs) != (int(s[0]), int(s[1])) for c, s in zip(circuits, shape)):
-        raise ValueError("the parameter file was built for another set of circuits")
-    self = cls.__new__(cls)
-    self.prover, self.fri_params = prover, fri_params
-    self.circuits = {c.name: c for c in circuits}
-    self.set_size = set_size
-    self.chains, self.vds = {}, {}
-    for n, s in zip(names, shape):
-        self.chains[n] = [(circuit_from_arrays(z, f"{n}/{step}/"), z[f"{n}/{step}/cap"], z[f"{n}/{step}/digest"]) for step in range(int(s[2]))]
-        self.vds[n] = (self.chains[n][-1][1], self.chains[n][-1][2])
-    rec = circuit_from_arrays(z, "rec/")
-    self.rec = InnerCircuit(rec, fri_params(rec), z["rec/cap"], z["rec/digest"], circuits[0].num_public_inputs + 4)
-    self.rec_common = common_data(rec)
-    self.digests = [self.vds[n][1] for n in names]
-    self.set_levels = self._set_tree(self.digests)
-    self.set_digest = self.set_levels[-1][0]
-    if [int(x) for x in self.set_digest] != [int(x) for x in z["set_digest"]]:
-        raise ValueError("the circuit set of the parameter file does not hash to its digest with this prover")
-    return self
+    return ckt  # without wires: a parameter file holds circuits, not witnesses
 
 
 def split_hash_element_to_low_high(b, element):
@@ -2357,7 +2371,7 @@ class RecursiveCircuitsVerifierGadget:
         fw = self.fw
         height = max(0, (fw.set_size - 1).bit_length()) - CIRCUIT_SET_CAP_HEIGHT
         vd = (np.zeros((1 << fw.rec.fp.cap_height, 4), dtype=np.uint64), np.zeros(4, dtype=np.uint64))
-        return fw._dummy_proof(fw.rec), vd, ([0] * height, [np.zeros(4, dtype=np.uint64)] * height)
+        return dummy_proof(fw.rec), vd, ([0] * height, [np.zeros(4, dtype=np.uint64)] * height)
 
     def verify_proof_in_circuit_set(self, b, proof, vd, membership):
         """any circuit of the set: verifier data as witnesses, digest check, membership in the set, same set in the proof
@@ -2391,6 +2405,7 @@ class FinalWrapCircuit:
         self.n_pi = num_public_inputs if num_public_inputs is not None else fw.rec.n_public_inputs - 4
         self.ckt = self._build(self.gadget.dummy_inputs(), strict=False)
         self.cap, self.digest = prover.verifier_data(self.ckt)
+        self._prog, self._session = None, ProofSession(prover)
 
     def _build(self, inputs, strict=True):
         b = Builder(strict, hasher=1)
@@ -2399,8 +2414,7 @@ class FinalWrapCircuit:
         return b.build(min_log_n=RECURSION_THRESHOLD)
 
     def program(self):
-        from . import WitnessProgram
-        if not hasattr(self, "_prog"):
+        if self._prog is None:
             self._prog = WitnessProgram(self.ckt)
         return self._prog
 
@@ -2418,16 +2432,7 @@ class FinalWrapCircuit:
         for pr, name in zip(proofs, names):
             vd = self.fw.vds[name]
             rows.append(universal_inputs(pr, vd, self.fw.membership(vd[1])))
-        cur = np.stack(rows)
-        prog = self.program()
-        if getattr(self.prover, "device_witness", False):
-            return self.prover.prove_chain([self.ckt], [prog], cur, capture=capture, name="final wrap")
-        wires, pi_hash, pis = prog.run(cur)
-        outs = self.prover.prove_batch(self.ckt, wires, pi_hash)
-        if capture is not None:
-            for i, (c, o, p) in enumerate(outs):
-                capture.append(("final wrap", 0, self.ckt, self.digest, wires[i].copy(), pi_hash[i].copy(), c, o, p))
-        return [(c, o, p, pis[i]) for i, (c, o, p) in enumerate(outs)]
+        return self._session.prove_chain("final wrap", [(self.ckt, self.cap, self.digest)], [self.program()], np.stack(rows), capture=capture)
 
 
 def map_logic(b, child_pis, inputs):
@@ -2526,94 +2531,41 @@ class DeviceProof:
         return caps, openings.reshape(-1, 2), fri, pis
 
 
-def _generate_proofs_batch(self, name, jobs, threads=0, session=None, capture=None):
-    """RecursiveCircuits.generate_proof for a batch of nodes of circuit `name`: jobs = [(child_proofs, child_names, inputs)].
-    Witnesses come from the circuits' recorded programs (csrc/witness.hip: host threads, one proof each), proving from
-    prover.prove_batch(circuit, wires [B][135][n], pi_hash [B][4]). Returns the final proofs, one per job.
-    `session` (ProofSession): the prover and the host wire matrices to use instead of the framework's own -- independent trees
-    (the reference's independent rows / blocks) run in one thread each with a session of their own, so that one tree's witness
-    generation fills the time another's prove() spends on the GPU; circuits, verifier data and witness programs are shared.
-    `capture` (a list): receives, per job and chain step, (name, step, circuit, circuit digest, wire matrix [135][n], pi_hash, caps,
-    openings, proof) -- what a checker needs to prove the same witness again."""
-    sess = session if session is not None else self.default_session()
-    progs = self.witness_programs(name)
-    on_device = bool(getattr(sess.prover, "device_witness", False))
-    rows, patches = [], []
-    for j, (child_proofs, child_names, inputs) in enumerate(jobs):
-        parts = [np.asarray(self.set_digest, dtype=np.uint64)]
-        for pr, cn in zip(child_proofs, child_names):
-            vd = self.vds[cn]
-            if isinstance(pr, DeviceProof) and not on_device:
-                pr = pr.to_host(sess.prover.ctx)
-            if isinstance(pr, DeviceProof):  # the proof words are copied in on the device; the host fills what surrounds them
-                bits, sib = self.membership(vd[1])
-                head = np.concatenate([np.asarray(vd[0], dtype=np.uint64).ravel(), np.asarray(vd[1], dtype=np.uint64).ravel()])
-                patches.append((j, sum(p.size for p in parts) + head.size, pr))
-                parts += [head, np.zeros(pr.n_words, dtype=np.uint64), np.asarray(bits, dtype=np.uint64).ravel(), np.asarray(sib, dtype=np.uint64).ravel()]
-            else:
-                parts.append(universal_inputs(pr, vd, self.membership(vd[1])))
-        if inputs is not None:
-            parts.append(np.asarray(inputs, dtype=np.uint64).ravel())
-        rows.append(np.concatenate(parts))
-    cur = np.stack(rows)
-    if getattr(sess.prover, "device_witness", False):
-        assert cur.shape[1] == progs[0].n_inputs, f"{name}: {cur.shape[1]} inputs for a program of {progs[0].n_inputs}"
-        return sess.prover.prove_chain([c[0] for c in self.chains[name]], progs, cur, capture=capture, name=name, patches=patches)
-    proofs = None
-    for step, prog in enumerate(progs):
-        assert cur.shape[1] == prog.n_inputs, f"{name} step {step}: {cur.shape[1]} inputs for a program of {prog.n_inputs}"
-        rows = bool(getattr(sess.prover, "rows_layout", False))
-        wires, pi_hash, pis = prog.run(cur, threads, out=sess.wire_buffer(name, step, cur.shape[0], prog.log_n, rows), rows=rows)
-        outs = sess.prover.prove_batch(self.chains[name][step][0], wires, pi_hash)
-        proofs = [(c, o, p, pis[i]) for i, (c, o, p) in enumerate(outs)]
-        if capture is not None:
-            ckt, _, digest = self.chains[name][step]
-            for i, (c, o, p) in enumerate(outs):
-                w = np.ascontiguousarray(wires[i].T) if rows else wires[i].copy()
-                capture.append((name, step, ckt, digest, w, pi_hash[i].copy(), c, o, p))
-        if step + 1 < len(progs):
-            cur = np.stack([proof_inputs(p) for p in proofs])
-    return proofs
-
-
 class ProofSession:
     """what one thread of generate_proofs_batch owns: its prover (a GPU context / stream of its own) and the host wire
     matrices it fills, one per (circuit, batch size), reused from call to call. With a GPU prover the matrices live in pinned
-    host memory and go up asynchronously on the prover's stream (prover.pinned_wires)."""
+    host memory and go up asynchronously on the prover's stream (prover.wire_matrix)."""
 
     def __init__(self, prover):
         self.prover, self.buffers = prover, {}
 
     def wire_buffer(self, name, step, batch, log_n, rows=False):
-        cap = max(batch, getattr(self.prover, "capacity", 0) or 0)  # a prover with a capacity serves every narrower batch from one matrix
+        cap = max(batch, self.prover.capacity)  # a prover with a capacity serves every narrower batch from one matrix
         key = (name, step, cap)
         buf = self.buffers.get(key)
         if buf is None:
-            shape = (cap, 1 << log_n, 135) if rows else (cap, 135, 1 << log_n)
-            make = getattr(self.prover, "pinned_wires", None)
-            buf = self.buffers[key] = make(shape) if make is not None else np.empty(shape, dtype=np.uint64)
+            buf = self.buffers[key] = self.prover.wire_matrix((cap, 1 << log_n, 135) if rows else (cap, 135, 1 << log_n))
         return buf[:batch]
 
-
-def _default_session(self):
-    if not hasattr(self, "_session"):
-        self._session = ProofSession(self.prover)
-    return self._session
-
-
-def _witness_programs(self, name):
-    """the recorded witness programs of a circuit's chain (base, wraps); read-only once made, shared by every session"""
-    from . import WitnessProgram
-    if not hasattr(self, "programs"):
-        self.programs = {}
-    progs = self.programs.get(name)
-    if progs is None:
-        progs = self.programs[name] = [WitnessProgram(c[0]) for c in self.chains[name]]
-    return progs
-
-
-RecursiveCircuits.default_session = _default_session
-RecursiveCircuits.to_bytes = _params_to_bytes
-RecursiveCircuits.from_bytes = classmethod(_params_from_bytes)
-RecursiveCircuits.witness_programs = _witness_programs
-RecursiveCircuits.generate_proofs_batch = _generate_proofs_batch
+    def prove_chain(self, name, chain, progs, cur, threads=0, capture=None, patches=()):
+        """the proofs of `chain` = [(circuit, cap, digest)] per step, the first step's witness inputs being cur [B][n_inputs] and
+        every later step's the proof before it (proof_inputs): [(caps, openings, proof, public_inputs)] of the last step. A prover
+        with device_witness runs the whole chain (ProverBackend.prove_chain; patches: see there); otherwise progs[step] fills the
+        wire matrices on `threads` host threads and prover.prove_batch proves them, step by step. capture: see
+        RecursiveCircuits.generate_proofs_batch."""
+        if self.prover.device_witness:
+            assert cur.shape[1] == progs[0].n_inputs, f"{name}: {cur.shape[1]} inputs for a program of {progs[0].n_inputs}"
+            return self.prover.prove_chain([c[0] for c in chain], progs, cur, capture=capture, name=name, patches=patches)
+        rows = self.prover.rows_layout
+        for step, (prog, (ckt, _, digest)) in enumerate(zip(progs, chain)):
+            assert cur.shape[1] == prog.n_inputs, f"{name} step {step}: {cur.shape[1]} inputs for a program of {prog.n_inputs}"
+            wires, pi_hash, pis = prog.run(cur, threads, out=self.wire_buffer(name, step, cur.shape[0], prog.log_n, rows), rows=rows)
+            outs = self.prover.prove_batch(ckt, wires, pi_hash)
+            proofs = [(c, o, p, pis[i]) for i, (c, o, p) in enumerate(outs)]
+            if capture is not None:
+                for i, (c, o, p) in enumerate(outs):
+                    w = np.ascontiguousarray(wires[i].T) if rows else wires[i].copy()
+                    capture.append((name, step, ckt, digest, w, pi_hash[i].copy(), c, o, p))
+            if step + 1 < len(progs):
+                cur = np.stack([proof_inputs(p) for p in proofs])
+        return proofs

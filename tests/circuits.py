@@ -37,7 +37,7 @@ class OrcCircuit(ctypes.Structure):
 
 def orc_circuit(ckt):
     """(OrcCircuit, keep-alive list) of a built circuit"""
-    luts = getattr(ckt, "luts", None) or []
+    luts = ckt.luts or []  # bench.py's CPU farm hands over a stand-in with luts = None
     tabs = [np.ascontiguousarray(t["table"], dtype=np.uint16) for t in luts]
     arr = (OrcLookup * max(1, len(luts)))()
     for i, (t, tab) in enumerate(zip(luts, tabs)):
@@ -49,9 +49,7 @@ def orc_circuit(ckt):
 
 def oracle_params(ckt, variant=0, **kw):
     """standard_recursion_config FRI / oracle shape of a built circuit (with the lookup polynomials, if any)"""
-    nlp = getattr(ckt, "num_lookup_polys", 0)
-    return O.standard_params(ckt.log_n, (int(ckt.pre.shape[0]), NUM_WIRES, 2 * (NUM_ROUTED // 8 + nlp), 16), variant=variant,
-                             num_lookup_polys=nlp, **kw)
+    return O.standard_params(ckt.log_n, ckt.oracle_widths(), variant=variant, num_lookup_polys=ckt.num_lookup_polys, **kw)
 
 
 def prove_witness(ckt, fp, circuit_digest, wires, pi_hash):

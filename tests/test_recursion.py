@@ -85,7 +85,7 @@ def test_wrap_rejects_a_bad_inner_proof(base_and_proof):
         R.wrap_circuit(inner, caps, openings, proof, pis)
 
 
-class OracleProver:
+class OracleProver(R.ProverBackend):
     """proving back end for recursion.RecursiveCircuits on the CPU: the oracle proves, and verifies what it proved"""
 
     def verifier_data(self, ckt):

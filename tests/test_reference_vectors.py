@@ -116,10 +116,7 @@ def circuit_of(p, variant):
     assert ckt.num_constants == ckt.num_selectors + int(p["num_constants"]) or ckt.num_constants == int(p["num_constants"]), "constants = selectors + gate constants"
     ckt.public_inputs = u64(p["public_inputs"])
     ckt.pi_hash = O.hash_n_to_m_no_pad(ckt.public_inputs, 4, variant)
-    ckt.pi_row = None
     ckt.gate_array = (mp2.Gate * len(gates))(*gates)
-    ckt.luts, ckt.num_lookup_selectors, ckt.num_lookup_polys = [], 0, 0
-    ckt.domain_separator = []
     return ckt
 
 
