@@ -107,19 +107,23 @@ static gl2_t eval_ext_poly(const gl2_t* coeffs, size_t n, gl2_t z) {
 // Flat proof sizes (u64 words). Layout:
 //   caps[n_layers][2^cap][4] | queries[num_queries]{ per oracle: leaf[w] sib[(lg-cap)][4] ;
 //   per layer i: evals[2^arity][2] sib[(lg - sum_{j<=i} arity_j - cap)][4] } | final[len][2] | pow
-size_t orc_fri_proof_words(const orc_fri_params* P) {
+// words of one query round (the same for every round; defined for num_queries = 0 too, where the proof has no query section)
+static size_t query_words(const orc_fri_params* P) {
   unsigned lg = P->log_n + P->rate_bits;
-  size_t capw = ((size_t)4) << P->cap_height;
   size_t q = 0;
   for (uint32_t o = 0; o < P->n_oracles; o++) q += P->oracle_w[o] + 4 * (lg - P->cap_height);
   unsigned cur = lg;
-  unsigned deg = P->log_n;
   for (uint32_t i = 0; i < P->n_layers; i++) {
     cur -= P->arity_bits[i];
-    deg -= P->arity_bits[i];
     q += (2u << P->arity_bits[i]) + 4 * (cur - P->cap_height);
   }
-  return P->n_layers * capw + P->num_queries * q + (2ull << deg) + 1;
+  return q;
+}
+size_t orc_fri_proof_words(const orc_fri_params* P) {
+  size_t capw = ((size_t)4) << P->cap_height;
+  unsigned deg = P->log_n;
+  for (uint32_t i = 0; i < P->n_layers; i++) deg -= P->arity_bits[i];
+  return P->n_layers * capw + P->num_queries * query_words(P) + (2ull << deg) + 1;
 }
 static size_t n_lookup(const orc_fri_params* P) { return (size_t)P->zs_count * P->num_lookup_polys; }
 // config.num_challenges: one Z polynomial per challenge round, so zs_count when the oracles are plonky2's; the
@@ -247,11 +251,7 @@ void orc_fri_prove(const orc_fri_params* P, gl_t* const* coeffs, gl_t* const* le
     ext_coset_fft(values, cur_lg, shift);
   }
   size_t final_len = m >> P->rate_bits;
-  size_t qwords = 0;
-  {
-    orc_fri_params Q = *P;
-    qwords = (orc_fri_proof_words(&Q) - P->n_layers * capw - 2 * final_len - 1) / P->num_queries;
-  }
+  size_t qwords = query_words(P);
   gl_t* out_q = proof + P->n_layers * capw;
   gl_t* out_final = out_q + P->num_queries * qwords;
   for (size_t i = 0; i < final_len; i++) { out_final[2 * i] = cf[i].c[0]; out_final[2 * i + 1] = cf[i].c[1]; }
@@ -514,8 +514,7 @@ int orc_pcs_verify(const orc_fri_params* P, const gl_t circuit_digest[4], const 
   unsigned deg = k;
   for (uint32_t li = 0; li < P->n_layers; li++) deg -= P->arity_bits[li];
   size_t final_len = (size_t)1 << deg;
-  size_t total = orc_fri_proof_words(P);
-  size_t qwords = (total - P->n_layers * capw - 2 * final_len - 1) / P->num_queries;
+  size_t qwords = query_words(P);
   const gl_t* pq = proof + P->n_layers * capw;
   const gl_t* pfinal = pq + P->num_queries * qwords;
   orc_ch_observe(&ch, pfinal, 2 * final_len);
@@ -611,7 +610,10 @@ int orc_pcs_verify(const orc_fri_params* P, const gl_t circuit_digest[4], const 
 uint32_t orc_reduction_arity_bits(uint32_t degree_bits, uint32_t rate_bits, uint32_t cap_height,
                                   uint32_t arity_bits, uint32_t final_poly_bits, uint32_t* out) {
   uint32_t n = 0;
-  while (degree_bits > final_poly_bits && degree_bits + rate_bits - arity_bits >= cap_height) {
+  if (arity_bits == 0) return 0;
+  // plonky2 asserts degree_bits >= arity_bits inside the loop, and orc_fri_params holds 8 layers: stop there, as the device's
+  // mp2g_reduction_arity_bits does, instead of wrapping the u32 or writing past out[8]
+  while (degree_bits > final_poly_bits && degree_bits >= arity_bits && degree_bits + rate_bits >= cap_height + arity_bits && n < 8) {
     out[n++] = arity_bits;
     degree_bits -= arity_bits;
   }

@@ -11,6 +11,7 @@ import pytest
 
 import circuits as C
 import oracle as O
+from fri_param_cases import bump, circuit  # shared with the parameter cases
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -35,25 +36,6 @@ def prove_batch(ctx, ckt, batch, variant=0, seed=0x5EED, rand_row=True, wires=No
 
 def oracle_status(ckt, ofp, digest, ph, caps, openings, proof):
     return int(C.verify(ckt, ofp, digest, ph, caps, openings, proof))
-
-
-def bump(a, idx):
-    """v -> v + 1 mod p at flat index idx of array a (in place)"""
-    flat = a.reshape(-1)
-    flat[idx] = np.uint64((int(flat[idx]) + 1) % P)
-
-
-_built = {}
-
-
-def circuit(log_n, kinds_name, seed=3):
-    key = (log_n, kinds_name, seed)
-    if key not in _built:
-        if kinds_name == "LOOKUP":
-            _built[key] = C.build(log_n, C.ALL_KINDS + C.LOOKUP_KINDS, seed, luts=[(t, 100) for t in C.bits_lookup_tables()])
-        else:
-            _built[key] = C.build(log_n, getattr(C, kinds_name), seed)
-    return _built[key]
 
 
 ACCEPT_CASES = [(5, "ALL_KINDS", 0), (5, "ALL_KINDS", 1), (6, "ALL_KINDS", 0), (6, "ALL_KINDS", 1), (12, "ALL_KINDS", 0), (12, "ALL_KINDS", 1),
