@@ -266,6 +266,42 @@ GLHD u64 gl_mulw(u64 a, u64 b) {
   gl_mul_wide(a, b, lo, hi);
   return gl_reduce128w(lo, hi);
 }
+// gl_mulw for the S-boxes of the permutations (poseidon.cuh): the same 128-bit product, hence the same result for every input, with the
+// four multiply-adds spelled out. The two middle products share ONE accumulator, and the bit it can carry past 64 is the third
+// multiply-add's own carry-out. With a = a0 + 2^32 a1, b = b0 + 2^32 b1, M = 2^32 - 1:
+//   P  = a0 b0                     <= M^2             = 2^64 - 2^33 + 1
+//   m1 = a0 b1 + (P >> 32)         <= M^2 + M - 1     = 2^64 - 2^32 - 1         (P >> 32 <= M - 1): fits 64 bits
+//   m2 = a1 b0 + m1 = q + 2^64 k   <= 2 M^2 + M - 1   < 2^65: k is 0 or 1, the carry that the multiply-add hands over in an SGPR pair
+//   hi = a1 b1 + [q >> 32, k]      <= M^2 + 2 M - 1   = 2^64 - 2: the exact high word of a b <= (2^64 - 1)^2, so it cannot wrap
+//   lo = [lo32(P), lo32(q)]
+// m1 enters the third multiply-add as the whole register pair it was written to, and [q >> 32, k] pairs a word with the 0 / 1 that one
+// v_cndmask makes of the carry: of the addends only P >> 32 is zero-extended. gl_mul_wide, left to hipcc (m2 = a1 b0 + lo32(m1), then
+// hi = a1 b1 + (m1 >> 32) + (m2 >> 32)), zero-extends three more words into aligned pairs and joins the two high words in a 64-bit add of
+// their own: two moves and one v_lshl_add_u64 a product more, one v_cndmask less (profiles/mul_carry). Hazards as in gl_reduce96w: the
+// carry pair is read by the v_cndmask two wait states after the multiply-add that wrote it. The three multiply-adds that cannot carry
+// name VCC as the carry they do not use, as in gl_mulc_addw.
+// Only p2_sbox0 calls it. In gl_mul_wide itself, in gl_mulw and gl_mul_addw, or in the S-box of the gate evaluators the same form takes a
+// wave per SIMD from gate kernels (gate_constraints_lde_kernel<11> 90 -> 107 VGPRs, <18> 74 -> 98, gate_check_kernel 230 -> 260) and, in
+// gl_mul_wide, adds scratch to NTT kernels (profiles/mul_carry lists every scope).
+GLHD u64 gl_mulw_k(u64 a, u64 b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  const u32 a0 = (u32)a, a1 = (u32)(a >> 32), b0 = (u32)b, b1 = (u32)(b >> 32);
+  u64 p, m1, q, hi, k;
+  u32 kw;
+#define GL_MADV_(r, x, y, z) asm volatile("v_mad_u64_u32 %0, vcc, %1, %2, %3" : "=&v"(r) : "v"(x), "v"(y), "v"((u64)(z)) : "vcc")
+  asm volatile("v_mad_u64_u32 %0, vcc, %1, %2, 0" : "=&v"(p) : "v"(a0), "v"(b0) : "vcc");
+  GL_MADV_(m1, a0, b1, p >> 32);
+  asm volatile("v_mad_u64_u32 %0, %1, %3, %4, %5\n\t"
+               "s_nop 1\n\t"  // 2 wait states between the mad's SGPR carry and its first VALU reader
+               "v_cndmask_b32 %2, 0, 1, %1"
+               : "=&v"(q), "=&s"(k), "=&v"(kw) : "v"(a1), "v"(b0), "v"(m1));
+  GL_MADV_(hi, a1, b1, gl_mk((u32)(q >> 32), kw));
+#undef GL_MADV_
+  return gl_reduce128w(gl_mk((u32)p, (u32)q), hi);
+#else
+  return gl_mulw(a, b);
+#endif
+}
 
 // ---- sums of products without carry chains ------------------------------------------------------------------------------
 // sum_k a_k b_k as four 64-bit columns of 32-bit words: on gfx950 a 64-bit add without carry-out costs 1.6 issue slots, an

@@ -52,7 +52,8 @@ static_assert(POSEIDON2_DIAG_NARROW == 0xcfeu, "limbs 0, 8 and 9 take gl_mulc_ad
 // State limbs are arbitrary u64 representatives between rounds (gl.cuh "weak"); outputs are
 // canonicalised once at the end. Linear layers run on the 32-bit halves of the limbs in plain
 // 64-bit arithmetic (all weights are small) and reduce once per output limb.
-// x <- (x + rc)^7 ; x any u64, rc canonical
+// x <- (x + rc)^7 ; x any u64, rc canonical. For the gate evaluators and the lane-cooperative permutation: products in the order hipcc
+// chooses (gl_mulw_k here costs gate_check_kernel and the Poseidon gate's kernel a wave per SIMD)
 GLHD u64 p2_sbox(u64 x, u64 rc) {
   u64 t = gl_addw(x, rc);
   u64 t2 = gl_mulw(t, t), t4 = gl_mulw(t2, t2), t3 = gl_mulw(t, t2);
@@ -113,10 +114,11 @@ GLHD void p2_external_rc(u64 s[12], const u64* rc) {
 #endif
 }
 GLHD void p2_external(u64 s[12]) { p2_external_rc<false>(s, nullptr); }
-// x^7 for a limb whose round constant is already in (p2_external_rc)
+// x^7 for a limb whose round constant is already in (p2_external_rc). The S-box of the sponge, tree and proof-of-work kernels: its four
+// products take their middle column's carry from the multiply-add (gl_mulw_k; the permutation 3.09 -> 3.19 G perm/s: profiles/mul_carry)
 GLHD u64 p2_sbox0(u64 t) {
-  u64 t2 = gl_mulw(t, t), t4 = gl_mulw(t2, t2), t3 = gl_mulw(t, t2);
-  return gl_mulw(t3, t4);
+  u64 t2 = gl_mulw_k(t, t), t4 = gl_mulw_k(t2, t2), t3 = gl_mulw_k(t, t2);
+  return gl_mulw_k(t3, t4);
 }
 // d_i a + c for limb i of the internal layer's diagonal, as some u64 representative (a, c: any u64; i a constant after unrolling). d_i is
 // known when the library is built, so the product takes gl_mulc_addw and its 96-bit tail: without the carry for the nine limbs whose
@@ -175,7 +177,7 @@ GLHD void poseidon2_perm(u64 s[12]) {
   // the 22 internal rounds in two unrolled halves: 2.79 -> 2.84 G perm/s against no unrolling (tools/ubench; 4: 2.82, 22: 2.82)
 #pragma unroll 11
   for (int r = 0; r < 22; r++) {
-    s[0] = p2_sbox(s[0], c_p2_int[r]);
+    s[0] = p2_sbox0(gl_addw(s[0], c_p2_int[r]));  // p2_sbox's operations, with p2_sbox0's product
     p2_internal(s);
   }
 #pragma unroll

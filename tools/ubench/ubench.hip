@@ -123,6 +123,37 @@ GLD void poseidon2_perm_general(u64 s[12]) {
   for (int i = 0; i < 12; i++) s[i] = gl_canon(s[i]);
 }
 
+// the permutation as it was before gl_mulw_k: the S-boxes' products in the form hipcc gives gl_mul_wide (the A side of the `plain` /
+// `carry` rows; profiles/mul_carry)
+GLD u64 p2_sbox0_plain(u64 t) {
+  u64 t2 = gl_mulw(t, t), t4 = gl_mulw(t2, t2), t3 = gl_mulw(t, t2);
+  return gl_mulw(t3, t4);
+}
+GLD void poseidon2_perm_plain(u64 s[12]) {
+  p2_external_rc<true>(s, c_p2_ext);
+#pragma unroll 1
+  for (int r = 0; r < 4; r++) {
+#pragma unroll
+    for (int i = 0; i < 12; i++) s[i] = p2_sbox0_plain(s[i]);
+    if (r < 3) p2_external_rc<true>(s, c_p2_ext + 12 * (r + 1)); else p2_external(s);
+  }
+#pragma unroll 11
+  for (int r = 0; r < 22; r++) {
+    s[0] = p2_sbox0_plain(gl_addw(s[0], c_p2_int[r]));
+    p2_internal(s);
+  }
+#pragma unroll
+  for (int i = 0; i < 12; i++) s[i] = gl_addw(s[i], c_p2_ext[48 + i]);
+#pragma unroll 1
+  for (int r = 4; r < 8; r++) {
+#pragma unroll
+    for (int i = 0; i < 12; i++) s[i] = p2_sbox0_plain(s[i]);
+    if (r < 7) p2_external_rc<true>(s, c_p2_ext + 12 * (r + 1)); else p2_external(s);
+  }
+#pragma unroll
+  for (int i = 0; i < 12; i++) s[i] = gl_canon(s[i]);
+}
+
 template <int OP>
 __global__ void __launch_bounds__(256) k(u64* out, u64 seed) {
   u64 a[8];
@@ -162,6 +193,7 @@ __global__ void __launch_bounds__(256) k(u64* out, u64 seed) {
       if (OP == 27) a[i] = gl_mul_addw(a[i], c_p2_diag[1 + i], a[(i + 1) & 7]);                             // limbs 1..8 of the internal layer, general
       if (OP == 29) a[i] = gl_mul_addw(a[i], c_p2_diag[i & 1 ? 8 : 9], a[(i + 1) & 7]);                                                     // wide limbs 8, 9, general
       if (OP == 30) a[i] = gl_mulc_addw<false>(a[i], c_p2_diag[i & 1 ? 8 : 9], c_p2_diag_shl32[i & 1 ? 8 : 9], a[(i + 1) & 7]);               // wide limbs 8, 9, the carry folded in
+      if (OP == 31) a[i] = gl_mulw_k(a[i], a[(i + 1) & 7]);                                                                               // the S-boxes' product: one middle accumulator, its carry from the multiply-add
       if (OP == 28) a[i] = gl_mulc_addw<true>(a[i], c_p2_diag[1 + (i & 3) * 2], c_p2_diag_shl32[1 + (i & 3) * 2], a[(i + 1) & 7]);  // narrow limbs 1, 3, 5, 7
     }
   }
@@ -179,6 +211,12 @@ __global__ void __launch_bounds__(256) kperm_general(u64* out, u64 seed, int rep
   u64 s[12];
   for (int i = 0; i < 12; i++) s[i] = (seed * (threadIdx.x + 1 + i * 977) + blockIdx.x) % GL_P;
   for (int r = 0; r < reps; r++) poseidon2_perm_general(s);
+  out[blockIdx.x * blockDim.x + threadIdx.x] = s[0];
+}
+__global__ void __launch_bounds__(256) kperm_plain(u64* out, u64 seed, int reps) {  // Poseidon2 with hipcc's product in the S-boxes
+  u64 s[12];
+  for (int i = 0; i < 12; i++) s[i] = (seed * (threadIdx.x + 1 + i * 977) + blockIdx.x) % GL_P;
+  for (int r = 0; r < reps; r++) poseidon2_perm_plain(s);
   out[blockIdx.x * blockDim.x + threadIdx.x] = s[0];
 }
 __global__ void __launch_bounds__(256) kperm1(u64* out, u64 seed, int reps) {  // the original Poseidon permutation
@@ -215,6 +253,7 @@ __global__ void kcheck(u64* bad, u64 seed) {
         if (!((POSEIDON2_DIAG_NARROW >> j) & 1)) continue;
         if (gl_canon(gl_mulc_addw<true>(a, c_p2_diag[j], c_p2_diag_shl32[j], cadd)) != gl_canon(red64((u64)pc, (u64)(pc >> 64)))) atomicAdd((unsigned long long*)bad, 1ull);
       }
+      if (gl_canon(gl_mulw_k(a, b)) != want_m || gl_mulw_k(a, b) != gl_mulw(a, b) || gl_mulw_k(lo, hi) != gl_mulw(lo, hi)) atomicAdd((unsigned long long*)bad, 1ull);
       if (gl_canon(gl_mulw(a, b)) != want_m || gl_canon(gl_mul_addw(a, b, cadd)) != want_a || gl_mul(a, b) != want_m) atomicAdd((unsigned long long*)bad, 1ull);
     }
     if (gl_canon(gl_reduce128w(lo, hi)) != want || gl_canon(gl_reduce96w(lo, h32)) != gl_canon(red64(lo, h32)) ||
@@ -285,7 +324,7 @@ int main() {
     u64 h = 1; hipMemcpy(&h, bad, 8, hipMemcpyDeviceToHost);
     printf("asm reduce mismatches: %llu\n", (unsigned long long)h);
   }
-  const char* names[] = {"gl_mul", "v_mad_u64_u32", "add64", "cmp+sel+add64", "mul_lo_u32", "mul_hi_u32", "gl_add", "add32", "gl_mul_small", "add_co+addc", "cmp32+sel", "mulw(64bit)", "mulw(32chain)", "mul_wide", "red(64bit)", "red(32chain)", "gl_sub", "gl_addw", "mulw(asm red)", "red(asm)", "red(asm2)", "red(asm3)", "mulw(asm3)", "mul 2^24", "mul 2^48", "mul 2^72", "gl_canon", "mul_addw(diag)", "mulc_addw<narrow>", "mul_addw(wide d)", "mulc_addw<any>"};
+  const char* names[] = {"gl_mul", "v_mad_u64_u32", "add64", "cmp+sel+add64", "mul_lo_u32", "mul_hi_u32", "gl_add", "add32", "gl_mul_small", "add_co+addc", "cmp32+sel", "mulw(64bit)", "mulw(32chain)", "mul_wide", "red(64bit)", "red(32chain)", "gl_sub", "gl_addw", "mulw(asm red)", "red(asm)", "red(asm2)", "red(asm3)", "mulw(asm3)", "mul 2^24", "mul 2^48", "mul 2^72", "gl_canon", "mul_addw(diag)", "mulc_addw<narrow>", "mul_addw(wide d)", "mulc_addw<any>", "mulw_k(carry)"};
   double ops = (double)blocks * threads * ITERS * 8;
 #define RUN(N) { float ms = timeit([&] { hipLaunchKernelGGL(k<N>, dim3(blocks), dim3(threads), 0, 0, d, 0x9E3779B97F4A7C15ull); }); \
     printf("%-14s %8.3f ms  %8.2f Gop/s (lane-ops)\n", names[N], ms, ops / ms / 1e6); }
@@ -296,7 +335,7 @@ int main() {
 #define RUN(N) { float ms = timeit([&] { hipLaunchKernelGGL(k<N>, dim3(blocks), dim3(threads), 0, 0, d, 0x9E3779B97F4A7C15ull); }); \
     hipError_t e_ = hipGetLastError(); \
     printf("%-14s %8.3f ms  %8.2f Gop/s (lane-ops)  %5.1f slots%s\n", names[N], ms, ops / ms / 1e6, ms / add32_ms, e_ == hipSuccess ? "" : "  LAUNCH FAILED"); }
-  RUN(0) RUN(1) RUN(2) RUN(3) RUN(4) RUN(5) RUN(6) RUN(7) RUN(8) RUN(9) RUN(10) RUN(11) RUN(12) RUN(13) RUN(14) RUN(15) RUN(16) RUN(17) RUN(18) RUN(19) RUN(23) RUN(24) RUN(25) RUN(26) RUN(27) RUN(28) RUN(29) RUN(30)
+  RUN(0) RUN(1) RUN(2) RUN(3) RUN(4) RUN(5) RUN(6) RUN(7) RUN(8) RUN(9) RUN(10) RUN(11) RUN(12) RUN(13) RUN(14) RUN(15) RUN(16) RUN(17) RUN(18) RUN(19) RUN(23) RUN(24) RUN(25) RUN(26) RUN(27) RUN(28) RUN(29) RUN(30) RUN(12) RUN(31)
   {
     const char* inames[] = {"v_mov_b32", "v_lshl_add_u64", "v_mad_u64_u32(asm)", "v_cndmask_b32(sgpr)", "sub_co+subbrev+subb(+xor)", "v_sub_u32", "v_bitop3_b32", "v_add_u32",
                             "v_xor_b32", "mad acc+=zext(w)", "mov,mov,lshl_add acc+=zext(w)", "v_cndmask_b32_e64 vcc", "v_cndmask_b32_e32 vcc", "v_cndmask 0,-1,sgpr",
@@ -323,6 +362,18 @@ int main() {
     size_t diff = 0;
     for (size_t i = 0; i < ha.size(); i++) diff += ha[i] != hb[i];
     printf("poseidon2_perm general vs mulc: %zu of %zu outputs differ\n", diff, ha.size());
+    // the S-boxes' product both ways, three repeats each in turn (profiles/mul_carry)
+    diff = 0;
+    for (int rep = 0; rep < 3; rep++) {
+      ms = timeit([&] { hipLaunchKernelGGL(kperm_plain, dim3(blocks), dim3(threads), 0, 0, d, 0x9E3779B97F4A7C15ull, reps); });
+      printf("poseidon2_perm plain,   repeat %d %8.3f ms  %8.3f Gperm/s\n", rep, ms, (double)blocks * threads * reps / ms / 1e6);
+      hipMemcpy(ha.data(), d, ha.size() * sizeof(u64), hipMemcpyDeviceToHost);
+      ms = timeit([&] { hipLaunchKernelGGL(kperm, dim3(blocks), dim3(threads), 0, 0, d, 0x9E3779B97F4A7C15ull, reps); });
+      printf("poseidon2_perm carry,   repeat %d %8.3f ms  %8.3f Gperm/s\n", rep, ms, (double)blocks * threads * reps / ms / 1e6);
+      hipMemcpy(hb.data(), d, hb.size() * sizeof(u64), hipMemcpyDeviceToHost);
+      for (size_t i = 0; i < ha.size(); i++) diff += ha[i] != hb[i];
+    }
+    printf("poseidon2_perm plain vs carry: %zu of %zu outputs differ over the three repeats\n", diff, 3 * ha.size());
     ms = timeit([&] { hipLaunchKernelGGL(kperm1, dim3(blocks), dim3(threads), 0, 0, d, 0x9E3779B97F4A7C15ull, reps); });
     printf("poseidon_perm  %8.3f ms  %8.3f Gperm/s\n", ms, (double)blocks * threads * reps / ms / 1e6);
   }
