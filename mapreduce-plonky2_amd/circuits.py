@@ -432,6 +432,9 @@ def selector_polynomials(gates, instances, max_degree=MAX_DEGREE + 1):
         size = 0
         while start + size < num_gates and size + degs[start + size] < max_degree:
             size += 1
+        # a gate whose own degree reaches max_degree (ComparisonGate with 4-bit chunks or wider) fits no group: it takes one
+        # alone. Such a circuit has a witness and gate constraints, but no proof under this quotient degree factor.
+        size = max(size, 1)
         groups.append((start, start + size))
         start += size
     sel_idx = [next(j for j, (a, b) in enumerate(groups) if a <= i < b) for i in range(num_gates)]
