@@ -855,7 +855,8 @@ void mp2g_chain_free(mp2g_chain* chain);
  * mp2g_forest_prove: units[u] = unit_nodes[unit_offsets[u] .. unit_offsets[u+1]) are proved by the workers in parallel, each unit
  * level by level (levels counted inside the unit), every level's nodes of one circuit in batches of the chain's capacity. The units
  * of ONE call must not depend on each other (the items of one wave of an update plan do not); children outside a unit must have
- * been proved by an earlier call. A witness that violates a constraint fails the call as plonky2's prove() panics. */
+ * been proved by an earlier call or put into the pool by mp2g_forest_put_proofs (below: a stored proof as a child). A witness that
+ * violates a constraint fails the call as plonky2's prove() panics. */
 typedef struct mp2g_forest mp2g_forest;
 typedef struct {
   uint32_t n_inputs;         /* witness inputs of the base circuit (chain step 0), in words */
@@ -899,6 +900,29 @@ int mp2g_forest_release(mp2g_forest* f, uint64_t id);
  * created on the forest's first context with n_public_inputs = the node's public inputs): status [n_ids], host. An id that is
  * unknown, not proved or already released fails the call before anything is verified; no status is written then. */
 int mp2g_forest_verify(mp2g_forest* f, mp2g_verifier* v, const uint64_t* ids, uint32_t n_ids, uint32_t* status);
+/* Stored proofs as children: what the reference's harness does for every block after the first, where it proves the touched nodes
+ * of an UpdateTree only and takes each untouched sibling out of its proof store (get_proof_exact; celltree.rs:77-152,
+ * rowtree.rs:78-337 over ryhope/src/lib.rs:179-222 touched()). put_proofs registers `count` EXTERNAL nodes: no circuit, no
+ * children, no constant words in this forest, only a proof -- n_words[i] words at words + i * stride (host), in a parent's input
+ * order, i.e. what mp2g_forest_proof hands out. Each takes one pool slot; the words go up through pinned staging in chunks of at
+ * most mp2g_forest_staging_words() words on the forest's first context, one kernel per chunk scatters them into the slots and in
+ * the same pass checks every word for canonicity (< p). The call synchronises: on return the nodes are PUBLISHED -- usable as
+ * children by any worker, visible to mp2g_forest_proof / _proofs / _device_proof / _verify (the proof itself is NOT verified here:
+ * mp2g_forest_verify with its circuit's verifier does that where it lies) -- and a node's slot returns when its parent is proved
+ * unless keep[i] != 0, or on mp2g_forest_release. Refused, with nothing registered and every slot back: an id the forest knows
+ * (or listed twice); n_words[i] = 0 or > slot_words; stride < n_words[i]; fewer free slots than count (the message says how many
+ * are needed and how many are free); a word >= p (the message names the first such id); a call while mp2g_forest_prove runs (and
+ * mp2g_forest_prove refuses to start while this call runs). A unit that lists an external node is refused like any proved node;
+ * mp2g_forest_proved does not count external nodes. */
+int mp2g_forest_put_proofs(mp2g_forest* f, uint32_t count, const uint64_t* ids, const uint64_t* words /* host, [count][stride] */,
+                           size_t stride, const uint32_t* n_words /* [count] */, const uint8_t* keep /* [count] or NULL */);
+/* mp2g_forest_proof for many published nodes at once: per chunk of at most mp2g_forest_staging_words() words one gather kernel from
+ * the slots into a device staging buffer, one device-to-host copy and one synchronisation. words [n_ids][stride] (host; NULL asks
+ * for the lengths only) and n_words [n_ids] receive what mp2g_forest_proof returns for each id. An id that is unknown, not proved
+ * or already released -- or a proof longer than stride -- fails the call before anything is written. */
+int mp2g_forest_proofs(mp2g_forest* f, const uint64_t* ids, uint32_t n_ids, uint64_t* words /* host, [n_ids][stride] */, size_t stride,
+                       uint32_t* n_words /* [n_ids] */);
+uint32_t mp2g_forest_staging_words(void);
 uint64_t mp2g_forest_proved(const mp2g_forest* f);
 uint32_t mp2g_forest_free_slots(mp2g_forest* f);
 void mp2g_forest_free(mp2g_forest* f);

@@ -780,6 +780,11 @@ class ProofChain:
             pass
 
 
+def forest_staging_words():
+    """mp2g_forest_staging_words: the most words Forest.put_proofs / Forest.proofs move per chunk (one kernel and one synchronisation each)"""
+    return int(load().mp2g_forest_staging_words())
+
+
 class ForestCircuit(ctypes.Structure):
     _fields_ = [("n_inputs", ctypes.c_uint32), ("n_children", ctypes.c_uint32), ("child_offset", ctypes.c_uint32 * 4), ("n_const", ctypes.c_uint32)]
 
@@ -850,6 +855,41 @@ class Forest:
 
     def release(self, node_id):
         _ck(load().mp2g_forest_release(self.h, int(node_id)))
+
+    def put_proofs(self, ids, proofs, keep=None):
+        """mp2g_forest_put_proofs: register the external nodes `ids` with their proofs -- word arrays in a parent's input order (what
+        proof_words returns), one per id or one [count][words] array -- in pool slots of their own; published on return. Raises, with
+        nothing registered, on a known id, an empty or oversized proof, a full pool, a non-canonical word or a running prove()."""
+        ids = _arr(ids).ravel()
+        rows = [_arr(p).ravel() for p in proofs]
+        if len(rows) != ids.size:
+            raise Mp2gError(f"put_proofs: {ids.size} ids, {len(rows)} proofs")
+        n_words = _arr([r.size for r in rows], np.uint32)
+        stride = max([r.size for r in rows] + [1])
+        words = np.zeros((ids.size, stride), dtype=np.uint64)
+        for i, r in enumerate(rows):
+            words[i, :r.size] = r
+        kp = np.ascontiguousarray(keep, dtype=np.uint8) if keep is not None else None
+        if kp is not None and kp.size != ids.size:
+            raise Mp2gError(f"put_proofs: {ids.size} ids, {kp.size} keep flags")
+        _ck(load().mp2g_forest_put_proofs(self.h, int(ids.size), _p(ids), _p(words), stride, _p(n_words), _p(kp) if kp is not None else None))
+
+    def proofs(self, ids):
+        """mp2g_forest_proofs: [proof_words(i) for i in ids] in one call (a gather kernel, a copy and a synchronisation per staging chunk
+        instead of one of each per proof). Raises before anything is downloaded when an id is unknown, unproved or released."""
+        ids = _arr(ids).ravel()
+        if not ids.size:
+            return []
+        n_words = np.zeros(ids.size, dtype=np.uint32)
+        _ck(load().mp2g_forest_proofs(self.h, _p(ids), int(ids.size), None, 0, _p(n_words)))
+        stride = int(n_words.max())
+        words = np.empty((ids.size, stride), dtype=np.uint64)
+        _ck(load().mp2g_forest_proofs(self.h, _p(ids), int(ids.size), _p(words), stride, _p(n_words)))
+        return [words[i, :int(n)].copy() for i, n in enumerate(n_words)]
+
+    @property
+    def free_slots(self):
+        return int(load().mp2g_forest_free_slots(self.h))
 
     @property
     def proved(self):

@@ -10,7 +10,13 @@
 // several subtrees' levels merge), each level's nodes of one circuit in batches of the chains' capacity. Final proofs live in a device
 // pool (one fixed-size slot each: public inputs, the three proof caps, openings, FRI words -- the order a parent's witness inputs take
 // them in); a parent's inputs receive its children's slots by one gather kernel, a batch's outputs reach their slots by another, and a
-// slot is returned when the parent is proved. No proof visits the host unless it is asked for (mp2g_forest_proof).
+// slot is returned when the parent is proved. No proof visits the host unless it is asked for (mp2g_forest_proof, mp2g_forest_proofs).
+//
+// A block after the first changes a few rows: the reference's harness then proves the touched nodes only and takes every untouched
+// sibling out of its proof store (celltree.rs:77-152, rowtree.rs:78-337 over ryhope's touched(); get_proof_exact). Such a sibling
+// enters the pool as an EXTERNAL node (mp2g_forest_put_proofs): no circuit, no children, no constants -- only its proof words, in
+// the order a parent's inputs take them, scattered from a staging buffer into a slot by one kernel that also checks every word
+// for canonicity. From there it is a published node like any other.
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -44,6 +50,7 @@ struct Node {
   int32_t slot = -1;        // pool slot of the proof, -1 = not proved (or released)
   uint32_t proof_words = 0; // words of the proof in its slot
   bool keep = false;        // the slot survives the parent (a checker downloads the proof later)
+  bool external = false;    // put there by mp2g_forest_put_proofs: published from the start, never part of a unit, not counted as proved here
   bool proved = false;      // PUBLISHED: the device has written the slot and the witness check of its batch passed (set in confirm_oldest)
   uint32_t queued_by = 0;   // worker + 1 of the unit whose stream holds the node's batch, queued and not yet confirmed; 0 = none
 };
@@ -56,6 +63,48 @@ struct Copy { const u64* src; u64* dst; uint32_t n; uint32_t pad; };
 __global__ void __launch_bounds__(256) forest_copy_kernel(const Copy* jobs) {
   const Copy c = jobs[blockIdx.x];
   for (uint32_t i = threadIdx.x; i < c.n; i += 256) c.dst[i] = c.src[i];
+}
+
+// mp2g_forest_put_proofs / mp2g_forest_proofs move proofs between host words and pool slots through a staging buffer in chunks of at
+// most STAGING_WORDS words (a proof starts at an even word: 16-byte aligned) and STAGING_JOBS proofs.
+constexpr uint32_t STAGING_WORDS = 1u << 18;  // 2 MiB: 16 proofs of the table circuits' ~15k words
+constexpr uint32_t STAGING_JOBS = 4096;
+// One workgroup per job moves words [src, src + n) -> [dst, dst + n): 16 bytes per lane where both ends are 16-byte aligned (a slot
+// is when slot_words is even or the slot's number is), the odd last word and every word of an unaligned job as 8 bytes.
+// CHECK (the way INTO the pool): every word must be canonical (< p); the lanes' verdicts meet in a wave vote, the four waves' in
+// LDS, and lane 0 stores the job's flag.
+template <bool CHECK>
+__global__ void __launch_bounds__(256) forest_stage_kernel(const Copy* jobs, uint32_t* flags) {
+  const Copy c = jobs[blockIdx.x];
+  uint32_t bad = 0;
+  if (((((uintptr_t)c.src) | ((uintptr_t)c.dst)) & 15) == 0) {
+    const ulonglong2* s = (const ulonglong2*)c.src;
+    ulonglong2* d = (ulonglong2*)c.dst;
+    const uint32_t pairs = c.n >> 1;
+    for (uint32_t i = threadIdx.x; i < pairs; i += 256) {
+      const ulonglong2 v = s[i];
+      if (CHECK) bad |= (uint32_t)(v.x >= GL_P) | (uint32_t)(v.y >= GL_P);
+      d[i] = v;
+    }
+    if ((c.n & 1) && threadIdx.x == 0) {
+      const u64 v = c.src[c.n - 1];
+      if (CHECK) bad |= (uint32_t)(v >= GL_P);
+      c.dst[c.n - 1] = v;
+    }
+  } else {
+    for (uint32_t i = threadIdx.x; i < c.n; i += 256) {
+      const u64 v = c.src[i];
+      if (CHECK) bad |= (uint32_t)(v >= GL_P);
+      c.dst[i] = v;
+    }
+  }
+  if (CHECK) {
+    __shared__ uint32_t wave_bad[4];
+    const uint32_t any = __any((int)bad) ? 1u : 0u;
+    if ((threadIdx.x & 63) == 0) wave_bad[threadIdx.x >> 6] = any;
+    __syncthreads();
+    if (threadIdx.x == 0) flags[blockIdx.x] = wave_bad[0] | wave_bad[1] | wave_bad[2] | wave_bad[3];
+  }
 }
 }  // namespace
 
@@ -80,7 +129,23 @@ struct mp2g_forest {
   struct Slot { Copy* h_jobs = nullptr; Copy* d_jobs = nullptr; uint32_t* h_flags = nullptr; hipEvent_t done = nullptr; };
   struct Worker { Slot ring[RING]; uint32_t cap_jobs = 0; uint32_t seq = 0; };
   std::vector<Worker> workers;
+  // the staging of mp2g_forest_put_proofs / mp2g_forest_proofs, made on first use (a forest that never imports or downloads in bulk
+  // holds none): pinned words, their device twin, the copy jobs and the canonicity flags of one chunk. One call at a time (stage_mu);
+  // the kernels run on the first context's stream.
+  struct Staging {
+    u64* h_words = nullptr; u64* d_words = nullptr; Copy* h_jobs = nullptr; Copy* d_jobs = nullptr;
+    uint32_t* h_flags = nullptr; uint32_t* d_flags = nullptr; size_t cap_words = 0;
+  } stage;
+  std::mutex stage_mu;
+  uint32_t proving = 0;    // mp2g_forest_prove calls inside (under mu): the node index must not grow beneath the workers
+  bool importing = false;  // a mp2g_forest_put_proofs call holds slots it has not registered yet (under mu)
   ~mp2g_forest() {
+    if (stage.h_words) (void)hipHostFree(stage.h_words);
+    if (stage.d_words) (void)hipFree(stage.d_words);
+    if (stage.h_jobs) (void)hipHostFree(stage.h_jobs);
+    if (stage.d_jobs) (void)hipFree(stage.d_jobs);
+    if (stage.h_flags) (void)hipHostFree(stage.h_flags);
+    if (stage.d_flags) (void)hipFree(stage.d_flags);
     for (auto& w : workers)
       for (auto& r : w.ring) {
         if (r.h_jobs) (void)hipHostFree(r.h_jobs);
@@ -418,6 +483,12 @@ int mp2g_forest_add_nodes(mp2g_forest* f, uint32_t circuit, uint32_t count, cons
 int mp2g_forest_prove(mp2g_forest* f, const uint64_t* unit_nodes, const uint32_t* unit_offsets, uint32_t n_units) {
   NEED(f && (n_units == 0 || (unit_nodes && unit_offsets)), "forest / units");
   if (!n_units) return 0;
+  {
+    std::lock_guard<std::mutex> g(f->mu);
+    if (f->importing) return fail("forest: mp2g_forest_prove while mp2g_forest_put_proofs is running");
+    f->proving++;
+  }
+  struct Proving { mp2g_forest* f; ~Proving() { std::lock_guard<std::mutex> g(f->mu); f->proving--; } } proving_guard{f};
   std::atomic<uint32_t> next{0};
   std::atomic<int> failed{0};
   std::mutex err_mu;
@@ -613,6 +684,174 @@ int mp2g_forest_verify(mp2g_forest* f, mp2g_verifier* v, const uint64_t* ids, ui
   }
   CK(hipSetDevice(f->ctxs[0]->device));
   return verifier_verify_gathered(v, srcs.data(), n_ids, status);
+}
+
+}  // extern "C"
+
+namespace {
+// the staging buffers, on first use; every chunk holds at least one proof of slot_words words
+int stage_ready(mp2g_forest* f) {
+  mp2g_forest::Staging& S = f->stage;
+  if (S.cap_words) return 0;
+  const size_t cap = std::max<size_t>(STAGING_WORDS, ((size_t)f->slot_words + 1) & ~(size_t)1);
+  CK(hipSetDevice(f->ctxs[0]->device));
+  if (!S.h_words) CK(hipHostMalloc((void**)&S.h_words, cap * sizeof(u64), hipHostMallocDefault));
+  if (!S.d_words) CK(hipMalloc((void**)&S.d_words, cap * sizeof(u64)));
+  if (!S.h_jobs) CK(hipHostMalloc((void**)&S.h_jobs, (size_t)STAGING_JOBS * sizeof(Copy), hipHostMallocDefault));
+  if (!S.d_jobs) CK(hipMalloc((void**)&S.d_jobs, (size_t)STAGING_JOBS * sizeof(Copy)));
+  if (!S.h_flags) CK(hipHostMalloc((void**)&S.h_flags, (size_t)STAGING_JOBS * sizeof(uint32_t), hipHostMallocDefault));
+  if (!S.d_flags) CK(hipMalloc((void**)&S.d_flags, (size_t)STAGING_JOBS * sizeof(uint32_t)));
+  S.cap_words = cap;
+  return 0;
+}
+// the chunk that starts at proof lo: proofs [lo, hi) at the even staging offsets off[i - lo]; returns hi and the words the chunk takes
+uint32_t stage_chunk(const mp2g_forest* f, const uint32_t* n_words, uint32_t lo, uint32_t count, std::vector<size_t>& off, size_t* total) {
+  off.clear();
+  size_t at = 0;
+  uint32_t hi = lo;
+  while (hi < count && hi - lo < STAGING_JOBS) {
+    const size_t padded = ((size_t)n_words[hi] + 1) & ~(size_t)1;
+    if (at + padded > f->stage.cap_words) break;
+    off.push_back(at);
+    at += padded;
+    hi++;
+  }
+  *total = at;
+  return hi;
+}
+// the chunks of mp2g_forest_put_proofs, with the slots already taken: 0, or the error (the caller returns the slots)
+int put_chunks(mp2g_forest* f, uint32_t count, const uint64_t* ids, const uint64_t* words, size_t stride, const uint32_t* n_words,
+               const std::vector<int32_t>& slots) {
+  { const int rc = stage_ready(f); if (rc) return rc; }
+  mp2g_forest::Staging& S = f->stage;
+  CK(hipSetDevice(f->ctxs[0]->device));
+  hipStream_t stream = f->ctxs[0]->stream;
+  std::vector<size_t> off;
+  for (uint32_t lo = 0; lo < count;) {
+    size_t total = 0;
+    const uint32_t hi = stage_chunk(f, n_words, lo, count, off, &total);
+    if (hi == lo) return fail("forest: internal: a proof does not fit the staging buffer");
+    for (uint32_t i = lo; i < hi; i++) {
+      memcpy(S.h_words + off[i - lo], words + (size_t)i * stride, (size_t)n_words[i] * sizeof(u64));
+      S.h_jobs[i - lo] = Copy{S.d_words + off[i - lo], f->pool.p + (size_t)slots[i] * f->slot_words, n_words[i], 0};
+    }
+    const uint32_t n = hi - lo;
+    CK(hipMemcpyAsync(S.d_words, S.h_words, total * sizeof(u64), hipMemcpyHostToDevice, stream));
+    CK(hipMemcpyAsync(S.d_jobs, S.h_jobs, (size_t)n * sizeof(Copy), hipMemcpyHostToDevice, stream));
+    hipLaunchKernelGGL(forest_stage_kernel<true>, dim3(n), dim3(256), 0, stream, (const Copy*)S.d_jobs, S.d_flags);
+    CK(hipGetLastError());
+    CK(hipMemcpyAsync(S.h_flags, S.d_flags, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    CK(hipStreamSynchronize(stream));
+    for (uint32_t i = 0; i < n; i++)
+      if (S.h_flags[i]) return fail("forest: the proof of external node %llu holds a word that is not canonical (>= p)", (unsigned long long)ids[lo + i]);
+    lo = hi;
+  }
+  return 0;
+}
+}  // namespace
+
+extern "C" {
+uint32_t mp2g_forest_staging_words(void) { return STAGING_WORDS; }
+
+int mp2g_forest_put_proofs(mp2g_forest* f, uint32_t count, const uint64_t* ids, const uint64_t* words, size_t stride, const uint32_t* n_words,
+                           const uint8_t* keep) {
+  NEED(f && (!count || (ids && words && n_words)), "forest / ids / words / lengths");
+  if (!count) return 0;
+  try {
+    std::lock_guard<std::mutex> sg(f->stage_mu);
+    std::vector<int32_t> slots(count);
+    {
+      std::lock_guard<std::mutex> g(f->mu);
+      if (f->proving) return fail("forest: mp2g_forest_put_proofs while mp2g_forest_prove is running");
+      std::unordered_map<uint64_t, uint32_t> seen;
+      seen.reserve(count);
+      for (uint32_t i = 0; i < count; i++) {
+        if (f->index.count(ids[i]) || !seen.emplace(ids[i], i).second) return fail("forest: node %llu registered twice", (unsigned long long)ids[i]);
+        if (!n_words[i] || n_words[i] > f->slot_words)
+          return fail("forest: the proof of external node %llu has %u words, a pool slot 1 .. %u", (unsigned long long)ids[i], n_words[i], f->slot_words);
+        if (stride < n_words[i]) return fail("forest: the proof of external node %llu has %u words, the rows of `words` %zu", (unsigned long long)ids[i], n_words[i], stride);
+      }
+      if (f->free_slots.size() < count)
+        return fail("forest: %u external proofs need %u pool slots, %zu are free: release roots or create a larger pool", count, count, f->free_slots.size());
+      for (uint32_t i = 0; i < count; i++) { slots[i] = f->free_slots.back(); f->free_slots.pop_back(); }
+      f->importing = true;
+    }
+    int rc = 1;
+    std::string msg = "out of memory";
+    try {
+      rc = put_chunks(f, count, ids, words, stride, n_words, slots);
+      if (rc) msg = mp2g_last_error();
+    } catch (...) {
+    }
+    std::lock_guard<std::mutex> g(f->mu);
+    f->importing = false;
+    if (!rc) {
+      try {
+        f->nodes.reserve(f->nodes.size() + count);
+        f->index.reserve(f->index.size() + count);
+      } catch (...) {
+        rc = 1;
+      }
+    }
+    if (rc) {  // nothing registered, every slot back
+      for (int32_t sl : slots) f->free_slots.push_back(sl);
+      return fail("%s", msg.c_str());
+    }
+    for (uint32_t i = 0; i < count; i++) {
+      Node n;
+      n.id = ids[i]; n.circuit = ~0u; n.slot = slots[i]; n.proof_words = n_words[i];
+      n.keep = keep && keep[i];
+      n.external = true; n.proved = true;  // published: the slot is written, the stream drained
+      f->index.emplace(n.id, (uint32_t)f->nodes.size());
+      f->nodes.push_back(n);
+    }
+    return 0;
+  } catch (const std::bad_alloc&) { return fail("out of memory"); } catch (...) { return fail("internal error"); }
+}
+
+int mp2g_forest_proofs(mp2g_forest* f, const uint64_t* ids, uint32_t n_ids, uint64_t* words, size_t stride, uint32_t* n_words) {
+  NEED(f && n_words && (ids || !n_ids), "forest / ids / lengths");
+  if (!n_ids) return 0;
+  try {
+    std::lock_guard<std::mutex> sg(f->stage_mu);
+    std::vector<const u64*> srcs(n_ids);
+    std::vector<uint32_t> len(n_ids);
+    {
+      std::lock_guard<std::mutex> g(f->mu);
+      for (uint32_t i = 0; i < n_ids; i++) {
+        auto it = f->index.find(ids[i]);
+        if (it == f->index.end()) return fail("forest: unknown node %llu", (unsigned long long)ids[i]);
+        const Node& nd = f->nodes[it->second];
+        if (!nd.proved || nd.slot < 0) return fail("forest: node %llu is not proved (or its proof was released)", (unsigned long long)ids[i]);
+        if (words && stride < nd.proof_words)
+          return fail("forest: the proof of node %llu has %u words, the rows of `words` %zu", (unsigned long long)ids[i], nd.proof_words, stride);
+        srcs[i] = f->pool.p + (size_t)nd.slot * f->slot_words;
+        len[i] = nd.proof_words;
+      }
+    }
+    if (words) {
+      { const int rc = stage_ready(f); if (rc) return rc; }
+      mp2g_forest::Staging& S = f->stage;
+      CK(hipSetDevice(f->ctxs[0]->device));
+      hipStream_t stream = f->ctxs[0]->stream;
+      std::vector<size_t> off;
+      for (uint32_t lo = 0; lo < n_ids;) {
+        size_t total = 0;
+        const uint32_t hi = stage_chunk(f, len.data(), lo, n_ids, off, &total);
+        if (hi == lo) return fail("forest: internal: a proof does not fit the staging buffer");
+        for (uint32_t i = lo; i < hi; i++) S.h_jobs[i - lo] = Copy{srcs[i], S.d_words + off[i - lo], len[i], 0};
+        CK(hipMemcpyAsync(S.d_jobs, S.h_jobs, (size_t)(hi - lo) * sizeof(Copy), hipMemcpyHostToDevice, stream));
+        hipLaunchKernelGGL(forest_stage_kernel<false>, dim3(hi - lo), dim3(256), 0, stream, (const Copy*)S.d_jobs, (uint32_t*)nullptr);
+        CK(hipGetLastError());
+        CK(hipMemcpyAsync(S.h_words, S.d_words, total * sizeof(u64), hipMemcpyDeviceToHost, stream));
+        CK(hipStreamSynchronize(stream));
+        for (uint32_t i = lo; i < hi; i++) memcpy(words + (size_t)i * stride, S.h_words + off[i - lo], (size_t)len[i] * sizeof(u64));
+        lo = hi;
+      }
+    }
+    for (uint32_t i = 0; i < n_ids; i++) n_words[i] = len[i];
+    return 0;
+  } catch (const std::bad_alloc&) { return fail("out of memory"); } catch (...) { return fail("internal error"); }
 }
 
 uint64_t mp2g_forest_proved(const mp2g_forest* f) { return f ? f->proved.load() : 0; }

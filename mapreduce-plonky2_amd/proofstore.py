@@ -3,7 +3,10 @@
 key-value implementation). The reference keeps every proof of a table build in it so that a later step (a parent node, a later
 block, another process) picks a child up as serialized `ProofWithVK` bytes (mp2-common/src/proof.rs:42-57); here it is what lets a
 table too large for one GPU lease be built block by block across calls -- every block's root goes in as ProofWithVK bytes
-(mp2g_proof_with_vk_serialize), the join levels take them out (mp2g_proof_with_vk_deserialize).
+(mp2g_proof_with_vk_serialize), the join levels take them out (mp2g_proof_with_vk_deserialize). A build that is given a store
+(table.NativeTableBuild.run(store=...)) keeps EVERY node there, under ProofKey.cell / ProofKey.row of the block's primary, and a block
+after the first (NativeTableBuild.update) proves its touched nodes only and takes each untouched sibling out of the store, as the
+reference's harness does with get_proof_exact (mp2-v1/tests/common/celltree.rs:77-152, rowtree.rs:78-337).
 
 A directory of files, not a storage engine: one file per key (header + proof), written to a temporary name and renamed, so a call
 that is cut off leaves either the whole proof with its header or nothing."""

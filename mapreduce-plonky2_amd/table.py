@@ -530,6 +530,55 @@ def expected_root_public_inputs(ctx, table, wit, root, nodes, spans, variant=0):
     return _u64cat(row_h[root], wit.row_digest[root], NEUTRAL_FIELDS, u256_to_limbs([sec[lo]])[0], u256_to_limbs([sec[hi - 1]])[0], [0])
 
 
+# ---- a block after the first: which nodes an update proves again, which it takes from the proof store ----------------------------------
+def cell_node_id(k, c):
+    """forest node ids: the row-tree node of row k = k; the cells-tree node (row k, position c) = (c << 40) | k"""
+    return (int(c) << 40) | int(k)
+
+
+def update_closure(n_cols, nodes, touched_rows, touched_cells):
+    """What the reference's harness derives from the UpdateTrees of a block that changes a few rows (celltree.rs:77-152,
+    rowtree.rs:78-337; ryhope/src/lib.rs:179-222 touched()). nodes: {row: (left, right)} of the row tree AFTER the change;
+    touched_rows: rows that are new (every cell of theirs is proved); touched_cells: {row: positions} (or (row, position) pairs)
+    of the value cells that changed, positions 1..n_cols. Returns
+      cells   {row: sorted positions}: the cells-tree nodes to prove again -- the changed positions and their ancestors up to the
+              cells root (sbbst parents); all positions of a new row;
+      rows    the row-tree nodes to prove again: the touched rows, the rows with touched cells, and every ancestor of either;
+      imports the node ids (cell_node_id) whose stored proofs those proofs take as children: the children of re-proved nodes
+              that are not re-proved themselves, and the cells root of a re-proved row whose cells are untouched.
+    Pure host arithmetic: needs no GPU."""
+    by_row = {}
+    for r, ps in (touched_cells.items() if hasattr(touched_cells, "items") else ((r, [c]) for r, c in touched_cells)):
+        by_row.setdefault(int(r), set()).update(int(c) for c in ps)
+    cells = {int(r): set(range(1, n_cols + 1)) for r in touched_rows}
+    cell_parent = {c: k for k in range(1, n_cols + 1) for c in sbbst_children(n_cols, k) if c is not None}
+    for r, ps in by_row.items():
+        have = cells.setdefault(r, set())
+        for c in ps:
+            if not 1 <= c <= n_cols:
+                raise ValueError(f"update_closure: row {r} has no cell position {c} (1..{n_cols})")
+            while c is not None and c not in have:
+                have.add(c)
+                c = cell_parent.get(c)
+    cells = {r: ps for r, ps in cells.items() if ps}
+    row_parent = {c: k for k, kids in nodes.items() for c in kids if c is not None}
+    rows = set()
+    for r in cells:
+        if r not in nodes:
+            raise KeyError(f"update_closure: row {r} is not a node of the row tree")
+        while r is not None and r not in rows:
+            rows.add(r)
+            r = row_parent.get(r)
+    imports, cells_root = set(), sbbst_root(n_cols)
+    for r, ps in cells.items():
+        imports.update(cell_node_id(r, ch) for c in ps for ch in sbbst_children(n_cols, c) if ch is not None and ch not in ps)
+    for r in rows:
+        imports.update(ch for ch in nodes[r] if ch is not None and ch not in rows)
+        if r not in cells:
+            imports.add(cell_node_id(r, cells_root))
+    return {r: sorted(ps) for r, ps in cells.items()}, rows, imports
+
+
 # ---- the same build with the scheduler in C++ (csrc/forest.hip) -------------------------------------------------------------------------
 class NativeTableBuild:
     """TableBuild with the unit loop in the library: the block's nodes (4 cells-tree nodes and 1 row-tree node per row) are registered
@@ -582,9 +631,7 @@ class NativeTableBuild:
         self.last_session = None
 
     # node ids: row-tree node of row k = k; cells-tree node (row k, position c) = (c << 40) | k
-    @staticmethod
-    def cell_id(k, c):
-        return (int(c) << 40) | int(k)
+    cell_id = staticmethod(lambda k, c: cell_node_id(k, c))
 
     def _child_block(self, fw, name):
         """verifier data and membership proof around a child proof of circuit `name` of set fw"""
@@ -592,25 +639,37 @@ class NativeTableBuild:
         bits, sib = fw.membership(vd[1])
         return (_u64cat(vd[0], vd[1]), _u64cat(bits, sib))
 
-    def register(self, table, wit, root, nodes, keep=()):
-        """every node of the block, circuit by circuit (numpy over all rows at once)"""
-        p, C, rows = self.p, table.n_cols, table.rows
-        keep = set(keep)
-        set_c, set_r = np.asarray(p.cells.set_digest, dtype=np.uint64), np.asarray(p.rows.set_digest, dtype=np.uint64)
-        neutral = np.asarray(NEUTRAL_FIELDS, dtype=np.uint64)
-        ks = np.arange(rows, dtype=np.uint64)
-        cell_kind = {}
+    @staticmethod
+    def cell_kinds(C):
+        """{position: (circuit name, [children])} of a cells tree over C value columns"""
+        kinds = {}
         for c in range(1, C + 1):
             kids = [x for x in sbbst_children(C, c) if x is not None]
-            cell_kind[c] = (("cells_leaf", "cells_partial", "cells_full")[len(kids)], kids)
+            kinds[c] = (("cells_leaf", "cells_partial", "cells_full")[len(kids)], kids)
+        return kinds
+
+    def register(self, table, wit, root, nodes, keep=(), keep_all=False, only=None):
+        """every node of the block, circuit by circuit (numpy over all rows at once). keep_all: every node keeps its slot (a build
+        that stores every proof). only = (cells {row: positions}, rows): register these nodes alone -- the closure of an update,
+        whose other children are external nodes of the forest -- with the words a full registration gives them."""
+        p, C, rows = self.p, table.n_cols, table.rows
+        keep = set(range(rows)) if keep_all else set(keep)
+        only_cells, only_rows = only if only is not None else (None, None)
+        set_c, set_r = np.asarray(p.cells.set_digest, dtype=np.uint64), np.asarray(p.rows.set_digest, dtype=np.uint64)
+        neutral = np.asarray(NEUTRAL_FIELDS, dtype=np.uint64)
+        cell_kind = self.cell_kinds(C)
         blocks_c = {n: self._child_block(p.cells, n) for n in ("cells_leaf", "cells_full", "cells_partial")}
         blocks_r = {n: self._child_block(p.rows, n) for n in ("row_leaf", "row_full", "row_partial")}
-        tile = lambda v: np.broadcast_to(np.asarray(v, dtype=np.uint64)[None, :], (rows, len(v)))
-        keep_cells = np.array([1 if k in keep else 0 for k in range(rows)], dtype=np.uint8)
         for c in range(1, C + 1):
             name, kids = cell_kind[c]
-            flat = np.concatenate([np.full((rows, 1), table.col_ids[c], dtype=np.uint64), table.values[:, c].astype(np.uint64), np.zeros((rows, 1), dtype=np.uint64),
-                                   wit.cell_digest[:, c - 1], tile(neutral)], axis=1)
+            ri = np.arange(rows, dtype=np.int64) if only_cells is None else np.array(sorted(k for k, ps in only_cells.items() if c in ps), dtype=np.int64)
+            m = len(ri)
+            if not m:
+                continue
+            ks = ri.astype(np.uint64)
+            tile = lambda v: np.broadcast_to(np.asarray(v, dtype=np.uint64)[None, :], (m, len(v)))
+            flat = np.concatenate([np.full((m, 1), table.col_ids[c], dtype=np.uint64), table.values[ri, c].astype(np.uint64), np.zeros((m, 1), dtype=np.uint64),
+                                   wit.cell_digest[ri, c - 1], tile(neutral)], axis=1)
             parts = [tile(set_c)]
             for kc in kids:
                 head, tail = blocks_c[cell_kind[kc][0]]
@@ -618,7 +677,8 @@ class NativeTableBuild:
             consts = np.ascontiguousarray(np.concatenate(parts + [flat], axis=1))
             child_ids = np.stack([(np.uint64(kc) << np.uint64(40)) | ks for kc in kids], axis=1) if kids else None
             is_root = c == sbbst_root(C)
-            self.forest.add_nodes(self.CIRCUITS.index(name), (np.uint64(c) << np.uint64(40)) | ks, child_ids, consts, keep_cells if is_root else None)
+            keep_cells = np.array([1 if int(k) in keep else 0 for k in ri], dtype=np.uint8)
+            self.forest.add_nodes(self.CIRCUITS.index(name), (np.uint64(c) << np.uint64(40)) | ks, child_ids, consts, keep_cells if is_root or keep_all else None)
         root_c = sbbst_root(C)
         root_name = cell_kind[root_c][0]
         head_c, tail_c = blocks_c[root_name]
@@ -626,7 +686,7 @@ class NativeTableBuild:
         # row nodes by kind; a child's verifier data and membership proof depend on the CHILD's circuit
         self.row_name = {k: ("row_leaf", "row_partial", "row_full")[(l is not None) + (r is not None)] for k, (l, r) in nodes.items()}
         for n in ("row_leaf", "row_partial", "row_full"):
-            ka = np.array(sorted(k for k, nm in self.row_name.items() if nm == n), dtype=np.int64)
+            ka = np.array(sorted(k for k, nm in self.row_name.items() if nm == n and (only_rows is None or k in only_rows)), dtype=np.int64)
             m = len(ka)
             if not m:
                 continue
@@ -658,10 +718,62 @@ class NativeTableBuild:
         at = n_pi + 3 * cw
         return caps, words[at:at + 2 * no].reshape(no, 2).copy(), words[at + 2 * no:].copy(), words[:n_pi].copy()
 
-    def run(self, table, wit, root, nodes, keep=()):
+    # ---- the proof store side: a node's ProofWithVK bytes and its key ---------------------------------------------------------
+    @staticmethod
+    def row_key(table, k):
+        """the tree key of row k in the proof store: its secondary-index value (RowProofIdentifier::tree_key)"""
+        return f"{table.secondary_int(k):064x}"
+
+    def node_key(self, table, table_name, primary, node_id):
+        """ProofKey of a forest node: CellProofIdentifier {table, primary, secondary = the row's key, tree_key = the position} or
+        RowProofIdentifier {table, primary, tree_key = the row's key} (proof_storage.rs:19-53)"""
+        from .proofstore import ProofKey
+        k, c = int(node_id) & ((1 << 40) - 1), int(node_id) >> 40
+        return ProofKey.cell(table_name, primary, self.row_key(table, k), c) if c else ProofKey.row(table_name, primary, self.row_key(table, k))
+
+    def node_name(self, C, node_id):
+        """the circuit of a node: a cells-tree node's by its position, a row's by its children (set by register)"""
+        c = int(node_id) >> 40
+        return self.cell_kinds(C)[c][0] if c else self.row_name[int(node_id)]
+
+    def _set_of(self, name):
+        rows_set = name.startswith("row")
+        fw = self.p.rows if rows_set else self.p.cells
+        fp, n_pi = (self.fp_rows, self.npi_rows) if rows_set else (self.fp_cells, self.npi_cells)
+        return rows_set, fw, fp, n_pi, fw.chains[name][-1][0].num_constants
+
+    def node_blob(self, words, name):
+        """a pooled proof as ProofWithVK bytes (mp2-common/src/proof.rs:42-52): what the proof store keeps"""
+        from . import serialize_proof, serialize_proof_with_vk
+        rows_set, fw, fp, _, num_constants = self._set_of(name)
+        vk_cap, vk_dig = fw.vds[name]
+        return serialize_proof_with_vk(serialize_proof(fp, num_constants, *self._host_proof(words, rows_set, name)), vk_cap, vk_dig)
+
+    def blob_words(self, blob, name):
+        """the inverse of node_blob: (the proof's words in a parent's input order, whether its verifier key is circuit `name`'s)"""
+        from . import deserialize_proof_with_vk
+        _, fw, fp, n_pi, num_constants = self._set_of(name)
+        (caps, openings, fri, pis), vk_cap, dig = deserialize_proof_with_vk(fp, num_constants, blob, n_pi)
+        want_cap, want_dig = fw.vds[name]
+        own = np.array_equal(vk_cap.ravel(), np.asarray(want_cap, dtype=np.uint64).ravel()) and np.array_equal(dig, np.asarray(want_dig, dtype=np.uint64).ravel())
+        return _u64cat(pis, caps[1:4], openings, fri), own
+
+    def _store_nodes(self, table, C, ids, store, table_name, primary, chunk=64):
+        """download the published nodes `ids` (Forest.proofs, `chunk` at a time) and store each under `primary`"""
+        ids = [int(i) for i in ids]
+        for lo in range(0, len(ids), chunk):
+            part = ids[lo:lo + chunk]
+            for i, words in zip(part, self.forest.proofs(part)):
+                store.store_proof(self.node_key(table, table_name, primary, i), self.node_blob(words, self.node_name(C, i)))
+
+    def run(self, table, wit, root, nodes, keep=(), store=None, table_name="table", primary=1):
         """register the block, then drain the batched work plan wave by wave, every wave as one mp2g_forest_prove over groups of its
         items; returns (root proof, name). Nodes in `keep` (and their children and cells roots) stay downloadable afterwards:
-        self.row_proofs / self.cells_roots hold them as host tuples, like TableBuild's."""
+        self.row_proofs / self.cells_roots hold them as host tuples, like TableBuild's.
+        store (a proofstore.ProofStore): EVERY node keeps its slot, and after the plan every proof goes into the store as ProofWithVK
+        bytes under ProofKey.cell / ProofKey.row of (table_name, primary) -- what update() later takes untouched siblings from;
+        self.last_proved = {node id: primary}. The pool then holds (C + 1) * rows proofs: a block that does not fit in free device
+        memory is refused before anything is proved."""
         from . import Forest
         C = table.n_cols
         keep_rows = set(keep)
@@ -677,8 +789,11 @@ class NativeTableBuild:
         unit = max(1, min(self.group_rows, -(-table.rows // len(self.provers))))
         per_row = max(2, cells_tree_live_peak(C))
         slots = self.pool_slots or (len(self.provers) * (per_row * unit + 4 * self.batch) + table.rows // max(1, self.subtree_size // 2) + 2 * len(keep_rows) + 256)
+        if store is not None:  # nothing returns to the pool: every proof stays until it has been stored
+            slots = (C + 1) * table.rows
+            self._pool_must_fit(slots, f"a build that stores every proof keeps ({C} + 1) x {table.rows} proofs in the pool")
         self.forest = Forest([pv.ctx for pv in self.provers], self.desc, self.chains, max(self.pw_cells, self.pw_rows), slots)
-        self.register(table, wit, root, nodes, keep_rows)
+        self.register(table, wit, root, nodes, keep_rows, keep_all=store is not None)
         ut = W.UpdateTree.from_map(0, root, nodes)
         plan = ut.into_batched_workplan(self.subtree_size) if self.subtree_size > 1 else ut.into_workplan()
         # the harness loop (drain the Ready items, prove, mark done) runs inside the library: a row key k stands for the row node k and
@@ -696,7 +811,125 @@ class NativeTableBuild:
         self.n_proofs += self.forest.proved
         self.row_proofs = {k: (self._host_proof(self.forest.proof_words(k), True, self.row_name[k]), self.row_name[k]) for k in keep_rows}
         self.cells_roots = {k: (self._host_proof(self.forest.proof_words(self.cell_id(k, sbbst_root(C))), False, self.cells_root_name), self.cells_root_name) for k in keep_rows}
+        if store is not None:
+            ids = [self.cell_id(k, c) for k in sorted(nodes) for c in range(1, C + 1)] + sorted(nodes)
+            self._store_nodes(table, C, ids, store, table_name, primary)
+            self.last_proved = {i: int(primary) for i in ids}
         return self.row_proofs[root]
+
+    def _pool_must_fit(self, slots, what):
+        """refuse, before anything is proved, a pool that free device memory cannot hold (mp2g_ctx_mem_info of the first worker)"""
+        need = slots * max(self.pw_cells, self.pw_rows) * 8
+        free, _ = self.provers[0].ctx.mem_info()
+        if need > free:
+            raise MemoryError(f"{what}: {slots} slots = {need} bytes do not fit in the {free} bytes of free device memory; "
+                              "build the table in smaller blocks (a stored build is not drained wave by wave)")
+
+    def update(self, table, wit, root, nodes, touched_rows, touched_cells, store, table_name, primary, last_proved, verify_imported=True):
+        """A block after the first (the reference's steady state: celltree.rs:77-152, rowtree.rs:78-337). table / wit / root / nodes
+        describe the NEW state; touched_rows / touched_cells as update_closure takes them. Only the closure is registered and
+        proved; every other child comes out of `store` under the primary that last_proved ({node id: primary}, as run(store=...)
+        and earlier updates return it) names, enters the pool as an external node (Forest.put_proofs, one call) and -- with
+        verify_imported -- is verified where it lies, by its circuit's verifier, before any proving starts: a stored proof that
+        does not verify raises ValueError naming its key and the status (as ProofStore.get_proof_verified), a missing one the
+        store's KeyError. The closure is proved through an UpdateTree built from the paths to the touched rows; the new proofs go
+        into the store under `primary`. Returns (root proof, name, the new last_proved)."""
+        from . import Forest
+        C = table.n_cols
+        cells, rows, imports = update_closure(C, nodes, touched_rows, touched_cells)
+        self.row_name = {k: ("row_leaf", "row_partial", "row_full")[(l is not None) + (r is not None)] for k, (l, r) in nodes.items()}
+        if not rows:  # nothing changed: the stored root stands
+            words, _ = self.blob_words(store.get_proof_exact(self.node_key(table, table_name, last_proved[root], root)), self.row_name[root])
+            return self._host_proof(words, True, self.row_name[root]), self.row_name[root], dict(last_proved)
+        closure = [self.cell_id(k, c) for k in sorted(cells) for c in cells[k]] + sorted(rows)
+        imports = sorted(imports)
+        # the stored siblings: bytes -> words, in one array for one put_proofs call
+        keys, words = {}, []
+        for i in imports:
+            if i not in last_proved:
+                raise KeyError(f"node {i} (row {i & ((1 << 40) - 1)}, cells position {i >> 40}) was never proved: last_proved does not name it")
+            keys[i] = self.node_key(table, table_name, last_proved[i], i)
+            w, own = self.blob_words(store.get_proof_exact(keys[i]), self.node_name(C, i))
+            if verify_imported and not own:
+                raise ValueError(f"proof with key {keys[i]!r} in {store.path} does not verify: status 30")  # a foreign verifier key, as verify_with_vk
+            words.append(w)
+        if self.forest is not None:
+            self.forest.free()
+        slots = len(closure) + len(imports)
+        self._pool_must_fit(slots, f"an update of {len(closure)} nodes over {len(imports)} stored proofs")
+        self.forest = Forest([pv.ctx for pv in self.provers], self.desc, self.chains, max(self.pw_cells, self.pw_rows), slots)
+        if imports:
+            self.forest.put_proofs(imports, words)
+        if verify_imported:
+            self._verify_imported(C, imports, keys, store)
+        self.register(table, wit, root, nodes, keep_all=True, only=(cells, rows))
+        # the work plan over the touched paths (UpdateTree::from_paths): its nodes are exactly the row nodes of the closure
+        parent = {c: k for k, kids in nodes.items() for c in kids if c is not None}
+        paths = []
+        for k in sorted(cells):
+            path = [k]
+            while path[-1] in parent:
+                path.append(parent[path[-1]])
+            paths.append(path[::-1])
+        ut = W.UpdateTree.from_paths(paths)
+        assert set(ut.nodes()) == rows
+        plan = ut.into_batched_workplan(self.subtree_size) if self.subtree_size > 1 else ut.into_workplan()
+        t0 = time.perf_counter()
+        self.wave_log = []
+        try:
+            while True:
+                wave = W.drain_wave(plan)
+                if not wave:
+                    break
+                units, unit = [], []
+                for it in wave:
+                    ks = [int(k) for k in it.subtree.nodes()] if it.subtree is not None else [int(it.k)]
+                    if it.subtree is not None:
+                        it.subtree.free()
+                    unit += [self.cell_id(k, c) for k in ks for c in cells.get(k, ())] + ks
+                    if len(unit) >= self.group_rows:
+                        units.append(unit)
+                        unit = []
+                if unit:
+                    units.append(unit)
+                self.forest.prove(units)
+                for it in wave:
+                    plan.done(it.k)
+                self.wave_log.append((len(wave), None, None))
+            assert plan.completed()
+        finally:
+            plan.free()
+        self.seconds_in_prove = time.perf_counter() - t0
+        assert self.forest.proved == len(closure)
+        self.n_proofs += self.forest.proved
+        self._store_nodes(table, C, closure, store, table_name, primary)
+        self.last_proved = dict(last_proved)
+        self.last_proved.update({i: int(primary) for i in closure})
+        name = self.row_name[root]
+        return self._host_proof(self.forest.proof_words(root), True, name), name, dict(self.last_proved)
+
+    def _verify_imported(self, C, imports, keys, store):
+        """the external nodes verified where they lie (Forest.verify), grouped by circuit: one verifier per wrap circuit, on the
+        forest's first context. The first rejected one raises ValueError naming its key and the status; the forest is dropped."""
+        from . import framework as FW
+        ctx = self.provers[0].ctx
+        by_name = {}
+        for i in imports:
+            by_name.setdefault(self.node_name(C, i), []).append(i)
+        for name, ids in by_name.items():
+            _, fw, fp, n_pi, _ = self._set_of(name)
+            wckt, wcap, wdig = fw.chains[name][-1]
+            cv = FW.CircuitVerifier(ctx, wckt, min(len(ids), self.batch), fp=fp, constants_sigmas_cap=wcap, circuit_digest=wdig, n_public_inputs=n_pi)
+            try:
+                for lo in range(0, len(ids), cv.capacity):
+                    part = ids[lo:lo + cv.capacity]
+                    for i, st in zip(part, self.forest.verify(part, cv).tolist()):
+                        if st:
+                            self.forest.free()
+                            self.forest = None
+                            raise ValueError(f"proof with key {keys[i]!r} in {store.path} does not verify: status {int(st)}")
+            finally:
+                cv.free()
 
     def _progress_writer(self, t0, total):
         """MP2G_PROGRESS_FILE=path: a line (seconds, proofs so far, of how many) every 30 s while a long block is proved (the forest's
