@@ -170,12 +170,32 @@ static _Thread_local gl_t g_pow_override;
 static _Thread_local int g_pow_override_armed;
 // the NEXT proof made ON THIS THREAD (one proof, then the search is back) takes `witness` as its proof-of-work witness
 void orc_set_pow_witness(gl_t witness) { g_pow_override = witness; g_pow_override_armed = 1; }
+// A dishonest prover for the verifier's tests (tests/forged_fri_cases.py), thread-local and one-shot like the witness above: the
+// NEXT proof made ON THIS THREAD commits to a FRI commit phase that is inconsistent in the places named here and is honest about
+// everything else, so every Merkle path of the proof holds and only the verifier's field checks can reject it.
+//   stage < n_layers: (d0, d1) is added to layer `stage`'s extension values at the leaf-order positions first + k * stride, k < count
+//     (positions at or beyond the layer's length are skipped), after the values are laid out and before their tree is built. Folding
+//     goes on from the untouched coefficients: the layer disagrees with its neighbours only where it was changed. Position j is
+//     place j & (arity - 1) of coset j >> arity_bits.
+//   stage == n_layers: (d0, d1) is added to final-polynomial coefficient `first` (skipped when there is no such coefficient).
+// Unarmed, orc_fri_prove takes none of these branches and its proofs are bit for bit what they were.
+static _Thread_local struct { unsigned stage; size_t first, count, stride; gl_t d0, d1; int armed; } g_tamper;
+static _Thread_local size_t g_tamper_applied;
+void orc_set_fri_tamper(unsigned stage, size_t first, size_t count, size_t stride, gl_t d0, gl_t d1) {
+  g_tamper.stage = stage; g_tamper.first = first; g_tamper.count = count; g_tamper.stride = stride;
+  g_tamper.d0 = d0 % GL_P; g_tamper.d1 = d1 % GL_P;
+  g_tamper.armed = 1;
+}
+// how many values the last hook consumed on this thread changed (0: it named nothing the proof has)
+size_t orc_fri_tamper_applied(void) { return g_tamper_applied; }
 void orc_fri_prove(const orc_fri_params* P, gl_t* const* coeffs, gl_t* const* leaves, gl_t* const* levels,
                    gl2_t zeta, orc_challenger* ch, gl_t* proof) {
   unsigned k = P->log_n, lg = k + P->rate_bits;
   size_t n = (size_t)1 << k, N = (size_t)1 << lg;
   gl2_t alpha = orc_ch_get_ext(ch);
   gl2_t g_zeta = gl2_scale(zeta, gl_root_of_unity(k));
+  const int tampered = g_tamper.armed;  // consumed here: this proof, whatever it does with it
+  if (tampered) { g_tamper.armed = 0; g_tamper_applied = 0; }
 
   gl2_t* final_poly = calloc(N, sizeof(gl2_t));  // lde: zero padded to 8n
   gl2_t* comp = malloc(n * sizeof(gl2_t));
@@ -228,6 +248,13 @@ void orc_fri_prove(const orc_fri_params* P, gl_t* const* coeffs, gl_t* const* le
       lv[2 * j] = values[i].c[0];
       lv[2 * j + 1] = values[i].c[1];
     }
+    if (tampered && g_tamper.stage == li)
+      for (size_t t = 0, j = g_tamper.first; t < g_tamper.count && j < m; t++, j += g_tamper.stride) {
+        lv[2 * j] = gl_add(lv[2 * j], g_tamper.d0);
+        lv[2 * j + 1] = gl_add(lv[2 * j + 1], g_tamper.d1);
+        g_tamper_applied++;
+        if (!g_tamper.stride || g_tamper.stride >= m) break;  // one position only (and j cannot wrap)
+      }
     unsigned log_leaves = cur_lg - ab;
     gl_t* lvl = malloc(orc_merkle_levels_len(log_leaves, P->cap_height) * sizeof(gl_t));
     orc_merkle_build(P->variant, lv, 2 * arity, log_leaves, P->cap_height, lvl);
@@ -251,6 +278,10 @@ void orc_fri_prove(const orc_fri_params* P, gl_t* const* coeffs, gl_t* const* le
     ext_coset_fft(values, cur_lg, shift);
   }
   size_t final_len = m >> P->rate_bits;
+  if (tampered && g_tamper.stage == P->n_layers && g_tamper.first < final_len) {
+    cf[g_tamper.first] = gl2_add(cf[g_tamper.first], (gl2_t){{g_tamper.d0, g_tamper.d1}});
+    g_tamper_applied = 1;
+  }
   size_t qwords = query_words(P);
   gl_t* out_q = proof + P->n_layers * capw;
   gl_t* out_final = out_q + P->num_queries * qwords;

@@ -33,4 +33,11 @@ void orc_ch_init(orc_challenger* c, int variant);
 void orc_ch_observe(orc_challenger* c, const gl_t* e, size_t n);
 gl_t orc_ch_get(orc_challenger* c);
 gl2_t orc_ch_get_ext(orc_challenger* c);
+
+// One-shot, thread-local hooks consumed by the next orc_fri_prove on the calling thread (fri.c): the proof-of-work witness to use,
+// and a dishonest commit phase -- (d0, d1) added to layer `stage`'s values at positions first + k * stride, k < count, or, with
+// stage == n_layers, to final-polynomial coefficient `first`. orc_fri_tamper_applied: values the last consumed hook changed.
+void orc_set_pow_witness(gl_t witness);
+void orc_set_fri_tamper(unsigned stage, size_t first, size_t count, size_t stride, gl_t d0, gl_t d1);
+size_t orc_fri_tamper_applied(void);
 #endif

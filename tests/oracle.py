@@ -2,6 +2,7 @@
 
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg import this module.
 """
+import contextlib
 import ctypes
 import os
 import subprocess
@@ -40,6 +41,20 @@ def lib():
         _lib.orc_n_openings.restype = ctypes.c_size_t
         _lib.orc_bitrev.restype = ctypes.c_size_t
     return _lib
+
+
+@contextlib.contextmanager
+def omp_threads(n):
+    """at most n OpenMP threads for the oracle calls made inside (the calling thread's setting, put back on the way out). For
+    loops over hundreds of proofs of a few hundred rows: a parallel region there is microseconds of work, and a wide team spends
+    its time -- and, where the process has a CPU quota, the quota -- spinning at the barriers between them."""
+    L = lib()
+    before = L.omp_get_max_threads()
+    L.omp_set_num_threads(max(1, min(int(n), before)))
+    try:
+        yield
+    finally:
+        L.omp_set_num_threads(before)
 
 
 def arr(a, dtype=np.uint64):
@@ -249,6 +264,18 @@ class Challenger:
     def get(self, n):
         lib().orc_ch_get.restype = ctypes.c_uint64
         return np.array([lib().orc_ch_get(self.st) for _ in range(n)], dtype=np.uint64)
+
+
+def set_fri_tamper(stage, first, count=1, stride=1, delta=(1, 0)):
+    """orc_set_fri_tamper: the next proof made on this thread adds `delta` to layer `stage`'s values at first + k * stride, k < count
+    (stage == n_layers: to final-polynomial coefficient `first`) and commits honestly to the result"""
+    lib().orc_set_fri_tamper(ctypes.c_uint(stage), sz(first), sz(count), sz(stride), ctypes.c_uint64(delta[0] % P), ctypes.c_uint64(delta[1] % P))
+
+
+def fri_tamper_applied():
+    """how many values the last consumed tamper hook changed"""
+    lib().orc_fri_tamper_applied.restype = ctypes.c_size_t
+    return int(lib().orc_fri_tamper_applied())
 
 
 def fri_commit(fp, coeffs):

@@ -93,7 +93,7 @@ def test_rejects_code_for_code(ctx, mp2):
     and plonky2 accept such a mutation, so must the device).
     Code 5 (final polynomial) cannot be reached by mutating a proof: the final polynomial is observed before the PoW response and
     the query indices are drawn, so changing it changes which queries are made -- it needs a dishonest prover and is not in the
-    catalogue; the accept tests run that evaluation on all 28 queries of every proof."""
+    catalogue (test_gpu_forged_proofs.py has one); the accept tests run that evaluation on all 28 queries of every proof."""
     ckt = circuit(7, "LOOKUP")
     cp, d_ph, ph, caps, openings, proofs = prove_batch(ctx, ckt, 1, rand_row=False)
     ofp, dig = C.oracle_params(ckt), cp.circuit_digest
