@@ -370,6 +370,71 @@ int mp2g_row_tree_hashes_update_dev(mp2g_ctx* ctx, int variant, const mp2g_tree_
                                     uint32_t value_stride, const uint64_t* d_payload, const uint32_t* touched /* host */, uint32_t n_touched,
                                     uint64_t* d_hashes);
 
+/* ---- accumulated digests of a table's trees (off-circuit value side, csrc/tree_digest.hip) --------------------------------------
+ * The Ecgfp5 digest every node of a cells tree and of the row tree exposes as public inputs, device resident: one pass over a tree
+ * shape with one launch per level, and after a block only the touched nodes and their ancestors. Between the calls a point is the
+ * 20 words d_frac holds (fractional coordinates X:Z:U:T, 5 limbs each): a representative of the point, not a canonical form, so no
+ * call on the way pays Point::encode's inversion or Point::decode's square root. Compare points through mp2g_curve_emit_dev only. */
+/* Point::decode ([dep] plonky2_ecgfp5 curve/curve.rs) of `count` encodings into d_frac [count][20] (device). Refuses a limb >= p on
+ * the host before any upload ("point encoding is not canonical"), as mp2g_curve_sum does, and an invalid encoding after the launch
+ * (one synchronisation; d_frac then holds the neutral point at the refused entries). count == 0 returns 0 and launches nothing. */
+int mp2g_curve_decode_dev(mp2g_ctx* ctx, const uint64_t* pts_w /* host [count][5] */, uint32_t count, uint64_t* d_frac /* [count][20] */);
+/* Point::encode / the 11-limb Weierstrass form (group_hashing/mod.rs:163-174) of the points idx[0..count) of d_frac; idx NULL =
+ * the points 0..count-1. idx is a host array (free on return; it goes through the context's ring of pinned slots) whose entries the
+ * caller keeps inside d_frac: the call does not know that buffer's size. out_w [count][5] and out_weierstrass [count][11] are host
+ * arrays and compact (entry j belongs to idx[j]); either may be NULL. One synchronisation. */
+int mp2g_curve_emit_dev(mp2g_ctx* ctx, const uint64_t* d_frac, const uint32_t* idx /* host or NULL */, uint32_t count,
+                        uint64_t* out_w /* [count][5] */, uint64_t* out_weierstrass /* [count][11] */);
+/* acc[i] = own[i] + acc[left[i]] + acc[right[i]] for every node of `shape`: the accumulated digest SplitDigestPoint::accumulate
+ * (mp2-common/src/digest.rs:38-47) builds node by node up the cells tree (verifiable-db/src/cells_tree/full_node.rs:26-28) and the
+ * row tree (row_tree/full_node.rs:78-82). d_own / d_acc [n][20]. One launch per level of the shape, n - 1 additions in all (the
+ * complete addition: equal points, inverse points and the neutral point need no care); a missing child costs none. Any shape:
+ * unlike mp2g_curve_sum_ranges it does not need the tree laid out in order. Stream ordered, no synchronisation. Refused before any
+ * launch: shape NULL, d_own and d_acc overlapping, a shape first used with another context. An empty shape returns 0 and launches
+ * nothing. */
+int mp2g_tree_digests_dev(mp2g_ctx* ctx, const mp2g_tree_shape* shape, const uint64_t* d_own /* [n][20] */, uint64_t* d_acc /* [n][20] */);
+/* the same from encodings own_w [n][5] and to encodings out_w [n][5] / out_weierstrass [n][11] (either NULL) in host memory: decode,
+ * the pass, emit. Refuses what mp2g_curve_decode_dev refuses. */
+int mp2g_tree_digests(mp2g_ctx* ctx, const mp2g_tree_shape* shape, const uint64_t* own_w /* [n][5] */, uint64_t* out_w,
+                      uint64_t* out_weierstrass);
+/* the same for the touched nodes and their ancestors only (MerkleTreeKvDb::aggregate over touched(), ryhope/src/lib.rs:179-222; the
+ * set is mp2g_tree_shape_touched's). The contract is mp2g_row_tree_hashes_update_dev's: on entry d_acc holds valid digests for
+ * every node outside that set; on return every node of the set holds its digest under the current d_own and shape, and no word
+ * outside the set has been written. touched lists every node whose own digest or children differ from what d_acc was computed for;
+ * it is a host array, free on return, and the lists go through the context's ring of pinned slots. n_touched == 0 returns 0 and
+ * launches nothing. Refused before any launch: what mp2g_tree_digests_dev refuses, a touched index >= n (named in the message),
+ * touched NULL with n_touched != 0.
+ * While no level of the set has more than mp2g_tree_digests_update_fused_width() nodes and the set has at most 256 levels: ONE
+ * launch of one 128-lane workgroup for the whole set (one lane per node, a barrier between levels). Everything else: one launch
+ * per level of the set. */
+uint32_t mp2g_tree_digests_update_fused_width(void);
+int mp2g_tree_digests_update_dev(mp2g_ctx* ctx, const mp2g_tree_shape* shape, const uint64_t* d_own, const uint32_t* touched /* host */,
+                                 uint32_t n_touched, uint64_t* d_acc /* in and out */);
+/* every node of every row's cells tree: d_nodes[row][k-1] = D(col_ids[k] || values[row][k]) + d_nodes[row][left] +
+ * d_nodes[row][right] over the sbbst of the positions 1..n_cols-1, which is Cell::values_digest (verifiable-db/src/cells_tree/
+ * mod.rs:65-72) accumulated up the tree (cells_tree/full_node.rs:26-28, partial_node.rs) with every cell individual. n_cols,
+ * col_ids, d_values and the node indexing exactly as mp2g_cells_tree_hashes_dev takes them; d_nodes [rows][n_cols-1][20]. One launch
+ * per height of the cells tree, one square root per cell. row_idx (host, free on return) NULL with n_idx == 0 = all rows; otherwise
+ * only the listed rows' entries are written (duplicates allowed), and a list with n_idx == 0 returns 0 and launches nothing, as
+ * rows == 0 does. n_cols == 1: there are no cells and d_nodes is not touched. Refused before any launch: what
+ * mp2g_cells_tree_hashes_rows_dev refuses (variant, n_cols outside 1..256, a col_ids entry >= p, a row index >= rows, named in the
+ * message, row_idx NULL with n_idx != 0). Stream ordered. */
+int mp2g_cells_tree_digests_dev(mp2g_ctx* ctx, int variant, const uint64_t* col_ids /* host */, uint32_t n_cols, const uint32_t* d_values,
+                                uint32_t rows, const uint32_t* row_idx /* host or NULL */, uint32_t n_idx,
+                                uint64_t* d_nodes /* [rows][n_cols-1][20] */);
+/* the per-row terms of mp2g_row_digests (secondary_index_cell.rs:99-139; mp2-v1/src/values_extraction/mod.rs:499-571), device
+ * resident: d_own[row] = row_id * sum over columns of D(id_c || value_c). Row r's unique columns are the 8 * n_unique words at
+ * d_unique + r * unique_stride (u32 words, >= 8 * n_unique: pass d_values and n_cols * 8 to read column 0 of the table in place).
+ * d_cells_nodes NULL = map every column as mp2g_row_digests does; otherwise it is what mp2g_cells_tree_digests_dev wrote, and the
+ * sum is D(id_0 || value_0) + d_cells_nodes[row][root of the cells tree]: one square root per row instead of n_cols, the same
+ * group element. n_cols == 1 ignores d_cells_nodes. row_idx as above: only the listed rows of d_own [rows][20] are written.
+ * Refused before any launch: what mp2g_cells_tree_digests_dev refuses, d_unique NULL with n_unique != 0, unique_stride below
+ * 8 * n_unique. Stream ordered. */
+int mp2g_row_digests_dev(mp2g_ctx* ctx, int variant, const uint64_t* col_ids /* host */, uint32_t n_cols, const uint32_t* d_values,
+                         const uint32_t* d_unique, uint32_t unique_stride, uint32_t n_unique, uint32_t rows,
+                         const uint64_t* d_cells_nodes /* or NULL */, const uint32_t* row_idx /* host or NULL */, uint32_t n_idx,
+                         uint64_t* d_own /* [rows][20] */);
+
 /* ---- proof wire format between tree levels / GPUs ------------------------------------------ */
 /* bincode 1.3 (little-endian fixed-width ints, u64 length prefixes) serialization of plonky2's
  * ProofWithPublicInputs<F, C, 2> exactly as mp2-common/src/proof.rs:84-98 `serialize_proof`

@@ -1098,6 +1098,78 @@ def row_tree_hashes_update_dev(ctx, variant, shape, ident, d_values, value_strid
                                                _p(t), t.size, d_hashes))
 
 
+# ---- accumulated digests of a table's trees (csrc/tree_digest.hip): points stay on the device as 20 words each --------------------
+FRAC_BYTES = 160  # one point in fractional coordinates (X:Z:U:T, 5 limbs each): a representative, not a canonical form
+
+
+def curve_decode_dev(ctx, pts_w, d_frac):
+    """mp2g_curve_decode_dev: the encodings pts_w [count][5] decoded into d_frac [count][20]; refuses a limb >= p and an invalid
+    encoding. One synchronisation."""
+    a = _arr(pts_w).reshape(-1, 5)
+    _ck(load().mp2g_curve_decode_dev(ctx, _p(a), a.shape[0], d_frac))
+
+
+def curve_emit_dev(ctx, d_frac, count, idx=None):
+    """mp2g_curve_emit_dev: (encodings [k][5], Weierstrass forms [k][11]) of the points idx (a host list whose entries the caller
+    keeps inside d_frac) or, without one, of the points 0..count-1. One synchronisation."""
+    i = None if idx is None else _arr(idx, np.uint32).ravel()
+    k = int(count) if i is None else i.size
+    w, wei = np.zeros((k, 5), dtype=np.uint64), np.zeros((k, 11), dtype=np.uint64)
+    _ck(load().mp2g_curve_emit_dev(ctx, d_frac, None if i is None else _p(i), k, _p(w), _p(wei)))
+    return w, wei
+
+
+def tree_digests_dev(ctx, shape, d_own, d_acc):
+    """mp2g_tree_digests_dev: acc[i] = own[i] + acc[left[i]] + acc[right[i]] for every node of the shape, one launch per level;
+    stream ordered. The shape joins the context's handles as in row_tree_hashes_dev."""
+    if ctx is not None:
+        ctx._adopt(shape)
+    _ck(load().mp2g_tree_digests_dev(ctx, shape.h, d_own, d_acc))
+
+
+def tree_digests(ctx, shape, own_w):
+    """mp2g_tree_digests: the same from encodings own_w [n][5] in host memory; returns (encodings [n][5], Weierstrass [n][11])"""
+    a = _arr(own_w).reshape(-1, 5)
+    if a.shape[0] != shape.size:
+        raise ValueError("own_w has not one encoding per node of the shape")
+    if ctx is not None:
+        ctx._adopt(shape)
+    w, wei = np.zeros((shape.size, 5), dtype=np.uint64), np.zeros((shape.size, 11), dtype=np.uint64)
+    _ck(load().mp2g_tree_digests(ctx, shape.h, _p(a), _p(w), _p(wei)))
+    return w, wei
+
+
+def tree_digests_update_fused_width():
+    """mp2g_tree_digests_update_fused_width: the widest level of a touched closure that mp2g_tree_digests_update_dev still sums in one launch"""
+    return int(load().mp2g_tree_digests_update_fused_width())
+
+
+def tree_digests_update_dev(ctx, shape, d_own, touched, d_acc):
+    """mp2g_tree_digests_update_dev: the touched nodes and their ancestors only; stream ordered; touched is a host array"""
+    if ctx is not None:
+        ctx._adopt(shape)
+    t = _arr(touched, np.uint32).ravel()
+    _ck(load().mp2g_tree_digests_update_dev(ctx, shape.h, d_own, _p(t), t.size, d_acc))
+
+
+def cells_tree_digests_dev(ctx, variant, col_ids, d_values, rows, d_nodes, row_idx=None):
+    """mp2g_cells_tree_digests_dev: every node of every row's cells tree (row_idx None), or of the listed rows only, into d_nodes
+    [rows][n_cols-1][20]; stream ordered; col_ids and row_idx are host arrays"""
+    ids = _arr(col_ids).ravel()
+    idx = None if row_idx is None else _arr(row_idx, np.uint32).ravel()
+    _ck(load().mp2g_cells_tree_digests_dev(ctx, int(variant), _p(ids), ids.size, d_values, int(rows), None if idx is None else _p(idx),
+                                           0 if idx is None else idx.size, d_nodes))
+
+
+def row_digests_dev(ctx, variant, col_ids, d_values, d_unique, unique_stride, n_unique, rows, d_own, d_cells_nodes=None, row_idx=None):
+    """mp2g_row_digests_dev: the rows' own digests row_id * sum_c D(id_c || value_c) into d_own [rows][20]; with d_cells_nodes (what
+    cells_tree_digests_dev wrote) the cells' part of the sum is taken from the cells tree's root. Stream ordered."""
+    ids = _arr(col_ids).ravel()
+    idx = None if row_idx is None else _arr(row_idx, np.uint32).ravel()
+    _ck(load().mp2g_row_digests_dev(ctx, int(variant), _p(ids), ids.size, d_values, d_unique, int(unique_stride), int(n_unique), int(rows),
+                                    d_cells_nodes, None if idx is None else _p(idx), 0 if idx is None else idx.size, d_own))
+
+
 def leaf_permutations_queued():
     """permutations the Merkle leaf sponge has queued since the library was loaded (mp2g_stat_leaf_permutations)"""
     return int(load().mp2g_stat_leaf_permutations())

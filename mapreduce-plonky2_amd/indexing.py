@@ -229,3 +229,89 @@ class TableHashes:
             if d is not None:
                 d.free()
         self.d_values = self.d_cells = self.d_rows = None
+
+
+class TableDigests:
+    """The Ecgfp5 digests of a block of rows, kept on the device between blocks beside TableHashes: every node of every row's cells
+    tree (Cell::values_digest accumulated up the sbbst), every row's own digest row_id * (D(secondary cell) + cells root)
+    (secondary_index_cell.rs:99-139) and its accumulation up the row tree (row_tree/full_node.rs:78-82) -- the fields of
+    table.TableWitness, over any tree shape. Built by mp2g_cells_tree_digests_dev, mp2g_row_digests_dev with the cells roots and
+    mp2g_tree_digests_dev; update() runs the listed-rows forms of the first two and mp2g_tree_digests_update_dev, so a block costs its
+    touched closure. Points stay in fractional coordinates on the device; the accessors encode what they download.
+    values: uint32 [rows][n_cols][8], column 0 the secondary index (the row's unique data); shape: the row tree, one node per row."""
+
+    def __init__(self, ctx, col_ids, values, shape, variant=0):
+        self.ctx, self.shape, self.variant = ctx, shape, int(variant)
+        self.ids = np.ascontiguousarray(col_ids, dtype=np.uint64).ravel()
+        v = _table_values(values, self.ids.size)
+        self.rows, self.cells = v.shape[0], max(self.ids.size, 1) - 1
+        if shape.size != self.rows:
+            raise ValueError("the row tree's shape has not one node per row")
+        self.d_values = self.d_cells = self.d_own = self.d_acc = None
+        if self.rows:
+            fb = _mp2.FRAC_BYTES
+            self.d_values = ctx.to_device(v)
+            self.d_cells = ctx.alloc(self.rows * self.cells * fb) if self.cells else None
+            self.d_own, self.d_acc = ctx.alloc(self.rows * fb), ctx.alloc(self.rows * fb)
+            _mp2.cells_tree_digests_dev(ctx, self.variant, self.ids, self.d_values, self.rows, self.d_cells)
+            self._row_own(None)
+            _mp2.tree_digests_dev(ctx, shape, self.d_own, self.d_acc)
+
+    def _row_own(self, idx):
+        # the unique column is column 0 of the resident table, read in place
+        _mp2.row_digests_dev(self.ctx, self.variant, self.ids, self.d_values, self.d_values, self.ids.size * 8, 1, self.rows, self.d_own,
+                             self.d_cells, idx)
+
+    def update(self, rows, new_values):
+        """rows: the indices of the changed rows (distinct); new_values: uint32 [len(rows)][n_cols][8]. Returns the row-tree nodes
+        whose accumulated digest was recomputed (shape.touched(rows))."""
+        idx = np.ascontiguousarray(rows, dtype=np.uint32).ravel()
+        nv = np.ascontiguousarray(new_values, dtype=np.uint32).reshape(idx.size, self.ids.size, 8)
+        if idx.size and int(idx.max()) >= self.rows:
+            raise ValueError("row index outside the table")
+        touched = self.shape.touched(idx)
+        if not idx.size:
+            return touched
+        row_bytes = self.ids.size * 32
+        for j, r in enumerate(idx.tolist()):
+            self.d_values.upload_at(nv[j], r * row_bytes)
+        _mp2.cells_tree_digests_dev(self.ctx, self.variant, self.ids, self.d_values, self.rows, self.d_cells, idx)
+        self._row_own(idx)
+        _mp2.tree_digests_update_dev(self.ctx, self.shape, self.d_own, idx, self.d_acc)
+        return touched
+
+    def _listed(self, which):
+        idx = np.arange(self.rows, dtype=np.uint32) if which is None else np.ascontiguousarray(which, dtype=np.uint32).ravel()
+        if idx.size and int(idx.max()) >= self.rows:
+            raise ValueError("row index outside the table")
+        return idx
+
+    def cell_digests(self, rows=None):
+        """Weierstrass [len(rows)][n_cols-1][11]: the accumulated digest of every node of the rows' cells trees (position k at index k - 1)"""
+        idx = self._listed(rows)
+        if not idx.size or not self.cells:
+            return np.zeros((idx.size, self.cells, 11), dtype=np.uint64)
+        flat = (idx.astype(np.uint64)[:, None] * np.uint64(self.cells) + np.arange(self.cells, dtype=np.uint64)[None, :]).astype(np.uint32)
+        return _mp2.curve_emit_dev(self.ctx, self.d_cells, 0, flat)[1].reshape(idx.size, self.cells, 11)
+
+    def row_own(self, rows=None):
+        """Weierstrass [len(rows)][11]: the rows' own (individual) digests"""
+        idx = self._listed(rows)
+        return _mp2.curve_emit_dev(self.ctx, self.d_own, 0, idx)[1] if idx.size else np.zeros((0, 11), dtype=np.uint64)
+
+    def row_digests(self, nodes=None):
+        """(encodings [len(nodes)][5], Weierstrass [len(nodes)][11]): the accumulated digests of the row-tree nodes"""
+        idx = self._listed(nodes)
+        if not idx.size:
+            return np.zeros((0, 5), dtype=np.uint64), np.zeros((0, 11), dtype=np.uint64)
+        return _mp2.curve_emit_dev(self.ctx, self.d_acc, 0, idx)
+
+    def root_digests(self):
+        """row_digests of the row tree's root nodes, ascending"""
+        return self.row_digests(self.shape.describe()["roots"])
+
+    def free(self):
+        for d in (self.d_values, self.d_cells, self.d_own, self.d_acc):
+            if d is not None:
+                d.free()
+        self.d_values = self.d_cells = self.d_own = self.d_acc = None
