@@ -435,6 +435,52 @@ int mp2g_row_digests_dev(mp2g_ctx* ctx, int variant, const uint64_t* col_ids /* 
                          const uint64_t* d_cells_nodes /* or NULL */, const uint32_t* row_idx /* host or NULL */, uint32_t n_idx,
                          uint64_t* d_own /* [rows][20] */);
 
+/* ---- tables in contract storage: MPT storage-leaf digests (off-circuit value side, csrc/extraction.hip) --------------------------
+ * What the reference computes for a table that lives in contract storage (mp2-v1/src/values_extraction/mod.rs:298-496): every
+ * storage leaf holds one 32-byte EVM word, and the columns of its (slot, evm_word) are bit fields of that word.
+ *
+ * A column's layout is three u32: byte offset, bit offset (0..8), length in bits (1..256). extract_value (mp2-v1/src/
+ * values_extraction/gadgets/column_gadget.rs:326-368) cuts the field out: with k = ceil(length / 8), byte j < k of the result is
+ * ((word[b + j] & (2^(8 - bit) - 1)) << bit) + (word[b + j + 1] >> (8 - bit)), word[32] = 0; when m = length % 8 is not zero the
+ * last byte is shifted right by 8 - m; the k bytes are left-padded to 32. On the word as a 256-bit big-endian integer V that is
+ * ((V << (8 b + bit)) mod 2^256) >> (256 - 8 k), then the low byte shifted right by 8 - m: what the kernels do, on eight registers.
+ * Refused before anything is uploaded or launched, with a message that names the argument: length 0 or above 256, bit offset above
+ * 8, byte_offset + ceil(length / 8) > 32, more than 32 columns, a required pointer that is NULL, and for _dev a d_words / d_keys
+ * that is not 16-byte aligned (a word is read as two 16-byte loads). */
+/* the cut alone: out[leaf][col] = extract_value(words[leaf], layout[col]) as 8 big-endian u32 words, the cell format of
+ * mp2g_row_digests, mp2g_cells_tree_hashes and mp2g_cells_tree_digests_dev: a storage table reaches those entries without leaving
+ * the device. words [count][32] bytes; layout [n_cols][3] (host in both forms); out [count][n_cols][8]. count == 0 or n_cols == 0
+ * returns 0 and launches nothing. _dev is stream ordered. */
+int mp2g_extract_values(mp2g_ctx* ctx, const uint8_t* words, const uint32_t* layout, uint32_t n_cols, uint32_t count, uint32_t* out);
+int mp2g_extract_values_dev(mp2g_ctx* ctx, const uint8_t* d_words, const uint32_t* layout /* host */, uint32_t n_cols, uint32_t count,
+                            uint32_t* d_out);
+/* compute_leaf_single_values_digest / compute_leaf_mapping_values_digest / compute_leaf_mapping_of_mappings_values_digest
+ * (mod.rs:327-341, :374-406, :450-496) of `count` leaves of one (slot, evm_word), n_keys = 0 / 1 / 2:
+ *   S      = sum over the extracted columns of D(col_ids[c] || extract_value(word, layout[c]))      (ColumnGadgetData::digest,
+ *            column_gadget.rs:301-323), plus D(key_ids[j] || key_j) for every key when evm_word == 0 (mod.rs:389-400, :474-488)
+ *   row_id = HashToInt(H(H(key_0 || key_1) || n_table_columns + n_keys))                             (mod.rs:298-314, :499-523)
+ *   digest = row_id * S
+ * col_ids / layout: the n_extracted columns of this (slot, evm_word) (filter_table_column_identifiers, column_gadget.rs:372-389);
+ * n_table_columns = table_info.len(), every column of the table, those of other EVM words included. keys [count][n_keys][32]: each
+ * key left_pad32-ed, the outer key before the inner one; key_ids [n_keys]. A leaf without columns and without key digests gives the
+ * neutral point (encoding 0, Weierstrass [0 x 10, 1]). col_ids, layout and key_ids are host arrays in both forms and travel in the
+ * kernel's arguments.
+ * out_w [count][5] / out_weierstrass [count][11]: the leaves' digests; sum_w [5] / sum_weierstrass [11]: their sum, what a branch
+ * above all of them accumulates. Each output pointer may be NULL. _dev: d_frac_out [count][20] (or NULL) receives the leaves'
+ * digests in fractional coordinates, for mp2g_tree_digests_* and mp2g_curve_emit_dev; the other four outputs are host pointers;
+ * stream ordered, one synchronisation when a host output is asked for.
+ * Refused like the cut, and further: variant not 0 / 1, n_extracted > 32, n_keys > 2, n_table_columns < n_extracted, a col_ids or
+ * key_ids entry >= p. A refused call writes no output. count == 0 launches nothing; its sum is the neutral point. */
+int mp2g_leaf_values_digests(mp2g_ctx* ctx, int variant, const uint64_t* col_ids, const uint32_t* layout, uint32_t n_extracted,
+                             uint32_t n_table_columns, const uint8_t* words, const uint8_t* keys, const uint64_t* key_ids, uint32_t n_keys,
+                             uint32_t evm_word, uint32_t count, uint64_t* out_w, uint64_t* out_weierstrass, uint64_t sum_w[5],
+                             uint64_t sum_weierstrass[11]);
+int mp2g_leaf_values_digests_dev(mp2g_ctx* ctx, int variant, const uint64_t* col_ids /* host */, const uint32_t* layout /* host */,
+                                 uint32_t n_extracted, uint32_t n_table_columns, const uint8_t* d_words, const uint8_t* d_keys,
+                                 const uint64_t* key_ids /* host */, uint32_t n_keys, uint32_t evm_word, uint32_t count,
+                                 uint64_t* d_frac_out, uint64_t* out_w, uint64_t* out_weierstrass, uint64_t sum_w[5],
+                                 uint64_t sum_weierstrass[11]);
+
 /* ---- proof wire format between tree levels / GPUs ------------------------------------------ */
 /* bincode 1.3 (little-endian fixed-width ints, u64 length prefixes) serialization of plonky2's
  * ProofWithPublicInputs<F, C, 2> exactly as mp2-common/src/proof.rs:84-98 `serialize_proof`

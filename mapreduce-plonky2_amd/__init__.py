@@ -1005,6 +1005,64 @@ def row_digests(ctx, col_ids, values, unique, variant=POSEIDON2):
     return w, wei
 
 
+# ---- tables in contract storage (csrc/extraction.hip; the reference's names and orderings: extraction.py) -------------------------
+def _bytes32(a, inner=None):
+    """uint8 [count][32] (or [count][inner][32]) of words / keys given as arrays or as a list of 32-byte strings"""
+    if isinstance(a, (list, tuple)) and a and isinstance(a[0], (bytes, bytearray)):
+        a = np.frombuffer(b"".join(a), dtype=np.uint8)
+    a = _arr(a, np.uint8)
+    return a.reshape(-1, 32) if inner is None else a.reshape(-1, inner, 32)
+
+
+def extract_values(ctx, words, layout):
+    """mp2g_extract_values: extract_value (column_gadget.rs:326-368) of every word [count][32] under every layout row (byte offset,
+    bit offset, length in bits); uint32 [count][n_cols][8], the cell format of row_digests and the cells-tree calls"""
+    w, lay = _bytes32(words), _arr(layout, np.uint32).reshape(-1, 3)
+    out = np.zeros((w.shape[0], lay.shape[0], 8), dtype=np.uint32)
+    _ck(load().mp2g_extract_values(ctx, _p(w), _p(lay), lay.shape[0], w.shape[0], _p(out)))
+    return out
+
+
+def extract_values_dev(ctx, d_words, layout, count, d_out):
+    """mp2g_extract_values_dev: the same from d_words [count][32] (16-byte aligned) into d_out [count][n_cols][8]; stream ordered;
+    layout is a host array"""
+    lay = _arr(layout, np.uint32).reshape(-1, 3)
+    _ck(load().mp2g_extract_values_dev(ctx, d_words, _p(lay), lay.shape[0], int(count), d_out))
+
+
+def leaf_values_digests(ctx, col_ids, layout, n_table_columns, words, keys=None, key_ids=(), evm_word=0, variant=POSEIDON2):
+    """mp2g_leaf_values_digests: the values digest of every storage leaf (mod.rs:327-341, :374-406, :450-496). col_ids / layout: the
+    extracted columns; words [count][32]; keys [count][n_keys][32] with n_keys = len(key_ids). Returns (encodings [count][5],
+    Weierstrass [count][11], (encoding, Weierstrass) of the sum of all leaves)."""
+    ids, lay, kid = _arr(col_ids).ravel(), _arr(layout, np.uint32).reshape(-1, 3), _arr(key_ids).ravel()
+    w = _bytes32(words)
+    count = w.shape[0]
+    k = _bytes32(keys, kid.size) if kid.size else np.zeros((count, 0, 32), dtype=np.uint8)
+    if lay.shape[0] != ids.size or k.shape[0] != count:
+        raise ValueError("one layout row per extracted column and one key set per word are needed")
+    out_w, out_wei = np.zeros((count, 5), dtype=np.uint64), np.zeros((count, 11), dtype=np.uint64)
+    sum_w, sum_wei = np.zeros(5, dtype=np.uint64), np.zeros(11, dtype=np.uint64)
+    _ck(load().mp2g_leaf_values_digests(ctx, int(variant), _p(ids), _p(lay), ids.size, int(n_table_columns), _p(w), _p(k), _p(kid), kid.size,
+                                        int(evm_word), count, _p(out_w), _p(out_wei), _p(sum_w), _p(sum_wei)))
+    return out_w, out_wei, (sum_w, sum_wei)
+
+
+def leaf_values_digests_dev(ctx, variant, col_ids, layout, n_table_columns, d_words, d_keys, key_ids, evm_word, count, d_frac_out=None,
+                            each=False, total=True):
+    """mp2g_leaf_values_digests_dev: the same from d_words [count][32] and d_keys [count][n_keys][32] (16-byte aligned); the leaves'
+    points go to d_frac_out [count][20] when given. Returns (encodings, Weierstrass forms, (encoding, Weierstrass) of the sum): the
+    first two None without `each`, the last None without `total`; with neither the call is stream ordered."""
+    ids, lay, kid = _arr(col_ids).ravel(), _arr(layout, np.uint32).reshape(-1, 3), _arr(key_ids).ravel()
+    count = int(count)
+    out_w, out_wei = (np.zeros((count, 5), dtype=np.uint64), np.zeros((count, 11), dtype=np.uint64)) if each else (None, None)
+    sum_w, sum_wei = (np.zeros(5, dtype=np.uint64), np.zeros(11, dtype=np.uint64)) if total else (None, None)
+    _ck(load().mp2g_leaf_values_digests_dev(ctx, int(variant), _p(ids), _p(lay), ids.size, int(n_table_columns), d_words, d_keys, _p(kid),
+                                            kid.size, int(evm_word), count, d_frac_out, None if out_w is None else _p(out_w),
+                                            None if out_wei is None else _p(out_wei), None if sum_w is None else _p(sum_w),
+                                            None if sum_wei is None else _p(sum_wei)))
+    return out_w, out_wei, ((sum_w, sum_wei) if total else None)
+
+
 # ---- node hashes of a table's trees (csrc/index_hash.hip) ------------------------------------
 class TreeShape:
     """mp2g_tree_shape: a binary tree or forest over nodes 0..n-1 by its children arrays (-1 = no child), checked and levelled on
