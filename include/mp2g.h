@@ -481,6 +481,74 @@ int mp2g_leaf_values_digests_dev(mp2g_ctx* ctx, int variant, const uint64_t* col
                                  uint64_t* d_frac_out, uint64_t* out_w, uint64_t* out_weierstrass, uint64_t sum_w[5],
                                  uint64_t sum_weierstrass[11]);
 
+/* ---- Keccak-256 on the device: storage slot keys and MPT leaf words (off-circuit value side, csrc/storage.hip) ------------------
+ * What lies between an eth_getProof answer and the 32-byte EVM word mp2g_leaf_values_digests starts from. Keccak-256 is Ethereum's
+ * keccak256: Keccak-f[1600], rate 136 bytes, domain byte 0x01 (not SHA3-256's 0x06), final bit 0x80. One lane per message / leaf,
+ * one shared permutation (csrc/keccak.cuh).
+ *
+ * out[i] = keccak256(msgs + i * stride, lens ? lens[i] : len): the 32 digest bytes. Read as eight little-endian u32 words they are
+ * keccak256(node).pack(Endianness::Little), the H public input of the values-extraction proofs (leaf_single.rs:279,
+ * leaf_mapping.rs:340, branch.rs:318, extension.rs:183): no second output is needed. msgs [count][stride] bytes; a message is
+ * absorbed with 8-byte loads, so stride is a multiple of 8 and the base is 8-byte aligned. No byte at or past `stride` of a row is
+ * read and no byte in [len, stride) influences the result. lens [count] (or NULL: every message has `len` bytes).
+ * Refused before anything is uploaded or launched, with a message that names the argument: stride 0, not a multiple of 8 or above
+ * 65536; len > stride when lens is NULL; in the host form a lens[i] > stride (the message names i); msgs or out NULL; for _dev a
+ * d_msgs or d_out that is not 8-byte aligned (or a d_lens that is not 4-byte aligned). The host cannot see d_lens: in the _dev form
+ * a lane clamps its length to stride. Lanes of one wave may run different numbers of rate blocks. A refused call writes no output;
+ * count == 0 returns 0 and launches nothing; _dev is stream ordered. */
+int mp2g_keccak256_batch(mp2g_ctx* ctx, const uint8_t* msgs, uint32_t stride, const uint32_t* lens, uint32_t len, uint32_t count,
+                         uint8_t* out);
+int mp2g_keccak256_batch_dev(mp2g_ctx* ctx, const uint8_t* d_msgs, uint32_t stride, const uint32_t* d_lens, uint32_t len, uint32_t count,
+                             uint8_t* d_out);
+/* StorageSlot::location, mpt_key and mpt_nibbles (mp2-common/src/eth.rs:233-276) of `count` leaves. Per leaf:
+ *   loc = parents[i] when parents is given, otherwise `slot` as a 32-byte big-endian integer          (eth.rs:235)
+ *   for j = 0 .. n_keys-1, the outer key first: loc = keccak256(keys[i][j] || loc)                    (eth.rs:236-252)
+ *   loc += evm_offset, a 256-bit big-endian add                                                       (eth.rs:253-264)
+ *   mpt_key = keccak256(loc); nibbles[2 k] = mpt_key[k] >> 4, nibbles[2 k + 1] = mpt_key[k] & 15       (eth.rs:267-276)
+ * locations / mpt_keys [count][32], nibbles [count][64] (one nibble per byte: the K public input). keys [count][n_keys][32] are
+ * already left_pad32-ed and in the key order of mp2g_leaf_values_digests; n_keys <= 2: deeper nesting, and a mapping below a struct,
+ * chain two calls through `parents` [count][32] (the locations of the call before). The reference writes a mapping's slot `as u8`
+ * but a simple slot `as u64` (eth.rs:235, :239): slot > 255 with n_keys > 0 and parents NULL is refused, not truncated. The
+ * reference's checked_add(..).unwrap() panics when loc + evm_offset leaves 256 bits: here such a leaf gets all three outputs zeroed
+ * and is counted in *n_overflow (host in both forms; zeroed by the call). The 64-byte message is built in registers and the leaf's
+ * three or four permutations run back to back in one lane: nothing but the outputs touches memory.
+ * Each output pointer may be NULL. Refused before any upload or launch: n_keys > 2, the slot above, keys NULL with n_keys != 0, and
+ * for _dev any of d_parents / d_keys / d_locations / d_mpt_keys / d_nibbles that is not 8-byte aligned. count == 0 launches nothing
+ * and sets *n_overflow to 0. _dev is stream ordered, with one synchronisation when n_overflow is asked for. */
+int mp2g_storage_slot_keys(mp2g_ctx* ctx, uint64_t slot, const uint8_t* parents, const uint8_t* keys, uint32_t n_keys,
+                           uint32_t evm_offset, uint32_t count, uint8_t* locations, uint8_t* mpt_keys, uint8_t* nibbles,
+                           uint32_t* n_overflow);
+int mp2g_storage_slot_keys_dev(mp2g_ctx* ctx, uint64_t slot, const uint8_t* d_parents, const uint8_t* d_keys, uint32_t n_keys,
+                               uint32_t evm_offset, uint32_t count, uint8_t* d_locations, uint8_t* d_mpt_keys, uint8_t* d_nibbles,
+                               uint32_t* n_overflow /* host */);
+/* what mp2g_mpt_storage_leaves found in a node */
+enum mp2g_mpt_leaf_status {
+  MP2G_MPT_LEAF_OK = 0,
+  MP2G_MPT_LEAF_MALFORMED = 1,    /* list or item structure, lengths, a header form above 0xf8 */
+  MP2G_MPT_LEAF_NOT_A_LEAF = 2,   /* first nibble of the path not 2 or 3: extension nodes included */
+  MP2G_MPT_LEAF_BAD_VALUE = 3,    /* item 1 is not the RLP of one string of at most 32 bytes */
+  MP2G_MPT_LEAF_KEY_MISMATCH = 4  /* the path is not the tail of mpt_keys[i] */
+};
+/* MPT storage leaf nodes (mp2-common/src/mpt_sequential/leaf_or_extension.rs:49-87, utils.rs:41-67): nodes [count][stride] bytes,
+ * lens [count]. hashes[i] = keccak256(node i), always written, whatever the status. Then the node is opened as an RLP list: the
+ * header is 0xc0 + L or 0xf8 L with L >= 56, the payload ends exactly at lens[i], and the list holds exactly two string items.
+ * Item 0 is the hex-prefix path (1..33 bytes, at most 64 nibbles): its first nibble is 2 (even) or 3 (odd, the low nibble being the
+ * first path nibble); n_nibbles[i] is the path's nibble count, 0..64. The low nibble of an even path's first byte is not judged.
+ * Item 1's payload is the RLP of the value: a single byte below 0x80, or 0x80 + n followed by n <= 32 bytes that fill the item
+ * exactly. words[i] = left_pad32(value), left_pad_leaf_value's result and the word mp2g_leaf_values_digests takes; the empty string
+ * 0x80 gives the zero word. With mpt_keys [count][32] (or NULL) the path's nibbles must equal the last n_nibbles nibbles of
+ * mpt_keys[i]. status[i] is an mp2g_mpt_leaf_status, judged in that order: structure, the prefix, the value, the key. On a non-zero
+ * status words[i] and n_nibbles[i] are zero. Each of the four outputs may be NULL.
+ * The node's bytes are read at offsets that are all below min(lens[i], stride): a hostile length byte cannot read outside the
+ * node's row. Refused before any upload or launch: stride as for mp2g_keccak256_batch, nodes or lens NULL, in the host form a
+ * lens[i] > stride (named), for _dev a d_nodes / d_hashes / d_words that is not 8-byte aligned (or a d_lens / d_n_nibbles /
+ * d_status that is not 4-byte aligned); in the _dev form (every array on the device) a lane clamps its length to stride. count == 0 launches nothing. _dev is stream ordered. */
+int mp2g_mpt_storage_leaves(mp2g_ctx* ctx, const uint8_t* nodes, uint32_t stride, const uint32_t* lens, const uint8_t* mpt_keys,
+                            uint32_t count, uint8_t* hashes, uint8_t* words, uint32_t* n_nibbles, uint32_t* status);
+int mp2g_mpt_storage_leaves_dev(mp2g_ctx* ctx, const uint8_t* d_nodes, uint32_t stride, const uint32_t* d_lens,
+                                const uint8_t* d_mpt_keys, uint32_t count, uint8_t* d_hashes, uint8_t* d_words, uint32_t* d_n_nibbles,
+                                uint32_t* d_status);
+
 /* ---- proof wire format between tree levels / GPUs ------------------------------------------ */
 /* bincode 1.3 (little-endian fixed-width ints, u64 length prefixes) serialization of plonky2's
  * ProofWithPublicInputs<F, C, 2> exactly as mp2-common/src/proof.rs:84-98 `serialize_proof`

@@ -1063,6 +1063,93 @@ def leaf_values_digests_dev(ctx, variant, col_ids, layout, n_table_columns, d_wo
     return out_w, out_wei, ((sum_w, sum_wei) if total else None)
 
 
+# ---- Keccak-256: storage slot keys and MPT leaf words (csrc/storage.hip; the reference's names: extraction.py) ---------------------
+MPT_LEAF_OK, MPT_LEAF_MALFORMED, MPT_LEAF_NOT_A_LEAF, MPT_LEAF_BAD_VALUE, MPT_LEAF_KEY_MISMATCH = range(5)
+
+
+def rows_at_stride(msgs, stride=None, fill=0):
+    """(uint8 [count][stride], uint32 lens [count]) of a list of byte strings of unequal length (or of a uint8 [count][len] array):
+    one row per message at a stride that is a multiple of 8, the bytes past a message's end set to `fill`"""
+    if isinstance(msgs, np.ndarray):
+        msgs = [bytes(r) for r in np.ascontiguousarray(msgs, dtype=np.uint8).reshape(len(msgs), -1)]
+    lens = np.array([len(m) for m in msgs], dtype=np.uint32)
+    if stride is None:
+        stride = max(8, (int(lens.max(initial=0)) + 7) // 8 * 8)
+    rows = np.full((len(msgs), stride), fill, dtype=np.uint8)
+    for r, m in zip(rows, msgs):
+        r[:min(len(m), stride)] = np.frombuffer(bytes(m)[:stride], dtype=np.uint8)
+    return rows, lens
+
+
+def _opt(a):
+    return None if a is None else _p(a)
+
+
+def keccak256_batch(ctx, msgs, stride=None):
+    """mp2g_keccak256_batch: keccak256 of every message (a list of byte strings of unequal length); uint8 [count][32]. Read as eight
+    little-endian u32 words a digest is pack(Endianness::Little), the H public input."""
+    rows, lens = rows_at_stride(msgs, stride)
+    out = np.zeros((len(lens), 32), dtype=np.uint8)
+    _ck(load().mp2g_keccak256_batch(ctx, _p(rows), rows.shape[1], _p(lens), 0, len(lens), _p(out)))
+    return out
+
+
+def keccak256_batch_dev(ctx, d_msgs, stride, d_lens, length, count, d_out):
+    """mp2g_keccak256_batch_dev: d_msgs [count][stride] (8-byte aligned, stride a multiple of 8), d_lens [count] uint32 or None (every
+    message has `length` bytes) into d_out [count][32]; a device length above stride is clamped; stream ordered"""
+    _ck(load().mp2g_keccak256_batch_dev(ctx, d_msgs, int(stride), d_lens, int(length), int(count), d_out))
+
+
+def storage_slot_keys(ctx, slot, keys=None, n_keys=0, evm_offset=0, parents=None, count=None):
+    """mp2g_storage_slot_keys: StorageSlot::location / mpt_key / mpt_nibbles (eth.rs:233-276) of `count` leaves under `slot` (or under
+    parents [count][32]), keys [count][n_keys][32] left-padded, the outer key first. Returns (locations [count][32], mpt_keys
+    [count][32], nibbles [count][64], number of leaves whose location + evm_offset overflowed and were zeroed)."""
+    n_keys = int(n_keys)
+    k = _bytes32(keys, n_keys) if n_keys else None
+    par = _bytes32(parents) if parents is not None else None
+    if count is None:
+        count = k.shape[0] if k is not None else (par.shape[0] if par is not None else 1)
+    if (k is not None and k.shape[0] != count) or (par is not None and par.shape[0] != count):
+        raise ValueError("one key set and one parent per leaf are needed")
+    loc, key, nib = (np.zeros((count, w), dtype=np.uint8) for w in (32, 32, 64))
+    over = ctypes.c_uint32(0)
+    _ck(load().mp2g_storage_slot_keys(ctx, int(slot), _opt(par), _opt(k), n_keys, int(evm_offset), count, _p(loc), _p(key), _p(nib),
+                                      ctypes.byref(over)))
+    return loc, key, nib, over.value
+
+
+def storage_slot_keys_dev(ctx, slot, d_parents, d_keys, n_keys, evm_offset, count, d_locations=None, d_mpt_keys=None, d_nibbles=None,
+                          overflow=True):
+    """mp2g_storage_slot_keys_dev: the same between device buffers (8-byte aligned; each output may be None). Returns the number of
+    overflowed leaves, or None without `overflow`: then the call is stream ordered."""
+    over = ctypes.c_uint32(0)
+    _ck(load().mp2g_storage_slot_keys_dev(ctx, int(slot), d_parents, d_keys, int(n_keys), int(evm_offset), int(count), d_locations,
+                                          d_mpt_keys, d_nibbles, ctypes.byref(over) if overflow else None))
+    return over.value if overflow else None
+
+
+def mpt_storage_leaves(ctx, nodes, mpt_keys=None, stride=None):
+    """mp2g_mpt_storage_leaves: every MPT storage leaf node (a list of byte strings of unequal length) hashed and opened. Returns
+    (hashes [count][32], words [count][32] = left_pad32(value), n_nibbles [count], status [count] of MPT_LEAF_*); with mpt_keys
+    [count][32] the path must be the key's tail."""
+    rows, lens = rows_at_stride(nodes, stride)
+    count = len(lens)
+    k = _bytes32(mpt_keys) if mpt_keys is not None else None
+    if k is not None and k.shape[0] != count:
+        raise ValueError("one MPT key per node is needed")
+    hashes, words = np.zeros((count, 32), dtype=np.uint8), np.zeros((count, 32), dtype=np.uint8)
+    nib, status = np.zeros(count, dtype=np.uint32), np.zeros(count, dtype=np.uint32)
+    _ck(load().mp2g_mpt_storage_leaves(ctx, _p(rows), rows.shape[1], _p(lens), _opt(k), count, _p(hashes), _p(words), _p(nib), _p(status)))
+    return hashes, words, nib, status
+
+
+def mpt_storage_leaves_dev(ctx, d_nodes, stride, d_lens, d_mpt_keys, count, d_hashes=None, d_words=None, d_n_nibbles=None, d_status=None):
+    """mp2g_mpt_storage_leaves_dev: the same between device buffers (d_nodes, d_hashes, d_words 8-byte aligned; each output may be
+    None); stream ordered"""
+    _ck(load().mp2g_mpt_storage_leaves_dev(ctx, d_nodes, int(stride), d_lens, d_mpt_keys, int(count), d_hashes, d_words, d_n_nibbles,
+                                           d_status))
+
+
 # ---- node hashes of a table's trees (csrc/index_hash.hip) ------------------------------------
 class TreeShape:
     """mp2g_tree_shape: a binary tree or forest over nodes 0..n-1 by its children arrays (-1 = no child), checked and levelled on
