@@ -24,7 +24,10 @@ typedef uint32_t u32;
 // round 6, profiles/r06/ubench.txt): register move 0.79 (rounds 2-5 had inferred ~0.4 from A/B residuals), any 32-bit VALU operation
 // 0.85, v_cndmask with an SGPR condition 1.5, 64-bit add WITHOUT carry-out (v_lshl_add_u64) 1.5-1.6, v_mad_u64_u32 1.7, a carry-chain
 // instruction inside an asm chain 1.2, an add_co / addc pair with the hazard nop hipcc puts between them 4.4, a compare ~2.5, a 64-bit
-// compare + select + add 6.2. Hence the rules below: a carry (or borrow)
+// compare + select + add 6.2. A move is not free in context either: a word that has to enter a 64-bit addend slot costs two moves and
+// the 64-bit add, and where it can enter as the multiplicand of a v_mad_u64_u32 by one instead (read in place from any register, odd or
+// even) the permutation gains -- 55 moves and 28 adds a round of Poseidon2's internal layer for 31 such multiply-adds, +2.7 %
+// (profiles/p2_carry; alone in a stream the two forms cost the same, 1.54 against 1.59 slots). Hence the rules below: a carry (or borrow)
 // is taken from an add_co / addc pair or from the multiply-add's own carry-out only where the value really can wrap; every
 // correction that provably cannot wrap is a carry-less 64-bit add of a mask; sums of products go through carry-free columns
 // (gl_cols) or ride in the addend slots of the multiply-adds (gl_mul_add_wide); compares are avoided altogether.
@@ -218,8 +221,8 @@ GLHD u64 gl_mul_add(u64 a, u64 b, u64 c) { return gl_canon(gl_mul_addw(a, b, c))
 // a * d + c as some u64 representative for a CONSTANT d whose fold e = d 2^32 mod p is known when the library is built: with
 // a = a0 + 2^32 a1 the integer X = a0 d + a1 e + c is congruent to a d + c and has 97 bits at most, not 128, so the tail is
 // gl_reduce96w (one multiply-add, one select, one carry-less add) where gl_mul_addw pays gl_reduce128w with its subtract chain: 16.2
-// (narrow) and 18.7 (any pair) against 23.7 issue slots (tools/ubench, profiles/p2_diag). a, c: any u64; d, e: canonical and
-// wave-uniform (they are read from SGPRs), e = d 2^32 (mod p). Write d = d0 + 2^32 d1, e = e0 + 2^32 e1, c = c0 + 2^32 c1, M = 2^32 - 1:
+// (narrow; 15.4 re-associated, below) and 18.7 (any pair) against 23.7 issue slots (tools/ubench, profiles/p2_diag). a, c: any u64;
+// d, e: canonical and wave-uniform (they are read from SGPRs), e = d 2^32 (mod p). Write d = d0 + 2^32 d1, e = e0 + 2^32 e1, c = c0 + 2^32 c1, M = 2^32 - 1:
 //   p0 = a0 d0 + c0               <= M^2 + M         = 2^64 - 2^32
 //   p1 = a0 d1 + (p0 >> 32) + c1  <= M d1 + 2 M      <= 2^64 - 1                a0 d + c = lo32(p0) + 2^32 p1
 //   q0 = a1 e0 + lo32(p0)         <= M^2 + M         = 2^64 - 2^32
@@ -235,26 +238,47 @@ GLHD u64 gl_mul_add(u64 a, u64 b, u64 c) { return gl_canon(gl_mul_addw(a, b, c))
 // Either way X = lo32(q0) + 2^32 lo32(q1) + 2^64 (q1 >> 32) (mod p) with a top word below 2^32, which is what gl_reduce96w takes for any
 // lo. Hazards as in gl_reduce128w: the carry pair is read by one v_cndmask two wait states after the multiply-add that wrote it.
 #define GL_MULC_NARROW(d, e) (((d) >> 32) + ((e) >> 32) <= 0xFFFFFFFDULL)
-// The four multiply-adds are spelled out and kept in program order (asm volatile; the three that cannot carry name VCC as the carry
+// The multiply-adds are spelled out and kept in program order (asm volatile; those that cannot carry name VCC as the carry
 // they do not use): left to the compiler the last one loses its addend to a separate 64-bit add and the products of neighbouring
 // limbs interleave, which costs 10-20 VGPRs in the sponge kernels (an occupancy step) and 2 % of the permutation.
+// The NARROW form is re-associated: the same integer columns, but each product's carry word (the odd register of its pair) enters the
+// next column as the MULTIPLICAND of a multiply-add by one, which reads a 32-bit word from any register, where the order above has it
+// moved into an aligned (word, 0) pair and added with a 64-bit add. The addends that remain are [c0, 0] and [c1, 0], which all twelve
+// limbs of the internal layer share, and [lo32(p0), 0]:
+//   p0 = a0 d0 + c0               <= M^2 + M         = 2^64 - 2^32          q0 = a1 e0 + lo32(p0)   <= M^2 + M
+//   p1 = a0 d1 + c1               <= M d1 + M                               q1 = a1 e1 + t          <= M (d1 + e1) + 2 M
+//   t  = (p0 >> 32) 1 + p1        <= M d1 + 2 M      <= 2^64 - 1            u  = (q0 >> 32) 1 + q1  <= M (d1 + e1) + 3 M <= 2^64 - 2^32
+// t is the p1 of the table above and u its q1, so their bounds carry over: nothing wraps, X = lo32(q0) + 2^32 u. Six multiply-adds,
+// no 64-bit add and two moves fewer a product than the order above: 15.4 against 16.6 issue slots, the permutation 3.20 -> 3.26
+// G perm/s (tools/ubench, profiles/p2_carry). The pairs that take the carry (limbs 0, 8 and 9) keep the order above.
 template <bool NARROW>
 GLHD u64 gl_mulc_addw(u64 a, u64 d, u64 e, u64 c) {
 #if defined(__HIP_DEVICE_COMPILE__)
   const u32 a0 = (u32)a, a1 = (u32)(a >> 32);
-  u64 p0, p1, q0, q1, k;
+  u64 p0, p1, q0, q1;
 #define GL_MAD_(r, x, y, z) asm volatile("v_mad_u64_u32 %0, vcc, %1, %2, %3" : "=&v"(r) : "v"(x), "s"((u32)(y)), "v"((u64)(z)) : "vcc")
+  if (NARROW) {
+#define GL_MAD1_(r, w, z) asm volatile("v_mad_u64_u32 %0, vcc, %1, 1, %2" : "=&v"(r) : "v"((u32)(w)), "v"((u64)(z)) : "vcc")
+    u64 t, u;
+    GL_MAD_(p0, a0, d, (u64)(u32)c);
+    GL_MAD_(p1, a0, d >> 32, c >> 32);
+    GL_MAD1_(t, p0 >> 32, p1);
+    GL_MAD_(q0, a1, e, p0 & GL_EPS);
+    GL_MAD_(q1, a1, e >> 32, t);
+    GL_MAD1_(u, q0 >> 32, q1);
+#undef GL_MAD1_
+    return gl_reduce96w(gl_mk((u32)q0, (u32)u), u >> 32);
+  }
+  u64 k;
   GL_MAD_(p0, a0, d, (u64)(u32)c);
   GL_MAD_(p1, a0, d >> 32, (p0 >> 32) + (c >> 32));
   GL_MAD_(q0, a1, e, p0 & GL_EPS);
 #undef GL_MAD_
   asm volatile("v_mad_u64_u32 %0, %1, %2, %3, %4" : "=&v"(q1), "=s"(k) : "v"(a1), "s"((u32)(e >> 32)), "v"(p1 + (q0 >> 32)));
-  if (!NARROW) {
-    u32 m;
-    asm("s_nop 1\n\t"  // 2 wait states between the mad's SGPR carry and its first VALU reader
-        "v_cndmask_b32 %0, 0, -1, %1" : "=v"(m) : "s"(k));
-    q1 += (u64)m;
-  }
+  u32 m;
+  asm("s_nop 1\n\t"  // 2 wait states between the mad's SGPR carry and its first VALU reader
+      "v_cndmask_b32 %0, 0, -1, %1" : "=v"(m) : "s"(k));
+  q1 += (u64)m;
   return gl_reduce96w(gl_mk((u32)q0, (u32)q1), q1 >> 32);
 #else
   (void)e;  // the host path is not the target

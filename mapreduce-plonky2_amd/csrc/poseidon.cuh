@@ -127,21 +127,49 @@ GLHD u64 p2_diag_mul_addw(int i, u64 a, u64 c) {
   if ((POSEIDON2_DIAG_NARROW >> i) & 1) return gl_mulc_addw<true>(a, c_p2_diag[i], c_p2_diag_shl32[i], c);
   return gl_mulc_addw<false>(a, c_p2_diag[i], c_p2_diag_shl32[i], c);
 }
+// The sum S of the twelve limbs (any u64 each, so S < 12 2^64 has 68 bits at most) as some u64 representative, without splitting the
+// limbs into zero-extended halves. Write s_i = l_i + 2^32 h_i, L = sum l_i, H = sum h_i (both exact, below 12 2^32), so S = L + 2^32 H:
+//   W = sum s_i mod 2^64            eleven carry-less 64-bit adds on the limbs' own register pairs
+//   H                               twelve multiply-adds by one; as the multiplicand a high word is read in place, from the odd register
+//   c = L >> 32 <= 11               the carry of the low words. hi32(W) = (c + lo32(H)) mod 2^32 and c < 2^32, so
+//                                   c = (hi32(W) - lo32(H)) mod 2^32 exactly: one 32-bit subtract, which may wrap
+//   T = H + c <= 12 M + 11          S = lo32(L) + 2^32 T, and lo32(T) = hi32(W), hence S = W + 2^64 (T >> 32)
+// with a top word T >> 32 <= 11, which gl_reduce96w takes. The multiply-adds are spelled out (asm volatile; they name VCC as the carry
+// they do not use, as in gl_mulc_addw): a multiplication by one written in C is folded back into two moves and a 64-bit add. Against
+// the sum of zero-extended halves (24 moves into aligned pairs, 24 64-bit adds) this is 29.5 moves and 10 adds a round fewer for 13
+// multiply-adds more: the permutation 3.26 -> 3.28 G perm/s on top of the re-associated gl_mulc_addw (tools/ubench, profiles/p2_carry).
+GLD u64 p2_limb_sum(const u64 s[12]) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  u64 w = s[0], ha, hb;
+#pragma unroll
+  for (int i = 1; i < 12; i++) w += s[i];
+#define P2_MAD1_(r, x, z) asm volatile("v_mad_u64_u32 %0, vcc, %1, 1, %2" : "=v"(r) : "v"((u32)((x) >> 32)), "v"(z) : "vcc")
+  asm volatile("v_mad_u64_u32 %0, vcc, %1, 1, 0" : "=v"(ha) : "v"((u32)(s[0] >> 32)) : "vcc");
+  asm volatile("v_mad_u64_u32 %0, vcc, %1, 1, 0" : "=v"(hb) : "v"((u32)(s[1] >> 32)) : "vcc");
+#pragma unroll
+  for (int i = 2; i < 12; i += 2) {  // two chains
+    P2_MAD1_(ha, s[i], ha);
+    P2_MAD1_(hb, s[i + 1], hb);
+  }
+  const u64 h = ha + hb;
+  const u32 c = (u32)(w >> 32) - (u32)h;
+  u64 t;
+  asm volatile("v_mad_u64_u32 %0, vcc, %1, 1, %2" : "=v"(t) : "v"(c), "v"(h) : "vcc");
+#undef P2_MAD1_
+  return gl_reduce96w(w, t >> 32);
+#else
+  unsigned __int128 x = 0;  // device code only: the host pass merely has to parse a body
+  for (int i = 0; i < 12; i++) x += s[i];
+  return gl_reduce96w((u64)x, (u64)(x >> 64));
+#endif
+}
 // s_i <- d_i s_i + sum_j s_j. Device code: sum reduced once, then a weak multiply and a weak add per limb (2.60 -> 2.71 G perm/s against the
 // fused form of the host code below -- 128-bit product plus the 68-bit sum, one reduction --, whose carry chains cost more than the second
 // reduction saves)
 GLHD void p2_internal(u64 s[12]) {
 #if defined(__HIP_DEVICE_COMPILE__)
-  // the 68-bit sum from the 32-bit halves (each v_mad_u64_u32 adds a zero-extended word into a 64-bit accumulator: no carry
-  // chains), reduced ONCE to some representative; every limb is then weak multiply + weak add
-  u64 al = 0, ah = 0;
-#pragma unroll
-  for (int i = 0; i < 12; i++) {
-    al += (u64)(u32)s[i];
-    ah += s[i] >> 32;
-  }
-  ah += al >> 32;  // < 2^37
-  const u64 sum = gl_reduce96w(gl_mk((u32)al, (u32)ah), ah >> 32);  // any representative will do below
+  // the 68-bit sum reduced ONCE to some representative (any will do below); every limb is then weak multiply + weak add
+  const u64 sum = p2_limb_sum(s);
 #pragma unroll
   for (int i = 0; i < 12; i++) {
     s[i] = p2_diag_mul_addw(i, s[i], sum);  // the sum rides in the product's addend slots

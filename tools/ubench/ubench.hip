@@ -154,6 +154,73 @@ GLD void poseidon2_perm_plain(u64 s[12]) {
   for (int i = 0; i < 12; i++) s[i] = gl_canon(s[i]);
 }
 
+// the internal layer as it was before the carries went through multiply-adds by one (the A sides of the `split` / `carry` rows;
+// profiles/p2_carry): the limb sum from zero-extended halves, and the narrow multiply-add with its carry words moved into aligned
+// (word, 0) pairs and added. SUM / MULC choose the old (0) or the present (1) form of each, so that each change has a row of its own.
+GLD u64 gl_mulc_addw_narrow_moves(u64 a, u64 d, u64 e, u64 c) {
+  const u32 a0 = (u32)a, a1 = (u32)(a >> 32);
+  u64 p0, p1, q0, q1, k;
+#define GL_MAD_(r, x, y, z) asm volatile("v_mad_u64_u32 %0, vcc, %1, %2, %3" : "=&v"(r) : "v"(x), "s"((u32)(y)), "v"((u64)(z)) : "vcc")
+  GL_MAD_(p0, a0, d, (u64)(u32)c);
+  GL_MAD_(p1, a0, d >> 32, (p0 >> 32) + (c >> 32));
+  GL_MAD_(q0, a1, e, p0 & GL_EPS);
+#undef GL_MAD_
+  asm volatile("v_mad_u64_u32 %0, %1, %2, %3, %4" : "=&v"(q1), "=s"(k) : "v"(a1), "s"((u32)(e >> 32)), "v"(p1 + (q0 >> 32)));
+  return gl_reduce96w(gl_mk((u32)q0, (u32)q1), q1 >> 32);
+}
+GLD u64 p2_limb_sum_split(const u64 s[12]) {
+  u64 al = 0, ah = 0;
+#pragma unroll
+  for (int i = 0; i < 12; i++) {
+    al += (u64)(u32)s[i];
+    ah += s[i] >> 32;
+  }
+  ah += al >> 32;
+  return gl_reduce96w(gl_mk((u32)al, (u32)ah), ah >> 32);
+}
+template <int SUM, int MULC>
+GLD void p2_internal_ab(u64 s[12]) {
+  const u64 sum = SUM ? p2_limb_sum(s) : p2_limb_sum_split(s);
+#pragma unroll
+  for (int i = 0; i < 12; i++) {
+    if (MULC || !((POSEIDON2_DIAG_NARROW >> i) & 1)) s[i] = p2_diag_mul_addw(i, s[i], sum);
+    else s[i] = gl_mulc_addw_narrow_moves(s[i], c_p2_diag[i], c_p2_diag_shl32[i], sum);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+template <int SUM, int MULC>
+GLD void poseidon2_perm_ab(u64 s[12]) {
+  p2_external_rc<true>(s, c_p2_ext);
+#pragma unroll 1
+  for (int r = 0; r < 4; r++) {
+#pragma unroll
+    for (int i = 0; i < 12; i++) s[i] = p2_sbox0(s[i]);
+    if (r < 3) p2_external_rc<true>(s, c_p2_ext + 12 * (r + 1)); else p2_external(s);
+  }
+#pragma unroll 11
+  for (int r = 0; r < 22; r++) {
+    s[0] = p2_sbox0(gl_addw(s[0], c_p2_int[r]));
+    p2_internal_ab<SUM, MULC>(s);
+  }
+#pragma unroll
+  for (int i = 0; i < 12; i++) s[i] = gl_addw(s[i], c_p2_ext[48 + i]);
+#pragma unroll 1
+  for (int r = 4; r < 8; r++) {
+#pragma unroll
+    for (int i = 0; i < 12; i++) s[i] = p2_sbox0(s[i]);
+    if (r < 7) p2_external_rc<true>(s, c_p2_ext + 12 * (r + 1)); else p2_external(s);
+  }
+#pragma unroll
+  for (int i = 0; i < 12; i++) s[i] = gl_canon(s[i]);
+}
+template <int SUM, int MULC>
+__global__ void __launch_bounds__(256) kperm_ab(u64* out, u64 seed, int reps) {
+  u64 s[12];
+  for (int i = 0; i < 12; i++) s[i] = (seed * (threadIdx.x + 1 + i * 977) + blockIdx.x) % GL_P;
+  for (int r = 0; r < reps; r++) poseidon2_perm_ab<SUM, MULC>(s);
+  out[blockIdx.x * blockDim.x + threadIdx.x] = s[0];
+}
+
 template <int OP>
 __global__ void __launch_bounds__(256) k(u64* out, u64 seed) {
   u64 a[8];
@@ -195,6 +262,7 @@ __global__ void __launch_bounds__(256) k(u64* out, u64 seed) {
       if (OP == 30) a[i] = gl_mulc_addw<false>(a[i], c_p2_diag[i & 1 ? 8 : 9], c_p2_diag_shl32[i & 1 ? 8 : 9], a[(i + 1) & 7]);               // wide limbs 8, 9, the carry folded in
       if (OP == 31) a[i] = gl_mulw_k(a[i], a[(i + 1) & 7]);                                                                               // the S-boxes' product: one middle accumulator, its carry from the multiply-add
       if (OP == 28) a[i] = gl_mulc_addw<true>(a[i], c_p2_diag[1 + (i & 3) * 2], c_p2_diag_shl32[1 + (i & 3) * 2], a[(i + 1) & 7]);  // narrow limbs 1, 3, 5, 7
+      if (OP == 32) a[i] = gl_mulc_addw_narrow_moves(a[i], c_p2_diag[1 + (i & 3) * 2], c_p2_diag_shl32[1 + (i & 3) * 2], a[(i + 1) & 7]);  // the same with the carry words moved and added
     }
   }
   u64 r = 0;
@@ -324,7 +392,7 @@ int main() {
     u64 h = 1; hipMemcpy(&h, bad, 8, hipMemcpyDeviceToHost);
     printf("asm reduce mismatches: %llu\n", (unsigned long long)h);
   }
-  const char* names[] = {"gl_mul", "v_mad_u64_u32", "add64", "cmp+sel+add64", "mul_lo_u32", "mul_hi_u32", "gl_add", "add32", "gl_mul_small", "add_co+addc", "cmp32+sel", "mulw(64bit)", "mulw(32chain)", "mul_wide", "red(64bit)", "red(32chain)", "gl_sub", "gl_addw", "mulw(asm red)", "red(asm)", "red(asm2)", "red(asm3)", "mulw(asm3)", "mul 2^24", "mul 2^48", "mul 2^72", "gl_canon", "mul_addw(diag)", "mulc_addw<narrow>", "mul_addw(wide d)", "mulc_addw<any>", "mulw_k(carry)"};
+  const char* names[] = {"gl_mul", "v_mad_u64_u32", "add64", "cmp+sel+add64", "mul_lo_u32", "mul_hi_u32", "gl_add", "add32", "gl_mul_small", "add_co+addc", "cmp32+sel", "mulw(64bit)", "mulw(32chain)", "mul_wide", "red(64bit)", "red(32chain)", "gl_sub", "gl_addw", "mulw(asm red)", "red(asm)", "red(asm2)", "red(asm3)", "mulw(asm3)", "mul 2^24", "mul 2^48", "mul 2^72", "gl_canon", "mul_addw(diag)", "mulc_addw<narrow>", "mul_addw(wide d)", "mulc_addw<any>", "mulw_k(carry)", "mulc_addw<narrow,moves>"};
   double ops = (double)blocks * threads * ITERS * 8;
 #define RUN(N) { float ms = timeit([&] { hipLaunchKernelGGL(k<N>, dim3(blocks), dim3(threads), 0, 0, d, 0x9E3779B97F4A7C15ull); }); \
     printf("%-14s %8.3f ms  %8.2f Gop/s (lane-ops)\n", names[N], ms, ops / ms / 1e6); }
@@ -335,7 +403,7 @@ int main() {
 #define RUN(N) { float ms = timeit([&] { hipLaunchKernelGGL(k<N>, dim3(blocks), dim3(threads), 0, 0, d, 0x9E3779B97F4A7C15ull); }); \
     hipError_t e_ = hipGetLastError(); \
     printf("%-14s %8.3f ms  %8.2f Gop/s (lane-ops)  %5.1f slots%s\n", names[N], ms, ops / ms / 1e6, ms / add32_ms, e_ == hipSuccess ? "" : "  LAUNCH FAILED"); }
-  RUN(0) RUN(1) RUN(2) RUN(3) RUN(4) RUN(5) RUN(6) RUN(7) RUN(8) RUN(9) RUN(10) RUN(11) RUN(12) RUN(13) RUN(14) RUN(15) RUN(16) RUN(17) RUN(18) RUN(19) RUN(23) RUN(24) RUN(25) RUN(26) RUN(27) RUN(28) RUN(29) RUN(30) RUN(12) RUN(31)
+  RUN(0) RUN(1) RUN(2) RUN(3) RUN(4) RUN(5) RUN(6) RUN(7) RUN(8) RUN(9) RUN(10) RUN(11) RUN(12) RUN(13) RUN(14) RUN(15) RUN(16) RUN(17) RUN(18) RUN(19) RUN(23) RUN(24) RUN(25) RUN(26) RUN(27) RUN(28) RUN(29) RUN(30) RUN(12) RUN(31) RUN(32) RUN(28)
   {
     const char* inames[] = {"v_mov_b32", "v_lshl_add_u64", "v_mad_u64_u32(asm)", "v_cndmask_b32(sgpr)", "sub_co+subbrev+subb(+xor)", "v_sub_u32", "v_bitop3_b32", "v_add_u32",
                             "v_xor_b32", "mad acc+=zext(w)", "mov,mov,lshl_add acc+=zext(w)", "v_cndmask_b32_e64 vcc", "v_cndmask_b32_e32 vcc", "v_cndmask 0,-1,sgpr",
@@ -374,6 +442,22 @@ int main() {
       for (size_t i = 0; i < ha.size(); i++) diff += ha[i] != hb[i];
     }
     printf("poseidon2_perm plain vs carry: %zu of %zu outputs differ over the three repeats\n", diff, 3 * ha.size());
+    // the internal layer's limb sum and narrow multiply-add, old (0) and present (1) form of each, three repeats in turn (profiles/p2_carry)
+    {
+      std::vector<u64> hv[4];
+      for (auto& v : hv) v.resize(ha.size());
+      diff = 0;
+      for (int rep = 0; rep < 3; rep++) {
+#define RUNAB(S, M) { ms = timeit([&] { hipLaunchKernelGGL((kperm_ab<S, M>), dim3(blocks), dim3(threads), 0, 0, d, 0x9E3779B97F4A7C15ull, reps); }); \
+          printf("poseidon2_perm sum %d mulc %d, repeat %d %8.3f ms  %8.3f Gperm/s\n", S, M, rep, ms, (double)blocks * threads * reps / ms / 1e6); \
+          hipMemcpy(hv[2 * S + M].data(), d, ha.size() * sizeof(u64), hipMemcpyDeviceToHost); }
+        RUNAB(0, 0) RUNAB(1, 0) RUNAB(0, 1) RUNAB(1, 1)
+#undef RUNAB
+        for (int v = 1; v < 4; v++)
+          for (size_t i = 0; i < ha.size(); i++) diff += hv[v][i] != hv[0][i];
+      }
+      printf("poseidon2_perm sum / mulc rows: %zu of %zu outputs differ from the (0, 0) row over the three repeats\n", diff, 9 * ha.size());
+    }
     ms = timeit([&] { hipLaunchKernelGGL(kperm1, dim3(blocks), dim3(threads), 0, 0, d, 0x9E3779B97F4A7C15ull, reps); });
     printf("poseidon_perm  %8.3f ms  %8.3f Gperm/s\n", ms, (double)blocks * threads * reps / ms / 1e6);
   }
