@@ -549,6 +549,126 @@ int mp2g_mpt_storage_leaves_dev(mp2g_ctx* ctx, const uint8_t* d_nodes, uint32_t 
                                 const uint8_t* d_mpt_keys, uint32_t count, uint8_t* d_hashes, uint8_t* d_words, uint32_t* d_n_nibbles,
                                 uint32_t* d_status);
 
+/* ---- MPT inclusion proofs on the device: open nodes, walk paths to the root (csrc/mpt.cuh, csrc/mpt.hip) -------------------------
+ * What ProofQuery::verify_storage_proof / verify_state_proof (mp2-common/src/eth.rs:345-399), the walk of
+ * mpt_sequential/utils.rs:69-121 and its in-circuit twin Circuit::verify_mpt_proof (mpt_sequential/mod.rs:163-234) compute around
+ * a leaf: the leaf is hashed, and for every parent the child's hash is found at the key's nibble in a branch, or after the shared
+ * nibbles of an extension, up to the root. Two stages, split the way the data is shared: the proofs of one table share their upper
+ * nodes, so every distinct node is hashed and opened once (mp2g_mpt_open_nodes), and the proofs are walked over a table of node
+ * indices (mp2g_mpt_verify_paths). Keys have a fixed 64 nibbles (storage and state tries).
+ * Out of scope: exclusion proofs (an empty child is a status, not a proof); embedded children, beyond reporting them; receipt and
+ * transaction tries, whose keys are not 64 nibbles; the per-node DV / N sums of the reference's branch circuit. */
+#define MP2G_MPT_MAX_DEPTH 65 /* 64 branches and a leaf with an empty path */
+/* kinds of a node: bits 0-1 of its info word */
+#define MP2G_MPT_NODE_INVALID 0
+#define MP2G_MPT_NODE_BRANCH 1
+#define MP2G_MPT_NODE_EXTENSION 2
+#define MP2G_MPT_NODE_LEAF 3
+/* why a node is MP2G_MPT_NODE_INVALID: bits 2-4 of its info word */
+enum mp2g_mpt_node_reason {
+  MP2G_MPT_NODE_MALFORMED = 1,      /* list header, an item's header byte or length, a string of a length its place does not allow */
+  MP2G_MPT_NODE_ITEM_COUNT = 2,     /* neither 2 nor 17 items */
+  MP2G_MPT_NODE_EMBEDDED_CHILD = 3, /* a child shorter than 32 bytes embedded in its parent: valid Ethereum, not supported here */
+  MP2G_MPT_NODE_BRANCH_VALUE = 4,   /* item 16 of a branch is not the empty string */
+  MP2G_MPT_NODE_BAD_PREFIX = 5      /* first nibble of the hex-prefix path above 3 */
+};
+/* how the value of a path's leaf is judged */
+#define MP2G_MPT_VALUE_WORD 0    /* storage: the RLP of one string of at most 32 bytes */
+#define MP2G_MPT_VALUE_ACCOUNT 1 /* state: the RLP list [nonce, balance, storageHash, codeHash] */
+#define MP2G_MPT_VALUE_RAW 2     /* not judged */
+/* what mp2g_mpt_verify_paths found on a path */
+enum mp2g_mpt_path_status {
+  MP2G_MPT_PATH_OK = 0,
+  MP2G_MPT_PATH_BAD_PATH = 1,      /* depth outside 1..max_depth, or a node index >= n_nodes */
+  MP2G_MPT_PATH_ROOT_MISMATCH = 2, /* the hash of the node at level 0 is not the root */
+  MP2G_MPT_PATH_HASH_MISMATCH = 3, /* the hash of a node below level 0 is not what its parent holds for the key */
+  MP2G_MPT_PATH_BAD_NODE = 4,      /* a node of kind MP2G_MPT_NODE_INVALID */
+  MP2G_MPT_PATH_LEAF_ABOVE = 5,    /* a leaf above the last level */
+  MP2G_MPT_PATH_NO_LEAF = 6,       /* a branch or an extension at the last level */
+  MP2G_MPT_PATH_KEY_LENGTH = 7,    /* a branch after 64 nibbles, an extension that passes 64, a leaf that does not end at 64 */
+  MP2G_MPT_PATH_EMPTY_CHILD = 8,   /* the branch has no child at the key's nibble: an exclusion proof, which this call does not prove */
+  MP2G_MPT_PATH_KEY_MISMATCH = 9,  /* the nibbles of an extension or of the leaf are not the key's */
+  MP2G_MPT_PATH_BAD_VALUE = 10     /* the leaf's value is not what the mode asks for */
+};
+/* Stage 1. nodes [n_nodes][stride] bytes and lens [n_nodes], laid out as mp2g_keccak256_batch takes its messages: its stride and
+ * alignment rules apply, and a _dev lane clamps its length to the stride. Outputs, each of which may be NULL:
+ *   hashes [n_nodes][32]  keccak256(node), written for every node whatever its structure
+ *   info [n_nodes]        what the node is, packed so that the walk needs no second scan:
+ *     bits 0-1            kind: MP2G_MPT_NODE_INVALID, _BRANCH, _EXTENSION, _LEAF
+ *     bits 2-4            an mp2g_mpt_node_reason when the kind is INVALID (every other bit is then 0), else 0
+ *     bits 5-6            length of the list header (1, 2 or 3)
+ *     bit 7               0
+ *     bits 8-23           branch: 16-bit mask of the non-empty children, bit k for nibble k; bits 24-31 are 0
+ *     bits 8-14           extension / leaf: nibble count of the path (extension 1..64, leaf 0..64); bit 15 is 0
+ *     bits 16-31          extension / leaf: byte offset of item 1's header byte
+ * The rules by which a node is judged, in their order:
+ * 1. List header. Accepted forms: 0xc0+L (L < 56), 0xf8 L (L >= 56), or 0xf9 hi lo (L >= 256). The payload must end exactly at
+ *    lens[i]. Anything else is MALFORMED. (mp2g_mpt_storage_leaves accepts only the first two forms; real 532-byte branch nodes
+ *    start f9 02 11.)
+ * 2. Items. An item is a string: a single byte below 0x80, 0x80+k with k <= 55, or 0xb8 k with k >= 56. Or it is a short list
+ *    0xc0+k, k <= 55. A short list is only recognised, never entered. The items are scanned in order. A header byte outside these
+ *    forms is MALFORMED, and so is an item that runs past the payload: the first such item decides. A node has 2 or 17 items that
+ *    fill the payload exactly. Any other count is ITEM_COUNT; the scan ends where an 18th item begins, without judging it.
+ * 3. 17 items: a branch. Each of items 0..15 is either the empty string 0x80 (mask bit clear) or a 32-byte string 0xa0 ... (mask
+ *    bit set). A list item is EMBEDDED_CHILD. A string of any other length is MALFORMED. Item 16 must be the empty string, else
+ *    BRANCH_VALUE: the keys have a fixed 64 nibbles, so a branch never holds a value. The first offending item decides. With the
+ *    mask, the child at nibble k lies at header_len + k + 32 * popcount(mask & ((1 << k) - 1)) + 1. The walk relies on this.
+ * 4. 2 items: the hex-prefix path is item 0, a string of 1..33 bytes, else MALFORMED. Its first nibble selects the kind: 0 or 1 is
+ *    an extension, 2 or 3 is a leaf, anything else is BAD_PREFIX; an odd first nibble makes the byte's low nibble the first of the
+ *    path, and the low nibble of an even path's first byte is not judged. The nibble count is at most 64; 65 nibbles is MALFORMED.
+ *    For an extension: at least 1 nibble, else MALFORMED; item 1 is a 32-byte string; a list as item 1 is EMBEDDED_CHILD; any other
+ *    item 1 is MALFORMED. For a leaf, item 1 is any string that ends the list (a list is MALFORMED). Its content is judged by the
+ *    walk, per value mode.
+ * Every byte is read at an offset below min(lens[i], stride): a hostile length byte cannot read outside the node's row.
+ * Refused before any upload or launch, with a message that names the argument: stride as for mp2g_keccak256_batch; nodes or lens
+ * NULL; in the host form a lens[i] > stride (named); for _dev a d_nodes / d_hashes that is not 8-byte aligned or a d_lens / d_info
+ * that is not 4-byte aligned. A refused call writes nothing; n_nodes == 0 launches nothing; _dev is stream ordered. */
+int mp2g_mpt_open_nodes(mp2g_ctx* ctx, const uint8_t* nodes, uint32_t stride, const uint32_t* lens, uint32_t n_nodes, uint8_t* hashes,
+                        uint32_t* info);
+int mp2g_mpt_open_nodes_dev(mp2g_ctx* ctx, const uint8_t* d_nodes, uint32_t stride, const uint32_t* d_lens, uint32_t n_nodes,
+                            uint8_t* d_hashes, uint32_t* d_info);
+/* Stage 2, one lane per proof. The node table with stage 1's hashes and info (the host form takes the table alone and runs stage
+ * 1 itself); paths [count][max_depth] node indices, root first, as eth_getProof orders them; depths [count]; mpt_keys [count][32];
+ * roots with root_stride 0 (one root for all paths) or 32 (one per path), or roots NULL: the root is not checked; a value mode.
+ * max_depth is at most MP2G_MPT_MAX_DEPTH.
+ * The walk starts with ptr = 0 (nibbles consumed) and expected = root. For level l = 0 .. depth-1:
+ * 1. Index. depth outside 1..max_depth, or an index >= n_nodes, is BAD_PATH.
+ * 2. Hash. hashes[idx] != expected is ROOT_MISMATCH at level 0 and HASH_MISMATCH below it.
+ * 3. Node. Kind 0 is BAD_NODE (so is, in the _dev form, an info word that does not fit its node's length: no bit of it is trusted
+ *    for a read).
+ * 4. Position. A leaf above the last level is LEAF_ABOVE. A non-leaf at the last level is NO_LEAF.
+ * 5. Branch. ptr == 64 is KEY_LENGTH. A clear mask bit for nibble key[ptr] is EMPTY_CHILD. Otherwise expected becomes that child
+ *    and ptr becomes ptr + 1.
+ * 6. Extension with n nibbles. ptr + n > 64 is KEY_LENGTH. The nibbles are compared with key[ptr .. ptr+n): a difference is
+ *    KEY_MISMATCH. expected becomes item 1 and ptr becomes ptr + n.
+ * 7. Leaf with n nibbles. ptr + n != 64 is KEY_LENGTH. The nibbles are compared, and a difference is KEY_MISMATCH. Then the value,
+ *    item 1's payload, is judged by mode:
+ *      MP2G_MPT_VALUE_WORD     the RLP of one string of <= 32 bytes, by exactly the rules of mp2g_mpt_storage_leaves, else BAD_VALUE;
+ *                              words[i] = left_pad32(value)
+ *      MP2G_MPT_VALUE_ACCOUNT  an RLP list (0xc0+L or 0xf8 L) of exactly four strings that fills the payload, items 2 and 3 of 32
+ *                              bytes (nonce, balance, storageHash, codeHash), else BAD_VALUE; words[i] = item 2, the storage root
+ *      MP2G_MPT_VALUE_RAW      not judged, and words is not written
+ * The first failing level decides; within a level the order is the one above. The words of an ACCOUNT call are, as they lie on the
+ * device, the roots (root_stride 32) of a WORD call: state root -> account -> storage root -> leaf word without a download.
+ * Outputs, each of which may be NULL: status [count], an mp2g_mpt_path_status; fail_level [count], 0 on success; words [count][32],
+ * zero on failure; val_off / val_len [count], item 1's payload inside the leaf node, zero on failure; consumed [count][max_depth]
+ * (bytes): the value of ptr on entering each level, which is what the reference's key pointer counts from the other end, 0xff for
+ * the levels after the failing one or past depth (all of them when depth itself is refused).
+ * Refused before any upload or launch, with a message that names the argument: the table as for mp2g_mpt_open_nodes; NULL paths,
+ * depths, mpt_keys, d_hashes or d_info; max_depth 0 or above 65; a root_stride that is neither 0 nor 32; an unknown mode; in the
+ * host form the first depths[i] above max_depth (named); for _dev d_nodes / d_hashes / d_roots / d_words not 8-byte aligned, any
+ * u32 array not 4-byte aligned. A path index >= n_nodes is a per-proof status, not a refusal. A refused call writes nothing;
+ * count == 0 launches nothing; _dev is stream ordered. */
+int mp2g_mpt_verify_paths(mp2g_ctx* ctx, const uint8_t* nodes, uint32_t stride, const uint32_t* lens, uint32_t n_nodes,
+                          const uint32_t* paths, const uint32_t* depths, uint32_t max_depth, const uint8_t* mpt_keys, uint32_t count,
+                          const uint8_t* roots, uint32_t root_stride, uint32_t mode, uint32_t* status, uint32_t* fail_level,
+                          uint8_t* words, uint32_t* val_off, uint32_t* val_len, uint8_t* consumed);
+int mp2g_mpt_verify_paths_dev(mp2g_ctx* ctx, const uint8_t* d_nodes, uint32_t stride, const uint32_t* d_lens, const uint8_t* d_hashes,
+                              const uint32_t* d_info, uint32_t n_nodes, const uint32_t* d_paths, const uint32_t* d_depths,
+                              uint32_t max_depth, const uint8_t* d_mpt_keys, uint32_t count, const uint8_t* d_roots,
+                              uint32_t root_stride, uint32_t mode, uint32_t* d_status, uint32_t* d_fail_level, uint8_t* d_words,
+                              uint32_t* d_val_off, uint32_t* d_val_len, uint8_t* d_consumed);
+
 /* ---- proof wire format between tree levels / GPUs ------------------------------------------ */
 /* bincode 1.3 (little-endian fixed-width ints, u64 length prefixes) serialization of plonky2's
  * ProofWithPublicInputs<F, C, 2> exactly as mp2-common/src/proof.rs:84-98 `serialize_proof`

@@ -1150,6 +1150,64 @@ def mpt_storage_leaves_dev(ctx, d_nodes, stride, d_lens, d_mpt_keys, count, d_ha
                                            d_status))
 
 
+# ---- MPT inclusion proofs: nodes opened once, paths walked to the root (csrc/mpt.hip; the proof sets: extraction.py) ----------------
+MPT_MAX_DEPTH = 65
+MPT_NODE_INVALID, MPT_NODE_BRANCH, MPT_NODE_EXTENSION, MPT_NODE_LEAF = range(4)
+MPT_NODE_MALFORMED, MPT_NODE_ITEM_COUNT, MPT_NODE_EMBEDDED_CHILD, MPT_NODE_BRANCH_VALUE, MPT_NODE_BAD_PREFIX = range(1, 6)
+MPT_VALUE_WORD, MPT_VALUE_ACCOUNT, MPT_VALUE_RAW = range(3)
+(MPT_PATH_OK, MPT_PATH_BAD_PATH, MPT_PATH_ROOT_MISMATCH, MPT_PATH_HASH_MISMATCH, MPT_PATH_BAD_NODE, MPT_PATH_LEAF_ABOVE, MPT_PATH_NO_LEAF,
+ MPT_PATH_KEY_LENGTH, MPT_PATH_EMPTY_CHILD, MPT_PATH_KEY_MISMATCH, MPT_PATH_BAD_VALUE) = range(11)
+MPT_PATH_OUTPUTS = ("status", "fail_level", "words", "val_off", "val_len", "consumed")
+
+
+def mpt_open_nodes(ctx, nodes, stride=None):
+    """mp2g_mpt_open_nodes: every node (a list of byte strings of unequal length) hashed and opened. Returns (hashes [n_nodes][32],
+    info [n_nodes] uint32: kind, reason, header length, branch mask or nibble count and item 1's offset, as include/mp2g.h packs
+    them)."""
+    rows, lens = rows_at_stride(nodes, stride)
+    hashes, info = np.zeros((len(lens), 32), dtype=np.uint8), np.zeros(len(lens), dtype=np.uint32)
+    _ck(load().mp2g_mpt_open_nodes(ctx, _p(rows), rows.shape[1], _p(lens), len(lens), _p(hashes), _p(info)))
+    return hashes, info
+
+
+def mpt_open_nodes_dev(ctx, d_nodes, stride, d_lens, n_nodes, d_hashes=None, d_info=None):
+    """mp2g_mpt_open_nodes_dev: the same between device buffers (d_nodes, d_hashes 8-byte aligned; each output may be None); stream
+    ordered"""
+    _ck(load().mp2g_mpt_open_nodes_dev(ctx, d_nodes, int(stride), d_lens, int(n_nodes), d_hashes, d_info))
+
+
+def mpt_verify_paths(ctx, nodes, paths, depths, mpt_keys, roots=None, mode=MPT_VALUE_WORD, stride=None):
+    """mp2g_mpt_verify_paths: the proofs paths [count][max_depth] (indices into `nodes`, a list of byte strings; the root first) of
+    depths [count] walked under mpt_keys [count][32]. roots: None (not checked), 32 bytes (one root for all) or [count][32]. Returns
+    a dict of MPT_PATH_OUTPUTS: status (MPT_PATH_*), fail_level, words [count][32], val_off, val_len, consumed [count][max_depth]."""
+    rows, lens = rows_at_stride(nodes, stride)
+    paths, depths, k = _arr(paths, np.uint32), _arr(depths, np.uint32).ravel(), _bytes32(mpt_keys)
+    count = depths.size
+    paths = paths.reshape(count, -1) if count else paths.reshape(0, 1)
+    if k.shape[0] != count:
+        raise ValueError("one MPT key per path is needed")
+    r = None if roots is None else _bytes32([roots] if isinstance(roots, (bytes, bytearray)) else roots)
+    if r is not None and r.shape[0] not in (1, count):
+        raise ValueError("one root, or one root per path, is needed")
+    out = {"status": np.zeros(count, dtype=np.uint32), "fail_level": np.zeros(count, dtype=np.uint32),
+           "words": np.zeros((count, 32), dtype=np.uint8), "val_off": np.zeros(count, dtype=np.uint32),
+           "val_len": np.zeros(count, dtype=np.uint32), "consumed": np.zeros(paths.shape, dtype=np.uint8)}
+    root_stride = 32 if r is not None and r.shape[0] == count else 0
+    _ck(load().mp2g_mpt_verify_paths(ctx, _p(rows), rows.shape[1], _p(lens), len(lens), _p(paths), _p(depths), paths.shape[1], _p(k), count,
+                                     _opt(r), root_stride, int(mode), *(_p(out[name]) for name in MPT_PATH_OUTPUTS)))
+    return out
+
+
+def mpt_verify_paths_dev(ctx, d_nodes, stride, d_lens, d_hashes, d_info, n_nodes, d_paths, d_depths, max_depth, d_mpt_keys, count,
+                         d_roots=None, root_stride=0, mode=MPT_VALUE_WORD, d_status=None, d_fail_level=None, d_words=None, d_val_off=None,
+                         d_val_len=None, d_consumed=None):
+    """mp2g_mpt_verify_paths_dev: the same between device buffers, over the hashes and info words mpt_open_nodes_dev left (d_nodes,
+    d_hashes, d_roots, d_words 8-byte aligned; d_roots and each output may be None); stream ordered"""
+    _ck(load().mp2g_mpt_verify_paths_dev(ctx, d_nodes, int(stride), d_lens, d_hashes, d_info, int(n_nodes), d_paths, d_depths, int(max_depth),
+                                         d_mpt_keys, int(count), d_roots, int(root_stride), int(mode), d_status, d_fail_level, d_words,
+                                         d_val_off, d_val_len, d_consumed))
+
+
 # ---- node hashes of a table's trees (csrc/index_hash.hip) ------------------------------------
 class TreeShape:
     """mp2g_tree_shape: a binary tree or forest over nodes 0..n-1 by its children arrays (-1 = no child), checked and levelled on

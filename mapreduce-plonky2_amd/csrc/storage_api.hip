@@ -1,25 +1,9 @@
 // C ABI of the Keccak-256 entry points (include/mp2g.h) over the kernels of storage.hip. Every argument is judged on the host
 // before anything is uploaded or launched; a refused call writes no output.
-#include "ctx.h"
-#include "storage.h"
+#include "keccak_args.h"
 
 using namespace mp2g;
 
-static int aligned8(const void* p, const char* name) {
-  if ((uintptr_t)p & 7) return fail("invalid argument: %s is not 8-byte aligned", name);
-  return 0;
-}
-static int stride_arg(uint32_t stride) {
-  if (stride == 0 || stride % 8 || stride > MP2G_KECCAK_MAX_STRIDE)
-    return fail("invalid argument: stride %u is not a multiple of 8 in 8..%d", stride, MP2G_KECCAK_MAX_STRIDE);
-  return 0;
-}
-// the host's lengths against the row
-static int lens_arg(const uint32_t* lens, uint32_t count, uint32_t stride) {
-  for (uint32_t i = 0; i < count; i++)
-    if (lens[i] > stride) return fail("invalid argument: lens: entry %u is %u, above the stride %u", i, lens[i], stride);
-  return 0;
-}
 // everything mp2g_storage_slot_keys[_dev] refuses but its pointers to the leaves
 static int slot_args(uint64_t slot, bool parents, uint32_t n_keys) {
   if (n_keys > MP2G_LEAF_MAX_KEYS)
@@ -27,11 +11,6 @@ static int slot_args(uint64_t slot, bool parents, uint32_t n_keys) {
   if (n_keys && !parents && slot > 255)
     return fail("invalid argument: slot %llu of a mapping is above 255 (the reference writes it as one byte)", (unsigned long long)slot);
   return 0;
-}
-static hipError_t upload(DevBuf& d, const void* src, size_t bytes, hipStream_t st) {
-  hipError_t e = d.alloc(bytes);
-  if (e != hipSuccess) return e;
-  return hipMemcpyAsync(d.p, src, bytes, hipMemcpyHostToDevice, st);
 }
 
 extern "C" {

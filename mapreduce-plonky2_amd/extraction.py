@@ -14,14 +14,20 @@
   StorageSlot, bytes_to_nibbles       mp2-common/src/eth.rs:158-300, mpt_sequential/utils.rs:13-20: simple / mapping / node slots; location,
                                       mpt_key and mpt_nibbles are Keccak-256 and go through the library (csrc/storage.hip)
   storage_leaf_words                  from raw MPT leaf nodes and mapping keys to the leaves' words and values digests, on the device
+  MptProofSet, verify_mpt_proofs      eth.rs:345-399 verify_storage_proof / verify_state_proof, mpt_sequential/utils.rs:69-121: whole
+                                      eth_getProof paths, every distinct node hashed and opened once, every path walked to its root
+                                      (csrc/mpt.hip)
+  account_storage_roots               state root -> account leaf -> storage root, left on the device
+  storage_proof_words                 storage_leaf_words through whole proofs under a storage root
 
 A leaf's `value` is its 32-byte EVM word (MAPPING_LEAF_VALUE_LEN); a mapping key is any byte string of at most 32 bytes."""
 from dataclasses import dataclass
 
 import numpy as np
 
-from . import (POSEIDON2, curve_sum, leaf_values_digests, leaf_values_digests_dev, map_to_curve_batch, mpt_storage_leaves_dev,
-               rows_at_stride, storage_slot_keys, storage_slot_keys_dev)
+from . import (MPT_MAX_DEPTH, MPT_PATH_OUTPUTS, MPT_VALUE_ACCOUNT, MPT_VALUE_RAW, MPT_VALUE_WORD, POSEIDON2, DeviceBuffer, curve_sum,
+               keccak256_batch_dev, leaf_values_digests, leaf_values_digests_dev, map_to_curve_batch, mpt_open_nodes_dev,
+               mpt_storage_leaves_dev, mpt_verify_paths_dev, rows_at_stride, storage_slot_keys, storage_slot_keys_dev)
 from .identifiers import INNER_KEY_ID_PREFIX, KEY_ID_PREFIX, OUTER_KEY_ID_PREFIX
 
 MAX_FIELD_PER_EVM = 32  # the columns one launch takes (MP2G_LEAF_MAX_COLS); the reference's const generic of the same name
@@ -229,6 +235,148 @@ def storage_leaf_words(ctx, nodes, slot, mapping_keys, table_info, extracted_col
         digests = leaf_values_digests_dev(ctx, variant, [c.identifier for c in front], [c.layout() for c in front], len(table_info), d_words,
                                           d_keys, key_ids, evm_word, count, None, each=True, total=True)
         return d_hashes.download((count, 32), np.uint8), d_words.download((count, 32), np.uint8), digests
+    finally:
+        for b in bufs:
+            b.free()
+
+
+# ---- whole proofs: from the leaf up to the storage root, from the account up to the state root ------------------------------------
+class MptProofSet:
+    """The proofs of one trie (the `proof` lists of eth_getProof answers) as the library takes them: `nodes`, every distinct node
+    once, and paths [count][max_depth] of indices into it with depths [count], the root first."""
+
+    def __init__(self, nodes, paths, depths):
+        self.nodes, self.paths, self.depths = nodes, paths, depths
+
+    @classmethod
+    def from_proofs(cls, proofs, leaf_first=False):
+        """proofs: one list of node byte strings per proof, root first as eth_getProof orders them; leaf_first=True takes the
+        order the reference's circuits use (the leaf first, the root last). Nodes are deduplicated by their bytes."""
+        depths = np.array([len(p) for p in proofs], dtype=np.uint32)
+        max_depth = max(1, int(depths.max(initial=1)))
+        if max_depth > MPT_MAX_DEPTH:
+            raise ValueError(f"a proof of {max_depth} nodes is deeper than a 64-nibble key allows ({MPT_MAX_DEPTH})")
+        index, nodes = {}, []
+        paths = np.zeros((len(proofs), max_depth), dtype=np.uint32)
+        for i, proof in enumerate(proofs):
+            for level, node in enumerate(reversed(proof) if leaf_first else proof):
+                node = bytes(node)
+                if node not in index:
+                    index[node] = len(nodes)
+                    nodes.append(node)
+                paths[i, level] = index[node]
+        return cls(nodes, paths, depths)
+
+    def __len__(self):
+        return len(self.depths)
+
+
+def _device_bytes32(ctx, a, count, bufs):
+    """a DeviceBuffer as it is; otherwise `a` ([count][32], or one 32-byte string for all) uploaded and noted in bufs for freeing.
+    Returns (buffer, row stride)"""
+    if isinstance(a, DeviceBuffer):
+        return a, 32
+    rows = np.frombuffer(bytes(a), dtype=np.uint8).reshape(1, 32) if isinstance(a, (bytes, bytearray)) else \
+        np.ascontiguousarray(np.asarray([np.frombuffer(bytes(r), dtype=np.uint8) for r in a]), dtype=np.uint8).reshape(-1, 32)
+    if rows.shape[0] not in (1, count):
+        raise ValueError("one 32-byte row, or one per proof, is needed")
+    bufs.append(ctx.to_device(rows))
+    return bufs[-1], 32 if rows.shape[0] == count else 0
+
+
+def verify_mpt_proofs(ctx, proof_set, mpt_keys, roots, value=MPT_VALUE_WORD, d_words=None, root_stride=32):
+    """Every proof of proof_set walked from its root to its leaf under mpt_keys [count][32]: mpt_open_nodes_dev over the distinct
+    nodes, then mpt_verify_paths_dev. roots: None (not checked), one 32-byte string, [count][32], or a DeviceBuffer of [count][32]
+    (the words an ACCOUNT walk left; with root_stride=0 its first 32 bytes are the one root of all); mpt_keys may be a DeviceBuffer
+    too. value: MPT_VALUE_WORD / _ACCOUNT / _RAW. With d_words (a DeviceBuffer of 32 * count bytes) the words also stay on the
+    device. Returns the outputs by name (MPT_PATH_OUTPUTS) as arrays; nothing is raised for a failing proof: see its status and
+    fail_level."""
+    count, max_depth = len(proof_set), proof_set.paths.shape[1]
+    shapes = {"status": ((count,), np.uint32), "fail_level": ((count,), np.uint32), "words": ((count, 32), np.uint8),
+              "val_off": ((count,), np.uint32), "val_len": ((count,), np.uint32), "consumed": ((count, max_depth), np.uint8)}
+    if not count:
+        return {name: np.zeros(s, dtype=t) for name, (s, t) in shapes.items()}
+    rows, lens = rows_at_stride(proof_set.nodes)
+    n_nodes = len(lens)
+    bufs = []
+    try:
+        for a in (rows, lens, proof_set.paths, proof_set.depths):
+            bufs.append(ctx.to_device(a))
+        d_nodes, d_lens, d_paths, d_depths = bufs
+        d_keys, _ = _device_bytes32(ctx, mpt_keys, count, bufs)
+        if isinstance(roots, DeviceBuffer):
+            d_roots = roots
+        else:
+            d_roots, root_stride = (None, 0) if roots is None else _device_bytes32(ctx, roots, count, bufs)
+        bufs += [ctx.alloc(32 * max(n_nodes, 1)), ctx.alloc(4 * max(n_nodes, 1))]
+        d_hashes, d_info = bufs[-2:]
+        outs = {name: (d_words if name == "words" and d_words is not None else ctx.alloc(int(np.prod(s)) * np.dtype(t).itemsize))
+                for name, (s, t) in shapes.items()}
+        bufs += [b for b in outs.values() if b is not d_words]
+        if value == MPT_VALUE_RAW:
+            outs["words"].upload(np.zeros((count, 32), dtype=np.uint8))
+        mpt_open_nodes_dev(ctx, d_nodes, rows.shape[1], d_lens, n_nodes, d_hashes, d_info)
+        mpt_verify_paths_dev(ctx, d_nodes, rows.shape[1], d_lens, d_hashes, d_info, n_nodes, d_paths, d_depths, max_depth, d_keys, count,
+                             d_roots, root_stride, value, *(outs[name] for name in MPT_PATH_OUTPUTS))
+        return {name: outs[name].download(*shapes[name]) for name in MPT_PATH_OUTPUTS}
+    finally:
+        for b in bufs:
+            b.free()
+
+
+def _first_failure(out, what):
+    if out["status"].any():
+        bad = int(np.flatnonzero(out["status"])[0])
+        raise ValueError(f"{what} {bad} does not verify: status {int(out['status'][bad])} at level {int(out['fail_level'][bad])}")
+
+
+def account_storage_roots(ctx, account_proofs, addresses, state_root):
+    """ProofQuery::verify_state_proof (eth.rs:376-399) of every (accountProof, 20-byte address) under one state root, on the device:
+    the keys are keccak256(address) (keccak256_batch_dev), the leaves are judged as accounts. Returns (a DeviceBuffer of the
+    storage roots [count][32], which the caller frees and may pass as `roots` / `storage_root` of the storage walks, the same as an
+    array); raises ValueError naming the first failing proof, its status and level."""
+    count = len(account_proofs)
+    if len(addresses) != count or any(len(a) != 20 for a in addresses):
+        raise ValueError("one 20-byte address per account proof is needed")
+    rows, _ = rows_at_stride([bytes(a) for a in addresses], 24)
+    d_addr, d_keys, d_roots = ctx.to_device(rows), ctx.alloc(32 * count), ctx.alloc(32 * count)
+    try:
+        keccak256_batch_dev(ctx, d_addr, 24, None, 20, count, d_keys)
+        out = verify_mpt_proofs(ctx, MptProofSet.from_proofs(account_proofs), d_keys, state_root, MPT_VALUE_ACCOUNT, d_words=d_roots)
+        _first_failure(out, "account proof")
+    except BaseException:
+        d_roots.free()
+        raise
+    finally:
+        d_addr.free()
+        d_keys.free()
+    return d_roots, out["words"]
+
+
+def storage_proof_words(ctx, proofs, storage_root, slot, mapping_keys, table_info, extracted_column_identifiers, key_ids, evm_word=0,
+                        variant=POSEIDON2):
+    """What storage_leaf_words does, through whole proofs: from the eth_getProof storage proofs of one (slot, evm_word) of a table
+    and their mapping keys to the leaves' words and values digests without a host computation. storage_slot_keys_dev (the MPT key
+    of every leaf), mpt_open_nodes_dev and mpt_verify_paths_dev (every distinct node hashed and opened once, every path walked from
+    storage_root, 32 bytes or a DeviceBuffer that starts with them, down to its leaf), leaf_values_digests_dev over the words left
+    on the device. Returns (words [count][32], (encodings [count][5], Weierstrass [count][11], (encoding, Weierstrass) of the
+    sum)); raises ValueError naming the first failing proof, its status and level."""
+    count, n_keys = len(proofs), len(mapping_keys)
+    if len(key_ids) != n_keys or any(len(k) != count for k in mapping_keys):
+        raise ValueError("one key identifier per mapping level and one key per proof and level are needed")
+    info, n = extracted_first(table_info, extracted_column_identifiers)
+    front = info[:n]
+    d_keys = ctx.to_device(_keys(*mapping_keys)) if n_keys else None
+    d_mpt, d_words = ctx.alloc(32 * count), ctx.alloc(32 * count)
+    bufs = [b for b in (d_keys, d_mpt, d_words) if b is not None]
+    try:
+        if storage_slot_keys_dev(ctx, slot, None, d_keys, n_keys, evm_word, count, None, d_mpt, None):
+            raise OverflowError("location + evm_word leaves 256 bits")
+        out = verify_mpt_proofs(ctx, MptProofSet.from_proofs(proofs), d_mpt, storage_root, MPT_VALUE_WORD, d_words=d_words, root_stride=0)
+        _first_failure(out, "storage proof")
+        digests = leaf_values_digests_dev(ctx, variant, [c.identifier for c in front], [c.layout() for c in front], len(table_info), d_words,
+                                          d_keys, key_ids, evm_word, count, None, each=True, total=True)
+        return out["words"], digests
     finally:
         for b in bufs:
             b.free()
