@@ -557,7 +557,8 @@ int mp2g_mpt_storage_leaves_dev(mp2g_ctx* ctx, const uint8_t* d_nodes, uint32_t 
  * nodes, so every distinct node is hashed and opened once (mp2g_mpt_open_nodes), and the proofs are walked over a table of node
  * indices (mp2g_mpt_verify_paths). Keys have a fixed 64 nibbles (storage and state tries).
  * Out of scope: exclusion proofs (an empty child is a status, not a proof); embedded children, beyond reporting them; receipt and
- * transaction tries, whose keys are not 64 nibbles; the per-node DV / N sums of the reference's branch circuit. */
+ * transaction tries, whose keys are not 64 nibbles. The per-node DV / N sums of the reference's branch circuit are the next
+ * section's (mp2g_mpt_subtree_digests). */
 #define MP2G_MPT_MAX_DEPTH 65 /* 64 branches and a leaf with an empty path */
 /* kinds of a node: bits 0-1 of its info word */
 #define MP2G_MPT_NODE_INVALID 0
@@ -668,6 +669,64 @@ int mp2g_mpt_verify_paths_dev(mp2g_ctx* ctx, const uint8_t* d_nodes, uint32_t st
                               uint32_t max_depth, const uint8_t* d_mpt_keys, uint32_t count, const uint8_t* d_roots,
                               uint32_t root_stride, uint32_t mode, uint32_t* d_status, uint32_t* d_fail_level, uint8_t* d_words,
                               uint32_t* d_val_off, uint32_t* d_val_len, uint8_t* d_consumed);
+
+/* ---- MPT subtree digests on the device: DV and N of every trie node (csrc/mpt_graph.cuh, csrc/mpt_digest.hip) ---------------------
+ * What every node of the storage trie exposes in the values-extraction proofs (mp2-v1/src/values_extraction/public_inputs.rs:23-36:
+ * H, K, T, DV, DM, N): a branch's DV and N are the sums over its proved children (branch.rs:77-112), an extension passes its
+ * child's on (extension.rs:53-61), a leaf has its own digest and N = 1. The trie's shape is taken from the proofs themselves, over
+ * the node table, info words, paths and keys of mp2g_mpt_verify_paths; node bytes are not read, and no hash is checked again:
+ * d_status [count] is what a walk over the same tables left (NULL: every proof counts as MP2G_MPT_PATH_OK). Whatever the arrays
+ * hold, no index is used before it is held against n_nodes.
+ *
+ * Accepted proofs. Proof i counts when d_status is NULL or d_status[i] is MP2G_MPT_PATH_OK, depths[i] is in 1..max_depth, every
+ * index is below n_nodes, every level but the last is a BRANCH or an EXTENSION and the last a LEAF, and ptr (0 at the root, + 1 at a
+ * branch, + the info word's nibble count at an extension or leaf) never passes 64 and is 64 after the leaf. Any other proof
+ * contributes nothing anywhere and is counted in n_rejected.
+ * Occurrences. An accepted proof gives its node x = path[l] the tuple (parent, level, entered, slot): parent = path[l-1], or
+ * MP2G_MPT_NO_NODE at level 0; level = l; entered = ptr on entering x; slot = the key's nibble at the parent's `entered` below a
+ * branch, 0 below an extension and at level 0. via[x] is the lowest index of an accepted proof through x, and x's reference
+ * occurrence the one at the lowest level of proof via[x].
+ * Conflicts, in this order: (a) an occurrence of x whose tuple is not the reference occurrence's makes x and that occurrence's own
+ * parent MP2G_MPT_SUBTREE_CONFLICT; (b) two different nodes with one (parent, slot) make the parent a CONFLICT (the lower index is
+ * kept as the child); (c) a node with a CONFLICT child is a CONFLICT, up to the root. A node table deduplicated by bytes is not a
+ * tree: two leaves with equal tails and values below two nibbles of one branch are one entry, their digests differ (the mapping
+ * key enters a leaf's digest), and a per-node digest does not exist there. The call says so; it does not sum silently.
+ * Several accepted proofs that end at one leaf node with one tuple are one leaf: it counts once, with the digest of proof via[x].
+ * Sums. d_leaf_frac [count][20]: the leaves' digests by proof, as mp2g_leaf_values_digests_dev leaves them in d_frac_out. A LEAF
+ * takes d_leaf_frac[via[x]] and N = 1; an EXTENSION its child's point and N; a BRANCH the sum (the complete addition) of the
+ * children the proofs showed, in nibble order, and the sum of their N: a child no proof showed costs nothing. A CONFLICT or
+ * UNREACHED node gets the neutral point and N = 0. Points stay in fractional coordinates: compare them through mp2g_curve_emit_dev.
+ * Outputs, each of which may be NULL: d_acc_frac [n_nodes][20] (NULL: no point is read or added, and d_leaf_frac may be NULL);
+ * d_n_leaves, d_state (an mp2g_mpt_subtree_state), d_via, d_parent [n_nodes] u32; d_entered [n_nodes] bytes; totals (host):
+ * rejected proofs, CONFLICT nodes, levels (1 + the deepest level of a reached node). via, parent and entered are the reference
+ * occurrence's, for a CONFLICT node too; an UNREACHED node has via = parent = MP2G_MPT_NO_NODE and entered = 0xff.
+ * Four launches over the proofs (minima; the owner of each node writes its tuple; compare and OR; rule (c)), three over the nodes,
+ * then one launch per level from the deepest up. Launches are the only ordering, every shared word is an integer minimum or an OR,
+ * and no result depends on the schedule. One synchronisation, for the level counts and the totals. The context keeps a working
+ * buffer of 100 bytes per node (64 of them the child table) and one per proof, which grows, with one more synchronisation, when
+ * a call needs more.
+ * Refused before any upload or launch, with a message that names the argument: d_info NULL with n_nodes != 0; d_paths, d_depths or
+ * d_mpt_keys NULL with count != 0; d_leaf_frac NULL with d_acc_frac given and count != 0; max_depth 0 or above 65; d_leaf_frac /
+ * d_acc_frac not 8-byte aligned, any u32 array not 4-byte aligned; d_leaf_frac and d_acc_frac overlapping. A rejected proof and a
+ * conflict are outputs, not refusals. n_nodes == 0 launches nothing (every proof is rejected); count == 0 launches no kernel and
+ * fills the outputs with the UNREACHED values. */
+#define MP2G_MPT_NO_NODE 0xffffffffu
+enum mp2g_mpt_subtree_state { MP2G_MPT_SUBTREE_UNREACHED = 0, MP2G_MPT_SUBTREE_OK = 1, MP2G_MPT_SUBTREE_CONFLICT = 2 };
+int mp2g_mpt_subtree_digests_dev(mp2g_ctx* ctx, const uint32_t* d_info, uint32_t n_nodes, const uint32_t* d_paths, const uint32_t* d_depths,
+                                 uint32_t max_depth, const uint8_t* d_mpt_keys, const uint32_t* d_status /* or NULL */, uint32_t count,
+                                 const uint64_t* d_leaf_frac /* [count][20] */, uint64_t* d_acc_frac /* [n_nodes][20] */,
+                                 uint32_t* d_n_leaves, uint32_t* d_state, uint32_t* d_via, uint32_t* d_parent, uint8_t* d_entered,
+                                 uint32_t totals[3] /* host: rejected proofs, conflict nodes, levels */);
+/* The same from host arrays: the node table, paths, keys, roots and mode as mp2g_mpt_verify_paths takes them, and the leaves'
+ * digests as encodings leaf_w [count][5] (by proof). The call runs mp2g_mpt_open_nodes, mp2g_mpt_verify_paths (status [count], or
+ * NULL, receives its statuses), mp2g_curve_decode_dev, the pass and mp2g_curve_emit_dev itself. out_w [n_nodes][5] /
+ * out_weierstrass [n_nodes][11]: every node's sum; with both NULL no point is decoded or added and leaf_w may be NULL. The other
+ * outputs are the _dev form's, in host memory. Refused: what those calls refuse, and leaf_w NULL when a point output is given. */
+int mp2g_mpt_subtree_digests(mp2g_ctx* ctx, const uint8_t* nodes, uint32_t stride, const uint32_t* lens, uint32_t n_nodes,
+                             const uint32_t* paths, const uint32_t* depths, uint32_t max_depth, const uint8_t* mpt_keys, uint32_t count,
+                             const uint8_t* roots, uint32_t root_stride, uint32_t mode, const uint64_t* leaf_w /* [count][5] */,
+                             uint32_t* status /* [count], out */, uint64_t* out_w /* [n_nodes][5] */, uint64_t* out_weierstrass /* [n_nodes][11] */,
+                             uint32_t* n_leaves, uint32_t* state, uint32_t* via, uint32_t* parent, uint8_t* entered, uint32_t totals[3]);
 
 /* ---- proof wire format between tree levels / GPUs ------------------------------------------ */
 /* bincode 1.3 (little-endian fixed-width ints, u64 length prefixes) serialization of plonky2's

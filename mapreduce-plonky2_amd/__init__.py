@@ -1208,6 +1208,52 @@ def mpt_verify_paths_dev(ctx, d_nodes, stride, d_lens, d_hashes, d_info, n_nodes
                                          d_val_off, d_val_len, d_consumed))
 
 
+# ---- MPT subtree digests: DV and N of every trie node (csrc/mpt_digest.hip; the public-input rows: extraction.py) ------------------
+MPT_NO_NODE = 0xFFFFFFFF
+MPT_SUBTREE_UNREACHED, MPT_SUBTREE_OK, MPT_SUBTREE_CONFLICT = range(3)
+MPT_SUBTREE_OUTPUTS = ("n_leaves", "state", "via", "parent", "entered")
+
+
+def mpt_subtree_digests(ctx, nodes, paths, depths, mpt_keys, leaf_w, roots=None, mode=MPT_VALUE_WORD, stride=None, points=True):
+    """mp2g_mpt_subtree_digests: the proofs as mpt_verify_paths takes them, and the leaves' digests as encodings leaf_w [count][5] by
+    proof. Returns a dict: status [count] (MPT_PATH_*), w [n_nodes][5] and weierstrass [n_nodes][11] (every node's sum; None without
+    `points`, and leaf_w may then be None), n_leaves, state (MPT_SUBTREE_*), via, parent [n_nodes] uint32, entered [n_nodes] uint8,
+    totals (rejected proofs, conflict nodes, levels)."""
+    rows, lens = rows_at_stride(nodes, stride)
+    n = len(lens)
+    paths, depths, k = _arr(paths, np.uint32), _arr(depths, np.uint32).ravel(), _bytes32(mpt_keys)
+    count = depths.size
+    paths = paths.reshape(count, -1) if count else paths.reshape(0, 1)
+    if k.shape[0] != count:
+        raise ValueError("one MPT key per path is needed")
+    r = None if roots is None else _bytes32([roots] if isinstance(roots, (bytes, bytearray)) else roots)
+    if r is not None and r.shape[0] not in (1, count):
+        raise ValueError("one root, or one root per path, is needed")
+    lw = None if leaf_w is None else _arr(leaf_w).reshape(-1, 5)
+    if points and (lw is None or lw.shape[0] != count):
+        raise ValueError("one leaf digest per path is needed")
+    out = {"status": np.zeros(count, dtype=np.uint32), "w": np.zeros((n, 5), dtype=np.uint64) if points else None,
+           "weierstrass": np.zeros((n, 11), dtype=np.uint64) if points else None, "n_leaves": np.zeros(n, dtype=np.uint32),
+           "state": np.zeros(n, dtype=np.uint32), "via": np.zeros(n, dtype=np.uint32), "parent": np.zeros(n, dtype=np.uint32),
+           "entered": np.zeros(n, dtype=np.uint8), "totals": np.zeros(3, dtype=np.uint32)}
+    root_stride = 32 if r is not None and r.shape[0] == count else 0
+    _ck(load().mp2g_mpt_subtree_digests(ctx, _p(rows), rows.shape[1], _p(lens), n, _p(paths), _p(depths), paths.shape[1], _p(k), count, _opt(r),
+                                        root_stride, int(mode), _opt(lw if points else None), _p(out["status"]), _opt(out["w"]),
+                                        _opt(out["weierstrass"]), *(_p(out[name]) for name in MPT_SUBTREE_OUTPUTS), _p(out["totals"])))
+    return out
+
+
+def mpt_subtree_digests_dev(ctx, d_info, n_nodes, d_paths, d_depths, max_depth, d_mpt_keys, d_status, count, d_leaf_frac, d_acc_frac=None,
+                            d_n_leaves=None, d_state=None, d_via=None, d_parent=None, d_entered=None):
+    """mp2g_mpt_subtree_digests_dev: the same between device buffers, over the info words mpt_open_nodes_dev left and the statuses
+    mpt_verify_paths_dev left (d_status None: every proof counts as OK); d_leaf_frac [count][20] as leaf_values_digests_dev leaves
+    its d_frac_out; each output may be None. One synchronisation. Returns (rejected proofs, conflict nodes, levels)."""
+    totals = np.zeros(3, dtype=np.uint32)
+    _ck(load().mp2g_mpt_subtree_digests_dev(ctx, d_info, int(n_nodes), d_paths, d_depths, int(max_depth), d_mpt_keys, d_status, int(count),
+                                            d_leaf_frac, d_acc_frac, d_n_leaves, d_state, d_via, d_parent, d_entered, _p(totals)))
+    return tuple(int(t) for t in totals)
+
+
 # ---- node hashes of a table's trees (csrc/index_hash.hip) ------------------------------------
 class TreeShape:
     """mp2g_tree_shape: a binary tree or forest over nodes 0..n-1 by its children arrays (-1 = no child), checked and levelled on

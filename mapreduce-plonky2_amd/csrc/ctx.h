@@ -49,6 +49,7 @@ struct mp2g_ctx {
   mp2g::DevBuf wit_vals;  // slot tables of the device witness executor (mp2g_witness_program_run_dev), grown on demand
   mp2g::DevBuf wit_rows;  // its row-major staging wire matrices
   mp2g::DevBuf index_work;  // node-major digests of the rows' cells trees (mp2g_cells_tree_hashes_dev), grown on demand
+  mp2g::DevBuf mpt_work;    // the shape of a trie between the passes of mp2g_mpt_subtree_digests_dev (mpt_digest.h), grown on demand
   // The index lists of the update calls (mp2g_cells_tree_hashes_rows_dev, mp2g_row_tree_hashes_update_dev) are host arrays of the
   // caller's that the kernels read on the device. index_lists is their ONE device copy: an upload is ordered on the stream behind the
   // kernels of the call before, so one buffer serves calls queued back to back. What an upload reads on the host must outlive the

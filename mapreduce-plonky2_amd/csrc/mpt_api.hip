@@ -1,29 +1,9 @@
 // C ABI of the MPT inclusion-proof entry points (include/mp2g.h) over the kernels of mpt.hip. Every argument is judged on the host
 // before anything is uploaded or launched; a refused call writes no output.
-#include "keccak_args.h"
+#include "mpt_args.h"
 #include "mpt.h"
 
 using namespace mp2g;
-
-// stride, nodes and lens, as mp2g_keccak256_batch judges its messages; lens on the host only in the host forms
-static int table_args(const uint8_t* nodes, uint32_t stride, const uint32_t* lens, uint32_t n_nodes, bool host) {
-  int rc = stride_arg(stride);
-  if (rc || !n_nodes) return rc;
-  NEED(nodes, "nodes");
-  NEED(lens, "lens");
-  return host ? lens_arg(lens, n_nodes, stride) : 0;
-}
-// everything mp2g_mpt_verify_paths[_dev] refuses but its node table and the alignment of device pointers
-static int walk_args(const uint32_t* paths, const uint32_t* depths, uint32_t max_depth, const uint8_t* mpt_keys, uint32_t root_stride,
-                     uint32_t mode) {
-  if (max_depth == 0 || max_depth > MP2G_MPT_MAX_DEPTH) return fail("invalid argument: max_depth %u is not in 1..%d", max_depth, MP2G_MPT_MAX_DEPTH);
-  if (root_stride != 0 && root_stride != 32) return fail("invalid argument: root_stride %u is neither 0 nor 32", root_stride);
-  if (mode > MP2G_MPT_VALUE_RAW) return fail("invalid argument: mode %u is not an MP2G_MPT_VALUE_*", mode);
-  NEED(paths, "paths");
-  NEED(depths, "depths");
-  NEED(mpt_keys, "mpt_keys");
-  return 0;
-}
 
 extern "C" {
 
@@ -85,8 +65,7 @@ int mp2g_mpt_verify_paths(mp2g_ctx* c, const uint8_t* nodes, uint32_t stride, co
                           uint32_t* val_len, uint8_t* consumed) {
   int rc = table_args(nodes, stride, lens, n_nodes, true);
   if (rc || (rc = walk_args(paths, depths, max_depth, mpt_keys, root_stride, mode))) return rc;
-  for (uint32_t i = 0; i < count; i++)
-    if (depths[i] > max_depth) return fail("invalid argument: depths: entry %u is %u, above max_depth %u", i, depths[i], max_depth);
+  if ((rc = depths_arg(depths, count, max_depth))) return rc;
   if (!count) return 0;
   NEED(c, "ctx");
   const bool word = mode != MP2G_MPT_VALUE_RAW && words;

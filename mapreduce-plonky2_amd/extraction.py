@@ -19,15 +19,20 @@
                                       (csrc/mpt.hip)
   account_storage_roots               state root -> account leaf -> storage root, left on the device
   storage_proof_words                 storage_leaf_words through whole proofs under a storage root
+  mpt_subtree_digests                 values_extraction/branch.rs:77-112, extension.rs:53-61: DV and N of every node of the trie the
+                                      proofs show, summed up the trie on the device (csrc/mpt_digest.hip)
+  values_extraction_public_inputs     values_extraction/public_inputs.rs:23-36: H, K, T, DV, DM, N of every node
+  storage_proof_tree                  storage_proof_words carried on to every node's public inputs
 
 A leaf's `value` is its 32-byte EVM word (MAPPING_LEAF_VALUE_LEN); a mapping key is any byte string of at most 32 bytes."""
 from dataclasses import dataclass
 
 import numpy as np
 
-from . import (MPT_MAX_DEPTH, MPT_PATH_OUTPUTS, MPT_VALUE_ACCOUNT, MPT_VALUE_RAW, MPT_VALUE_WORD, POSEIDON2, DeviceBuffer, curve_sum,
-               keccak256_batch_dev, leaf_values_digests, leaf_values_digests_dev, map_to_curve_batch, mpt_open_nodes_dev,
-               mpt_storage_leaves_dev, mpt_verify_paths_dev, rows_at_stride, storage_slot_keys, storage_slot_keys_dev)
+from . import (MPT_MAX_DEPTH, MPT_NODE_BRANCH, MPT_NO_NODE, MPT_PATH_OUTPUTS, MPT_SUBTREE_OUTPUTS, MPT_VALUE_ACCOUNT, MPT_VALUE_RAW, MPT_VALUE_WORD, POSEIDON2,
+               DeviceBuffer, curve_emit_dev, curve_sum, keccak256_batch_dev, leaf_values_digests, leaf_values_digests_dev, map_to_curve_batch,
+               mpt_open_nodes_dev, mpt_storage_leaves_dev, mpt_subtree_digests_dev, mpt_verify_paths_dev, rows_at_stride, storage_slot_keys,
+               storage_slot_keys_dev)
 from .identifiers import INNER_KEY_ID_PREFIX, KEY_ID_PREFIX, OUTER_KEY_ID_PREFIX
 
 MAX_FIELD_PER_EVM = 32  # the columns one launch takes (MP2G_LEAF_MAX_COLS); the reference's const generic of the same name
@@ -249,22 +254,40 @@ class MptProofSet:
         self.nodes, self.paths, self.depths = nodes, paths, depths
 
     @classmethod
-    def from_proofs(cls, proofs, leaf_first=False):
+    def from_proofs(cls, proofs, leaf_first=False, by_position=False, mpt_keys=None, node_info=None):
         """proofs: one list of node byte strings per proof, root first as eth_getProof orders them; leaf_first=True takes the
-        order the reference's circuits use (the leaf first, the root last). Nodes are deduplicated by their bytes."""
+        order the reference's circuits use (the leaf first, the root last). Nodes are deduplicated by their bytes. With
+        by_position=True a node is identified by (its parent's index, its slot below that parent, its bytes): the table is then a
+        tree by construction, which mpt_subtree_digests needs. The slot is include/mp2g.h's: the key's nibble at the parent's
+        `entered` below a branch, 0 below an extension and at the root. It needs mpt_keys (one 32-byte key per proof) and node_info
+        ({node bytes: its info word}, as mpt_open_nodes gives them for the table by bytes: no node is parsed here). Without them
+        the slot is 0 everywhere: two leaves with equal tails and values below two nibbles of one branch share their parent and
+        their bytes, the table then holds them once, and the subtree call reports the conflict."""
         depths = np.array([len(p) for p in proofs], dtype=np.uint32)
         max_depth = max(1, int(depths.max(initial=1)))
         if max_depth > MPT_MAX_DEPTH:
             raise ValueError(f"a proof of {max_depth} nodes is deeper than a 64-nibble key allows ({MPT_MAX_DEPTH})")
+        if (mpt_keys is None) != (node_info is None):
+            raise ValueError("the slots need both the MPT keys and the nodes' info words")
+        if mpt_keys is not None and len(mpt_keys) != len(proofs):
+            raise ValueError("one MPT key per proof is needed")
         index, nodes = {}, []
         paths = np.zeros((len(proofs), max_depth), dtype=np.uint32)
         for i, proof in enumerate(proofs):
+            nib = bytes_to_nibbles(bytes(mpt_keys[i])) if by_position and mpt_keys is not None else None
+            parent, ptr, slot = None, 0, 0
             for level, node in enumerate(reversed(proof) if leaf_first else proof):
                 node = bytes(node)
-                if node not in index:
-                    index[node] = len(nodes)
+                name = (parent, slot, node) if by_position else node
+                if name not in index:
+                    index[name] = len(nodes)
                     nodes.append(node)
-                paths[i, level] = index[node]
+                paths[i, level] = parent = index[name]
+                if nib is not None:
+                    word = int(node_info[node])
+                    branch = word & 3 == MPT_NODE_BRANCH
+                    slot = nib[ptr] if branch and ptr < 64 else 0
+                    ptr += 1 if branch else word >> 8 & 0x7F
         return cls(nodes, paths, depths)
 
     def __len__(self):
@@ -377,6 +400,128 @@ def storage_proof_words(ctx, proofs, storage_root, slot, mapping_keys, table_inf
         digests = leaf_values_digests_dev(ctx, variant, [c.identifier for c in front], [c.layout() for c in front], len(table_info), d_words,
                                           d_keys, key_ids, evm_word, count, None, each=True, total=True)
         return out["words"], digests
+    finally:
+        for b in bufs:
+            b.free()
+
+
+# ---- every node of the trie: the public inputs of the values-extraction proofs ---------------------------------------------------
+GOLDILOCKS_P = 0xFFFFFFFF00000001
+NEUTRAL_WEIERSTRASS = (0,) * 10 + (1,)
+PUBLIC_INPUT_LEN = 96  # H 8, K 64, T 1, DV 11, DM 11, N 1 (public_inputs.rs:23-36)
+
+
+def mpt_subtree_digests(ctx, proof_set, mpt_keys, d_status, d_leaf_frac, d_info=None, points=True):
+    """DV and N of every node of the trie the proofs of proof_set show (mpt_subtree_digests_dev). mpt_keys [count][32] (an array or
+    a DeviceBuffer); d_status: the statuses verify over the same set left on the device, or None (every proof counts as OK);
+    d_leaf_frac: the leaves' digests by proof, as leaf_values_digests_dev leaves them in d_frac_out (None without `points`);
+    d_info: stage 1's info words when they are on the device already, otherwise the nodes are opened here. A per-node digest
+    needs node = position: build the set with by_position=True, or read the CONFLICT states. Returns the outputs by name: w
+    [n_nodes][5], weierstrass [n_nodes][11] (None without `points`), n_leaves, state, via, parent (uint32), entered (uint8),
+    totals (rejected proofs, conflict nodes, levels), and hashes / info when the nodes were opened here."""
+    count, max_depth, n = len(proof_set), proof_set.paths.shape[1], len(proof_set.nodes)
+    out = {"w": None, "weierstrass": None, "hashes": None, "info": None}
+    shapes = {"n_leaves": np.uint32, "state": np.uint32, "via": np.uint32, "parent": np.uint32, "entered": np.uint8}
+    bufs = []
+    try:
+        d_paths = d_depths = d_keys = None
+        if count:
+            d_paths, d_depths = ctx.to_device(proof_set.paths), ctx.to_device(proof_set.depths)
+            bufs += [d_paths, d_depths]
+            d_keys = _device_bytes32(ctx, mpt_keys, count, bufs)[0]
+        if d_info is None and n:
+            rows, lens = rows_at_stride(proof_set.nodes)
+            d_nodes, d_lens, d_hashes, d_info = ctx.to_device(rows), ctx.to_device(lens), ctx.alloc(32 * max(n, 1)), ctx.alloc(4 * max(n, 1))
+            bufs += [d_nodes, d_lens, d_hashes, d_info]
+            mpt_open_nodes_dev(ctx, d_nodes, rows.shape[1], d_lens, n, d_hashes, d_info)
+            out["hashes"], out["info"] = d_hashes.download((n, 32), np.uint8), d_info.download((n,), np.uint32)
+        d_acc = ctx.alloc(160 * max(n, 1)) if points else None
+        d_out = {name: ctx.alloc(np.dtype(t).itemsize * max(n, 1)) for name, t in shapes.items()}
+        bufs += [b for b in [d_acc] + list(d_out.values()) if b is not None]
+        out["totals"] = mpt_subtree_digests_dev(ctx, d_info, n, d_paths, d_depths, max_depth, d_keys, d_status, count,
+                                                d_leaf_frac if points else None, d_acc, *(d_out[name] for name in MPT_SUBTREE_OUTPUTS))
+        for name, t in shapes.items():
+            out[name] = d_out[name].download((n,), t)
+        if points:
+            out["w"], out["weierstrass"] = curve_emit_dev(ctx, d_acc, n)
+        return out
+    finally:
+        for b in bufs:
+            b.free()
+
+
+def values_extraction_public_inputs(hashes, info, keys, out, dm=None):
+    """The 96 public inputs (public_inputs.rs:23-36) every node's values-extraction proof exposes, [n_nodes][96] uint64: H, the node's
+    hash as eight little-endian u32; K, the 64 nibbles of the key of proof via[x]; T, the key pointer after the node, which counts
+    from the leaf's end (mpt_sequential/key.rs:18-55: 63 at the start, minus the nibbles of the node and of everything below it, so
+    entered - 1, and p - 1 at a root); DV, the node's values digest (Weierstrass, 11 limbs); DM, the table's metadata digest `dm`
+    (11 limbs; None: the neutral point); N, the leaves below the node. hashes [n_nodes][32] and keys [count][32] are those of the
+    walk, `out` what mpt_subtree_digests returned. info [n_nodes] is held against the table's size and otherwise not read: T
+    follows from `entered` alone. An UNREACHED node's K and T are zero."""
+    hashes, keys = np.ascontiguousarray(hashes, dtype=np.uint8).reshape(-1, 32), np.ascontiguousarray(keys, dtype=np.uint8).reshape(-1, 32)
+    n = hashes.shape[0]
+    if len(info) != n or any(len(out[name]) != n for name in ("weierstrass", "n_leaves", "via", "entered")):
+        raise ValueError("one hash, info word and output row per node are needed")
+    rows = np.zeros((n, PUBLIC_INPUT_LEN), dtype=np.uint64)
+    rows[:, :8] = hashes.view("<u4")
+    reached = np.flatnonzero(out["via"] != MPT_NO_NODE)
+    k = keys[out["via"][reached]]
+    rows[reached, 8:72:2], rows[reached, 9:72:2] = k >> 4, k & 15
+    rows[reached, 72] = (out["entered"][reached].astype(np.uint64) + np.uint64(GOLDILOCKS_P - 1)) % np.uint64(GOLDILOCKS_P)
+    rows[:, 73:84] = out["weierstrass"]
+    rows[:, 84:95] = np.asarray(NEUTRAL_WEIERSTRASS if dm is None else dm, dtype=np.uint64)
+    rows[:, 95] = out["n_leaves"]
+    return rows
+
+
+def storage_proof_tree(ctx, proofs, storage_root, slot, mapping_keys, table_info, extracted_column_identifiers, key_ids, evm_word=0,
+                       variant=POSEIDON2, dm=None):
+    """storage_proof_words carried on to every node of the trie: the MPT keys, the nodes opened and the paths walked from
+    storage_root (32 bytes or a DeviceBuffer that starts with them), the leaves' values digests, and from them the digest and the
+    leaf count of every node the proofs show (mpt_subtree_digests). Every hash, walk and sum runs on the device. The host does the
+    bookkeeping between them: it downloads the MPT keys and the info words of the distinct nodes and indexes the proofs by
+    position with them (MptProofSet.from_proofs(by_position=True, mpt_keys=..., node_info=...)). Returns (words [count][32], the
+    leaves' digests as storage_proof_words returns them, the per-node outputs of mpt_subtree_digests by name with hashes and info, the
+    public-input rows [n_nodes][96] of values_extraction_public_inputs under the metadata digest `dm`); raises ValueError naming
+    the first failing proof, its status and level."""
+    count, n_keys = len(proofs), len(mapping_keys)
+    if len(key_ids) != n_keys or any(len(k) != count for k in mapping_keys):
+        raise ValueError("one key identifier per mapping level and one key per proof and level are needed")
+    info, n = extracted_first(table_info, extracted_column_identifiers)
+    front = info[:n]
+    d_keys = ctx.to_device(_keys(*mapping_keys)) if n_keys else None
+    d_mpt, d_words, d_frac = ctx.alloc(32 * max(count, 1)), ctx.alloc(32 * max(count, 1)), ctx.alloc(160 * max(count, 1))
+    bufs = [b for b in (d_keys, d_mpt, d_words, d_frac) if b is not None]
+    try:
+        if storage_slot_keys_dev(ctx, slot, None, d_keys, n_keys, evm_word, count, None, d_mpt, None):
+            raise OverflowError("location + evm_word leaves 256 bits")
+        mpt_keys = d_mpt.download((count, 32), np.uint8)
+        # every distinct node is hashed and opened once, over the table by bytes; the table by position repeats those rows
+        by_bytes = MptProofSet.from_proofs(proofs)
+        rows, lens = rows_at_stride(by_bytes.nodes)
+        n_bytes = len(lens)
+        bufs += [ctx.to_device(rows), ctx.to_device(lens), ctx.alloc(32 * max(n_bytes, 1)), ctx.alloc(4 * max(n_bytes, 1))]
+        mpt_open_nodes_dev(ctx, bufs[-4], rows.shape[1], bufs[-3], n_bytes, bufs[-2], bufs[-1])
+        hashes, words = bufs[-2].download((n_bytes, 32), np.uint8), bufs[-1].download((n_bytes,), np.uint32)
+        ps = MptProofSet.from_proofs(proofs, by_position=True, mpt_keys=mpt_keys, node_info=dict(zip(by_bytes.nodes, words.tolist())))
+        where = {node: j for j, node in enumerate(by_bytes.nodes)}
+        src = np.array([where[node] for node in ps.nodes], dtype=np.int64)
+        rows, lens, hashes, words = rows[src], lens[src], hashes[src], words[src]
+        n_nodes, max_depth = len(lens), ps.paths.shape[1]
+        for a in (rows, lens, ps.paths, ps.depths, hashes, words):
+            bufs.append(ctx.to_device(a))
+        d_nodes, d_lens, d_paths, d_depths, d_hashes, d_info = bufs[-6:]
+        d_root, _ = _device_bytes32(ctx, storage_root, count, bufs)
+        bufs += [ctx.alloc(4 * max(count, 1)), ctx.alloc(4 * max(count, 1))]
+        d_status, d_level = bufs[-2:]
+        mpt_verify_paths_dev(ctx, d_nodes, rows.shape[1], d_lens, d_hashes, d_info, n_nodes, d_paths, d_depths, max_depth, d_mpt, count, d_root, 0,
+                             MPT_VALUE_WORD, d_status, d_level, d_words)
+        _first_failure({"status": d_status.download((count,), np.uint32), "fail_level": d_level.download((count,), np.uint32)}, "storage proof")
+        digests = leaf_values_digests_dev(ctx, variant, [c.identifier for c in front], [c.layout() for c in front], len(table_info), d_words,
+                                          d_keys, key_ids, evm_word, count, d_frac, each=True, total=True)
+        tree = mpt_subtree_digests(ctx, ps, d_mpt, d_status, d_frac, d_info=d_info)
+        tree["hashes"], tree["info"] = hashes, words
+        return d_words.download((count, 32), np.uint8), digests, tree, values_extraction_public_inputs(tree["hashes"], tree["info"], mpt_keys, tree, dm)
     finally:
         for b in bufs:
             b.free()
