@@ -906,6 +906,20 @@ int mp2g_prover_lookup_wires_dev(mp2g_prover* pr, const uint32_t* n_lookups /* [
 int mp2g_eval_gate_constraints(mp2g_ctx* ctx, const mp2g_gate* gates, uint32_t n_gates, uint32_t num_selectors,
                                const uint64_t* consts, uint32_t num_constants, const uint64_t* wires, uint32_t wires_w,
                                uint64_t npts, const uint64_t pi_hash[4], uint64_t* out);
+/* The quotient-side sibling: the alpha-reduced gate term of prove()'s quotient, sum_j alpha_{b,a}^j C_j, for B proofs at
+ * N = 2^log_points points each (1 <= log_points <= 24), computed by the launchers prove() itself runs on the LDE (the per-kind
+ * kernels, the fused launch of the light gates, one alpha-power table per batch). Host pointers: consts [num_constants][N]
+ * shared by the batch -- selectors, then num_lookup_selectors rows the gates never read, then the gate constants --,
+ * wires [B][wires_w][N], alphas [B][nc] with nc = 1 or 2, pi_hash [B][4], out [B][nc][N].
+ * POINT ORDER: column p of consts / wires is memory column p of the prover's bit-reversed LDE matrices; its result lands at
+ * out[b][a][bitrev(p, log_points)], the natural order the quotient is divided and committed in.
+ * Refused before anything is launched, with `out` untouched: a word >= p in consts, wires, alphas or pi_hash (the kernels take
+ * canonical words only), nc outside 1..2, B = 0, a gate table mp2g_prover_set_gates would refuse. A table without constraints
+ * (Noops, lookup gates) is valid and gives zeros. */
+int mp2g_eval_gate_constraints_lde(mp2g_ctx* ctx, const mp2g_gate* gates, uint32_t n_gates, uint32_t num_selectors,
+                                   uint32_t num_lookup_selectors, const uint64_t* consts, uint32_t num_constants,
+                                   const uint64_t* wires, uint32_t wires_w, uint32_t log_points, uint32_t B, const uint64_t* alphas,
+                                   uint32_t nc, const uint64_t* pi_hash, uint64_t* out);
 
 /* ---- batched proof verification on the device (csrc/verifier.hip) --------------------------------
  * Replaces [dep] plonky2 plonk/verifier.rs verify / verify_with_challenges and fri/verifier.rs verify_fri_proof -- the other half

@@ -490,6 +490,24 @@ def eval_gate_constraints(ctx, gates, num_selectors, consts, wires, pi_hash):
     return out
 
 
+def eval_gate_constraints_lde(ctx, gates, num_selectors, consts, wires, alphas, pi_hash, num_lookup_selectors=0, out=None):
+    """The gate term of the quotient, sum_j alpha^j C_j, by the launchers prove() runs on the LDE: consts [num_constants][N]
+    (selectors, num_lookup_selectors unread rows, gate constants), wires [B][w][N], alphas [B][nc], pi_hash [B][4]
+    -> [B][nc][N], N a power of two. Column p of the inputs is memory column p of the bit-reversed LDE; its result is at
+    [b][a][bitrev(p)]. Words >= p are refused. out: an array to fill instead of a new one."""
+    c, w, al, ph = _arr(consts), _arr(wires), _arr(alphas), _arr(pi_hash)
+    B, N, nc = w.shape[0], w.shape[-1], al.shape[-1]
+    if w.ndim != 3 or al.shape != (B, nc) or ph.shape != (B, 4) or c.ndim != 2 or c.shape[1] != N or N < 2 or N & (N - 1):
+        raise ValueError("consts [.][N], wires [B][.][N], alphas [B][nc], pi_hash [B][4] with N = 2^k >= 2")
+    if out is None:
+        out = np.zeros((B, nc, N), dtype=np.uint64)
+    if out.dtype != np.uint64 or not out.flags.c_contiguous or out.size < B * nc * N:
+        raise ValueError("out: a contiguous uint64 array of at least B * nc * N words")
+    _ck(load().mp2g_eval_gate_constraints_lde(ctx.h, gate_array(gates), len(gates), num_selectors, num_lookup_selectors, _p(c), c.shape[0],
+                                              _p(w), w.shape[1], N.bit_length() - 1, B, _p(al), nc, _p(ph), _p(out)))
+    return out
+
+
 class BatchedProver:
     """mp2g_prover: `batch` same-shape proofs per call, device resident."""
 

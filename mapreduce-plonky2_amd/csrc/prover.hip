@@ -786,6 +786,51 @@ int mp2g_eval_gate_constraints(mp2g_ctx* c, const mp2g_gate* gates, uint32_t n_g
   return 0;
 }
 
+// index of the first word >= p, or n
+static size_t first_non_canonical(const uint64_t* v, size_t n) {
+  size_t i = 0;
+  while (i < n && v[i] < GL_P) i++;
+  return i;
+}
+int mp2g_eval_gate_constraints_lde(mp2g_ctx* c, const mp2g_gate* gates, uint32_t n_gates, uint32_t num_selectors,
+                                   uint32_t num_lookup_selectors, const uint64_t* consts, uint32_t num_constants, const uint64_t* wires,
+                                   uint32_t wires_w, uint32_t log_points, uint32_t B, const uint64_t* alphas, uint32_t nc,
+                                   const uint64_t* pi_hash, uint64_t* out) {
+  NEED(nc >= 1 && nc <= 2, "nc must be 1 or 2");
+  NEED(B >= 1 && B <= 65535, "B must be in 1..65535");
+  NEED(log_points >= 1 && log_points <= 24, "log_points must be in 1..24");
+  NEED(n_gates >= 1 && n_gates <= MP2G_MAX_GATES, "1..MP2G_MAX_GATES gates");
+  NEED(c && gates && consts && wires && alphas && pi_hash && out, "ctx/pointers");
+  GateTable t;
+  const char* msg = gate_table_make(gates, n_gates, num_selectors, num_lookup_selectors, num_constants, wires_w, t, nullptr);
+  if (msg) return fail("invalid gate table: %s", msg);
+  const size_t N = (size_t)1 << log_points, cw = (size_t)num_constants * N, ww = (size_t)B * wires_w * N;
+  const size_t aw = (size_t)B * nc, pw = (size_t)B * 4, qw = (size_t)B * nc * N;
+  const struct { const char* name; const uint64_t* v; size_t n; } ins[] = {
+      {"consts", consts, cw}, {"wires", wires, ww}, {"alphas", alphas, aw}, {"pi_hash", pi_hash, pw}};
+  for (const auto& in : ins) {
+    const size_t i = first_non_canonical(in.v, in.n);
+    if (i < in.n) return fail("%s: word %zu is not canonical (>= p)", in.name, i);
+  }
+  DevBuf dc, dw, da, dp, dapw, dq;
+  CK(dc.alloc(cw * sizeof(u64)));
+  CK(dw.alloc(ww * sizeof(u64)));
+  CK(da.alloc(aw * sizeof(u64)));
+  CK(dp.alloc(pw * sizeof(u64)));
+  CK(dapw.alloc((size_t)B * 2 * MP2G_MAX_GATE_CONSTRAINTS * sizeof(u64)));
+  CK(dq.alloc(qw * sizeof(u64)));
+  CK(hipMemcpyAsync(dc.p, consts, cw * sizeof(u64), hipMemcpyHostToDevice, c->stream));
+  if (ww) CK(hipMemcpyAsync(dw.p, wires, ww * sizeof(u64), hipMemcpyHostToDevice, c->stream));  // a table of Noops may come without wires
+  CK(hipMemcpyAsync(da.p, alphas, aw * sizeof(u64), hipMemcpyHostToDevice, c->stream));
+  CK(hipMemcpyAsync(dp.p, pi_hash, pw * sizeof(u64), hipMemcpyHostToDevice, c->stream));
+  // what prove() runs between the alphas and quotient_perm_values
+  CK(alpha_powers(c->stream, B, da.p, nc, nc, dapw.p));
+  CK(gate_constraints_lde(c->stream, B, t, dc.p, dw.p, (u64)wires_w * N, log_points, dapw.p, nc, dp.p, dq.p));
+  CK(hipMemcpyAsync(out, dq.p, qw * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+  CK(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
 // ---- granular entry points over PolynomialBatch handles ----------------------------------------
 int mp2g_batch_eval_ext(const mp2g_batch* b, const uint64_t point[2], uint64_t* out) {
   NEED(b && point && out, "batch/point/out");
